@@ -2,13 +2,19 @@
 """Headline benchmark: greedy coreset iterations/sec on the workloads BASELINE.json names.
 
     python bench.py [--gpus N --steps K --warmup W] [--config c4|c2|c3|c5] [--alg fw|giga|omp --rows N --dim d]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one greedy iteration: one pass of the hot path over the resident rows.
 
+A plain run sets up, warms up, times the K steps and prints the line.  --full also runs everything beside the headline:
+the CPU baseline, the side legs named below, the default line's other configs and re-weight legs, and on multi-rank runs
+the other exchange mode and the one-shard leg.  --dump-outputs DIR writes what the timed steps computed (the coreset after
+the last step and the trace of the timed steps) as DIR/<name>.npy in float64.
+
   c4 (default)  BASELINE.json configs[3] and the metric's own config: synthetic randn N = 10,000,000, d = 512,
-                Frank-Wolfe, row-sharded over --gpus ranks (total N fixed => "scaling": "strong").  On one GPU the line
-                also carries two side legs of the same workload, neither of them the headline: rows stored in fp64
+                Frank-Wolfe, row-sharded over --gpus ranks (total N fixed => "scaling": "strong").  With --full, on one GPU
+                the line also carries two side legs of the same workload, neither of them the headline: rows stored in fp64
                 (`exact_mode_its`: the reference's arithmetic end to end) and rows stored in fp16 (`f16_rows_its`, with
                 `f16_rows_same_selections`: whether every selection equals the fp32 run's).
   c2            configs[1]: synthetic randn N = 1,000,000, d = 256, GIGA.
@@ -89,7 +95,15 @@ def parse():
                     help="c5: column sums of the full-data projection by the fp64-MFMA projection kernel (101 per greedy step), "
                          "or in closed form from the one-time (D+1)x(D+1) moments of the data (linear-regression family)")
     ap.add_argument("--features", type=int, default=10, help="c3: regression features D (simple_lr/main.py:24)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline (CPU baseline, fp64 / fp16 row legs, the default line's "
+                         "other configs and re-weight legs, multi-rank collective and one-shard legs); the --no-* switches "
+                         "still drop single legs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float64)")
     a = ap.parse_args()
+    if not a.full:      # a plain run: set-up, warm-up, the timed steps, the line
+        a.no_cpu_baseline = a.no_exact_mode = a.no_f16_leg = a.no_side_legs = a.no_one_rank_leg = True
     explicit = a.config is not None
     if a.config is None:
         a.config = "c4"
@@ -285,6 +299,22 @@ def wait_for_rank0(dist, rank, key):
         sys.stderr.write("bench.py: rank %d: store wait unavailable (%s)\n" % (rank, e))
 
 
+DUMP_BYTES = 64 << 20     # --dump-outputs: bytes written in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy in float64 (row indices stay exact below 2^53).  An array larger
+    than its share of DUMP_BYTES is cut to a fixed, seeded sample of its rows, kept in their order."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            keep = share // (a.nbytes // a.shape[0])
+            a = a[np.sort(np.random.RandomState(0).choice(a.shape[0], keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # =====================================================================================================================
 # greedy sparse-NNLS workloads (c2, c3, c4, ad hoc): step = one greedy iteration of HilbertCoreset's solver
 # =====================================================================================================================
@@ -359,7 +389,7 @@ def load_logistic(args, torch, dist, world, solver, info):
     info.update({"laplace_fit_s": t1 - t0, "projection_s": t2 - t1, "ingest_s": t3 - t2, "features": args.features,
                  "projection_kernel_ms": pms, "projection_kernel_gelem_per_s": (hi - lo) * args.dim / max(pms, 1e-9) / 1e6,
                  "row_norm_min": float(nrm.min()), "row_norm_max": float(nrm.max())})
-    sample = vecs[:min(args.cpu_rows or 1_000_000, hi - lo)].cpu().numpy() if lo == 0 else None
+    sample = vecs[:min(args.cpu_rows or 1_000_000, hi - lo)].cpu().numpy() if lo == 0 and not args.no_cpu_baseline else None
     del vecs, Z
     return sample
 
@@ -435,6 +465,11 @@ def run_snnls(args, torch, dist, nat, world, rank, local_rank):
     elapsed, tr, scan_ms, scan_launches, every = timed(solver, args.warmup, args.steps)
     sel, err, status = tr
     steps_done = len(sel)
+    if args.dump_outputs and rank == 0:
+        # what a caller of the solver receives: the timed steps' trace and the coreset after the last of them
+        idx, w = solver.sparse_weights()
+        dump_outputs(args.dump_outputs, {"selections": sel, "errors": err, "status": status,
+                                         "coreset_idcs": idx, "coreset_wts": w})
     out = None
     # device-stamped exchange step of the timed region (mailbox mode): every rank's own view, worst rank reported
     xstat = None
@@ -748,6 +783,9 @@ def run_sparsevi(args, torch, dist, nat, world, rank, local_rank):
         if host_leg:
             wait_for_rank0(dist, rank, "bench_host_legs_done_c5_%s" % args.colsum)      # (rank 0 times the oracle meanwhile)
         return None
+    if args.dump_outputs:
+        wts, pts, idcs = alg.get()      # what a caller of SparseVICoreset receives after the last timed step
+        dump_outputs(args.dump_outputs, {"coreset_wts": wts, "coreset_pts": pts, "coreset_idcs": idcs})
     # (the k-point core projections are launches too: their flops and time are in the totals, weight ~1e-5)
     per_launch_flops = 2.0 * (hi - lo) * D * S
     achieved = flops / (kms * 1e-3) / 1e12 if kms > 0 else 0.0
@@ -846,7 +884,7 @@ def side_legs(args, out, torch, dist, nat):
         a.config, a.kind, a.alg, a.rows, a.dim, a.what, a.adhoc = name, c["kind"], c["alg"], c["rows"], c["dim"], c["what"], False
         a.steps = {"sparsevi": 3, "logistic": 100}.get(a.kind, 300)
         a.warmup = {"sparsevi": 1, "logistic": 20}.get(a.kind, 30)
-        a.no_cpu_baseline, a.no_exact_mode, a.dtype = True, True, "float32"
+        a.no_cpu_baseline, a.no_exact_mode, a.dtype, a.dump_outputs = True, True, "float32", None
         for k, v in over.items():
             setattr(a, k, v)
         gc.collect()
@@ -1181,7 +1219,7 @@ def main():
         import copy
         import gc
         a2 = copy.copy(args)
-        a2.colsum, a2.no_cpu_baseline = "moments", True
+        a2.colsum, a2.no_cpu_baseline, a2.dump_outputs = "moments", True, None
         gc.collect()
         torch.cuda.empty_cache()
         r2 = run_sparsevi(a2, torch, dist, nat, world, rank, local_rank)

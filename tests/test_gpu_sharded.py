@@ -314,6 +314,33 @@ def test_bench_contract_one_and_two_ranks():
     assert four["config"]["final_error"] is not None
 
 
+def test_bench_plain_run_dumps_what_the_timed_steps_computed(tmp_path):
+    """A plain run times the headline alone (no CPU baseline, no legs beside it); --dump-outputs writes the timed steps' trace
+    and the coreset after the last step in float64, the same for two runs with the same arguments and for one and two ranks."""
+    args = ["--rows", "300000", "--dim", "64", "--steps", "25", "--warmup", "5"]
+    one, _ = _run_bench({}, 1, args + ["--dump-outputs", str(tmp_path / "a")])
+    assert one["steps"] == 25 and one["config"]["iterations_run"] == 25 and one["ms_per_step"] > 0
+    assert "cpu_baseline" not in one and "speedup_vs_cpu_baseline" not in one
+    again, _ = _run_bench({}, 1, args + ["--dump-outputs", str(tmp_path / "b")])
+    two, _ = _run_bench({"BENCH_SHARE_GPU": "1"}, 2, args + ["--dump-outputs", str(tmp_path / "c")])
+    assert "collective_leg" not in two["config"] and "one_rank_its" not in two
+    for name in ("selections", "errors", "status", "coreset_idcs", "coreset_wts"):
+        a = np.load(tmp_path / "a" / (name + ".npy"))
+        assert a.dtype == np.float64 and a.ndim == 1, name
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+        assert np.array_equal(a, np.load(tmp_path / "c" / (name + ".npy"))), name
+    sel, err = np.load(tmp_path / "a" / "selections.npy"), np.load(tmp_path / "a" / "errors.npy")
+    assert len(sel) == 25 and err[-1] == one["config"]["final_error"]
+    idx, w = np.load(tmp_path / "a" / "coreset_idcs.npy"), np.load(tmp_path / "a" / "coreset_wts.npy")
+    assert len(idx) == len(w) >= 1 and (w > 0).any()
+    # SparseVI: the coreset SparseVICoreset.get() returns after the last timed greedy step
+    svi = ["--config", "c5", "--rows", "100000", "--dim", "64", "--opt-itrs", "5", "--steps", "2", "--warmup", "1"]
+    line, _ = _run_bench({}, 1, svi + ["--dump-outputs", str(tmp_path / "svi")])
+    assert line["steps"] == 2 and "steps_s_moments" not in line
+    wts, pts, idcs = (np.load(tmp_path / "svi" / (n + ".npy")) for n in ("coreset_wts", "coreset_pts", "coreset_idcs"))
+    assert len(wts) == len(idcs) == pts.shape[0] >= 1 and pts.ndim == 2
+
+
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus N` with NO launcher around it starts N ranks itself (torch.distributed.run on 127.0.0.1) and
     prints one line with n_gpus == N; without enough devices (and without the share-one-GPU test switch) it exits non-zero
@@ -321,7 +348,7 @@ def test_bench_launches_its_own_ranks():
     import json
     import subprocess
     bench = os.path.join(ROOT, "bench.py")
-    args = ["--rows", "300000", "--dim", "64", "--steps", "10", "--warmup", "5", "--no-cpu-baseline"]
+    args = ["--rows", "300000", "--dim", "64", "--steps", "10", "--warmup", "5", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     one, _ = _run_bench({}, 1, args)
     assert one["rccl_ranks"] == 1 and one["process_group"]["world_size"] == 1
@@ -569,7 +596,7 @@ def test_config4_geometry_as_eight_shards(tmp_path):
 def test_bench_contract_eight_ranks():
     """bench.py --gpus 8 under torchrun (ranks sharing the GPU): the SCALE contract end to end -- n_gpus, rows_per_gpu,
     exchange mode + probe, the device-stamped exchange wait -- and the same bits as one rank."""
-    args = ["--rows", "400000", "--dim", "64", "--steps", "40", "--warmup", "5", "--no-cpu-baseline"]
+    args = ["--rows", "400000", "--dim", "64", "--steps", "40", "--warmup", "5", "--no-cpu-baseline", "--full"]
     one, _ = _run_bench({}, 1, args)
     eight, _ = _run_bench({"BENCH_SHARE_GPU": "1"}, 8, args)
     assert eight["n_gpus"] == 8 and eight["config"]["exchange"] == "mailbox"
@@ -593,7 +620,7 @@ def test_bench_contract_eight_ranks():
 
 
 def test_multi_rank_line_carries_cpu_baseline_and_both_rooflines():
-    """`BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 10` with NO launcher: the line of a multi-rank run carries the CPU
+    """`BENCH_SHARE_GPU=1 python bench.py --gpus 2 --steps 10 --full` with NO launcher: the line of a multi-rank run carries the CPU
     baseline (rank 0 times the oracle while the other rank waits on the rendezvous store), the per-GPU and the aggregate
     roofline, and the same workload as one shard with the scaling efficiency against it."""
     import json
@@ -601,7 +628,7 @@ def test_multi_rank_line_carries_cpu_baseline_and_both_rooflines():
     bench = os.path.join(ROOT, "bench.py")
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     out = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "10", "--warmup", "5", "--rows", "300000", "--dim", "64",
-                          "--cpu-seconds", "2"], capture_output=True, text=True, timeout=900, env=dict(env, BENCH_SHARE_GPU="1"), cwd=ROOT)
+                          "--cpu-seconds", "2", "--full"], capture_output=True, text=True, timeout=900, env=dict(env, BENCH_SHARE_GPU="1"), cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:]

@@ -27,17 +27,17 @@ pmc() { # name counters cmd...
 }
 for part in $PARTS; do
 case $part in
-c4) kt bench_c4 python $R/bench.py ;;
+c4) kt bench_c4 python $R/bench.py --full ;;
 c4pmc) pmc scan_c4_fetch "FETCH_SIZE" python $R/bench.py --steps 20 --warmup 2 --no-cpu-baseline --no-exact-mode --no-f16-leg --no-side-legs
        python $R/tools/scan_traffic.py $O/scan_traffic.json fw_n10000000_d512_float32=$(find $O/raw_scan_c4_fetch -name "*.db" | head -1) ;;
 shards) for n in 5000192 2500608 1250304; do
          pmc scan_shard_${n}_fetch "FETCH_SIZE" python $R/bench.py --rows $n --dim 512 --alg fw --steps 20 --warmup 2 --no-cpu-baseline
          python $R/tools/scan_traffic.py $O/scan_traffic.json fw_n${n}_d512_float32=$(find $O/raw_scan_shard_${n}_fetch -name "*.db" | head -1)
        done ;;
-c2) kt bench_c2 python $R/bench.py --config c2 --steps 1000 --warmup 20
+c2) kt bench_c2 python $R/bench.py --config c2 --steps 1000 --warmup 20 --full
     pmc scan_c2_fetch "FETCH_SIZE" python $R/bench.py --config c2 --steps 20 --warmup 2 --no-cpu-baseline
     python $R/tools/scan_traffic.py $O/scan_traffic.json giga_n1000000_d256_float32=$(find $O/raw_scan_c2_fetch -name "*.db" | head -1) ;;
-c3) kt bench_c3 python $R/bench.py --config c3
+c3) kt bench_c3 python $R/bench.py --config c3 --full
     pmc scan_c3_fetch "FETCH_SIZE" python $R/bench.py --config c3 --steps 20 --warmup 2 --no-cpu-baseline
     python $R/tools/scan_traffic.py $O/scan_traffic.json omp_n1000000_d512_float32=$(find $O/raw_scan_c3_fetch -name "*.db" | head -1) ;;
 c5) kt bench_c5 python $R/bench.py --config c5 --steps 1 --warmup 1 --no-cpu-baseline --no-side-legs
@@ -59,8 +59,8 @@ fam) # the other two likelihood families at the shard shape (N=625k, D=300, S=25
      done; done ;;
 xch) # the two exchange modes, two ranks sharing this GPU (what a 1-GPU box can run): per-iteration cost next to one shard
      bash $R/tools/share_gpu_bench.sh 2 200000 512 fw 2000 > $O/exchange_modes_2ranks.txt 2>&1
-     [ -n "$XCH_ONLY_SMALL" ] || BENCH_SHARE_GPU=1 python $R/bench.py --gpus 2 --steps 300 --warmup 30 --no-cpu-baseline > $O/bench_c4_2ranks_shared_gpu.json 2> $O/bench_c4_2ranks_shared_gpu.err
-     [ -n "$XCH_ONLY_SMALL" ] || BENCH_SHARE_GPU=1 python $R/bench.py --gpus 8 --steps 100 --warmup 10 --no-cpu-baseline > $O/bench_c4_8ranks_shared_gpu.json 2> $O/bench_c4_8ranks_shared_gpu.err ;;
+     [ -n "$XCH_ONLY_SMALL" ] || BENCH_SHARE_GPU=1 python $R/bench.py --gpus 2 --steps 300 --warmup 30 --no-cpu-baseline --full > $O/bench_c4_2ranks_shared_gpu.json 2> $O/bench_c4_2ranks_shared_gpu.err
+     [ -n "$XCH_ONLY_SMALL" ] || BENCH_SHARE_GPU=1 python $R/bench.py --gpus 8 --steps 100 --warmup 10 --no-cpu-baseline --full > $O/bench_c4_8ranks_shared_gpu.json 2> $O/bench_c4_8ranks_shared_gpu.err ;;
 opt) kt optimize python $R/tools/optimize_bench.py
      pmc optimize_mfma "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE" python $R/tools/optimize_bench.py
      kt gram python $R/tools/gram_bench.py 400,512 999,512 1497,1024 2048,2048 4096,1024
