@@ -4,8 +4,9 @@
     alg = bc.HilbertCoreset(X, projector, snnls=bc.snnls.GIGA)
     alg.build(1000); wts, pts, idcs = alg.get()
 
-Namespace mirrors bayesiancoresets/__init__.py:1-2 for the classes on the greedy / SparseVI path (SURVEY.md section 8);
-``BatchPSVICoreset`` is out of scope: the name exists and raises NotImplementedError."""
+Namespace mirrors bayesiancoresets/__init__.py:1-2.  ``BatchPSVICoreset`` (the batch pseudocoreset)
+runs with a ``DeviceProjector`` only: its pseudo-point gradients are device kernels (csrc/psvi.hip), and any other
+projector raises NotImplementedError."""
 from .coreset import Coreset, HilbertCoreset, UniformSamplingCoreset, SparseVICoreset, BatchPSVICoreset, ShardedHilbertCoreset
 from .projector import BlackBoxProjector, Projector, DeviceProjector
 from .linreg_sampler import LinregPosteriorSampler

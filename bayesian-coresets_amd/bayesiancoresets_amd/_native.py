@@ -40,6 +40,7 @@ SYMBOLS = (
     "bcx_sparsevi_adam_step_ws", "bcx_sparsevi_adam_scratch_bytes", "bcx_standard_normal", "bcx_column_means",
     "bcx_center_rows", "bcx_row_sumsq", "bcx_project_write_points",
     "bcx_laplace_sampler", "bcx_laplace_sampler_ok", "bcx_laplace_sampler_lds_bytes",
+    "bcx_project_grad_points", "bcx_psvi_gradient", "bcx_psvi_gradient_scratch_bytes",
 )
 
 
@@ -174,6 +175,10 @@ def load():
     lib.bcx_laplace_sampler_lds_bytes.restype = ctypes.c_int64
     lib.bcx_laplace_sampler_lds_bytes.argtypes = [i32, i32]
     sigs["bcx_row_sumsq"] = [vp, vp, i64, i32, i64, vp]
+    sigs["bcx_project_grad_points"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp]
+    sigs["bcx_psvi_gradient"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp, i64, vp, dbl, vp, vp]
+    lib.bcx_psvi_gradient_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_psvi_gradient_scratch_bytes.argtypes = [i32, i32]
     sigs["bcx_linreg_posterior_draw_factored"] = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp]
     sigs["bcx_sparsevi_adam_step_ws"] = [vp, i32, i32, vp, dbl, vp, i64, vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, i32, vp, i64]
     lib.bcx_linreg_posterior_factor_scratch_bytes.restype = ctypes.c_int64

@@ -1,0 +1,90 @@
+"""Batch pseudocoreset variational inference (reference: bayesiancoresets/coreset/bpsvi.py:6-64).
+
+``build(sz)`` starts from ``sz`` distinct data points drawn at random (bpsvi.py:15-22), each with weight N / sz, and then
+moves the weights AND the points themselves by ``opt_itrs`` steps of projected ADAM (util/opt.py: only the weights are
+kept non-negative).  The objective's gradient at (w, P) needs, after the sampler has drawn S parameters at (w, P):
+
+* the column sums of the projected data (or of a fresh random sub-sample of it, scaled by N / n);
+* the projected pseudo-points (k x S) and the gradients of those projections with respect to the points (k x S x dz).
+
+With a ``DeviceProjector`` all of it is one call, ``psvi_gradient``: the data's column sums as SparseVI takes them (fused
+projection, or the closed form for the linear-regression family), the points' projection, and the pseudo-point gradient
+as two products on the matrix cores (csrc/psvi.hip) -- the k x S x dz tensor is never formed, and one device->host copy
+returns (wgrad, ugrad).  The host keeps the ADAM state, the sampler calls and the random draws, in the reference's order:
+``choice`` once per build, then per step the sampler (projector.update) and, with ``n_subsample_opt``, one ``randint``.
+A NumPy sampler therefore reproduces the reference's trajectory.
+
+There is no host path: any other projector raises NotImplementedError.  The Poisson family's gradient has D entries for
+points of D + 1 columns, where the reference fails reshaping it (bpsvi.py:56): ``build`` raises ValueError before any
+draw."""
+import numpy as np
+
+from .coreset import Coreset
+from ..util.opt import nn_opt
+from ..projector import DeviceProjector
+
+
+class BatchPSVICoreset(Coreset):
+    def __init__(self, data, ll_projector, opt_itrs, n_subsample_opt=None, step_sched=lambda i: 1.0 / (1.0 + i), **kw):
+        if not isinstance(ll_projector, DeviceProjector):
+            raise NotImplementedError("BatchPSVICoreset runs on the device only: it needs a bc.DeviceProjector (the pseudo-point "
+                                      "gradients are csrc/psvi.hip kernels; there is no host fallback)")
+        self.data = data
+        self.ll_projector = ll_projector
+        self.opt_itrs = opt_itrs
+        n = data.shape[0]
+        self.n_subsample_opt = None if n_subsample_opt is None else min(n, n_subsample_opt)    # bpsvi.py:11
+        self.step_sched = step_sched
+        super().__init__(**kw)
+
+    def _rows(self, idx):
+        """data[idx] as a host array (``data`` may be a device tensor)."""
+        rows = self._sub(idx)
+        if hasattr(rows, "detach"):
+            rows = rows.detach().cpu().numpy()
+        return np.array(rows, dtype=np.float64)
+
+    def _sub(self, idx):
+        """data[idx] where it lives (a device tensor is indexed on its device)."""
+        if hasattr(self.data, "detach"):
+            import torch
+            return self.data[torch.as_tensor(idx, device=self.data.device)]
+        return self.data[idx]
+
+    # ---- bpsvi.py:15-22 ----------------------------------------------------------------------------------------------
+    def _build(self, sz):
+        if self.ll_projector.family == "poisson":
+            raise ValueError("BatchPSVICoreset: the Poisson family's pseudo-point gradient has D entries for points of D + 1 "
+                             "columns (the reference fails at bpsvi.py:56 reshaping it)")
+        n = self.data.shape[0]
+        first = np.random.choice(n, size=sz, replace=False)        # every build starts afresh
+        self.pts = self._rows(first)
+        self.wts = n / sz * np.ones(sz)
+        self.idcs = -1 * np.ones(sz)                               # (a float array, as in the reference)
+        self._optimize()
+
+    # ---- bpsvi.py:42-60 ----------------------------------------------------------------------------------------------
+    def _optimize(self):
+        k, d = self.wts.shape[0], self.pts.shape[1]
+        prj, n, nsub = self.ll_projector, self.data.shape[0], self.n_subsample_opt
+
+        def grd(x):
+            w, p = x[:k], x[k:].reshape((k, d))
+            prj.update(w, p)                                       # bpsvi.py:26
+            if nsub is None:
+                pts, scaling = self.data, 1.0
+            else:
+                pts, scaling = self._sub(np.random.randint(n, size=nsub)), n / nsub       # bpsvi.py:34-36
+            if k == 0:
+                return np.zeros(0)
+            wgrad, ugrad = prj.psvi_gradient(pts, p, w, scaling, persistent=pts is self.data)
+            if ugrad.shape[1] != d:
+                raise ValueError("pseudo-point gradient has %d entries for points of %d columns" % (ugrad.shape[1], d))
+            return np.hstack((wgrad, ugrad.reshape(k * d)))
+
+        x0 = np.hstack((self.wts, self.pts.reshape(k * d)))
+        x = nn_opt(x0, grd, nn_idcs=np.arange(k), opt_itrs=self.opt_itrs, step_sched=self.step_sched)
+        self.wts, self.pts = x[:k], x[k:].reshape((k, d))
+
+    def error(self):
+        return 0.0   # as in the reference (bpsvi.py:62-63: the KL estimate is not implemented)

@@ -297,10 +297,9 @@ class DeviceProjector(Projector):
 
     def project(self, pts, grad=False):
         if grad:
-            # (projector.py:19-29 on the host, at the samples the device holds)
             if self.loglikelihood is None or self.grad_loglikelihood is None:
-                raise NotImplementedError("gradient projections are not on the device path: construct the projector with "
-                                          "loglikelihood= and grad_loglikelihood= host callbacks")
+                return self._project_grad_device(pts)
+            # (projector.py:19-29 on the host, at the samples the device holds)
             samples = self.theta.cpu().numpy()
             pts = np.atleast_2d(np.asarray(pts, dtype=np.float64))
             lls = self.loglikelihood(pts, samples)
@@ -315,6 +314,68 @@ class DeviceProjector(Projector):
         if N:
             self._launch(self._lib.bcx_project_write, self._common(Z) + [out.data_ptr(), S, None], Z)
         return out
+
+    def _grad_dz(self, Z):
+        D, _ = self._dims(Z)
+        return D + 1 if self._fam == self.FAMILIES["linreg"] else D
+
+    def _psvi_scratch(self, k, S):
+        need = int(self._lib.bcx_psvi_gradient_scratch_bytes(int(k), int(S)))
+        if need < 0:
+            raise ValueError("pseudo-point gradients: k = %d, S = %d outside 1 <= k <= 4096, 1 <= S <= 8192" % (k, S))
+        if getattr(self, "_psvi_work", None) is None or self._psvi_work.numel() * 8 < need:
+            self._psvi_work = self._torch.empty((need + 7) // 8, dtype=self._torch.float64, device=self.device)
+        return self._psvi_work
+
+    def _project_grad_device(self, pts):
+        """(lls, glls) of projector.py:19-27 as device fp64 tensors (k x S and k x S x dz): lls centred over the samples,
+        glls centred over its last axis, the coordinates of the point, as the reference does (csrc/psvi.hip)."""
+        torch = self._torch
+        P = self._dev(pts)
+        k, S = P.shape[0], self.theta.shape[0]
+        dz = self._grad_dz(P)
+        lls = torch.empty((k, S), dtype=torch.float64, device=self.device)
+        glls = torch.empty((k, S, dz), dtype=torch.float64, device=self.device)
+        if k:
+            common = self._common(P)
+            self._launch(self._lib.bcx_project_write_points, common + [lls.data_ptr(), S, 1], P)
+            work = self._psvi_scratch(k, S)
+            self._check(self._lib.bcx_project_grad_points(*(common + [glls.data_ptr(), work.data_ptr()])))
+        return lls, glls
+
+    def psvi_gradient(self, pts, core, w, scaling=1.0, persistent=True):
+        """One gradient of BatchPSVI's objective (bpsvi.py:47-55) with ONE device->host copy: ``(wgrad, ugrad)`` as host
+        arrays (k and k x dz), at the current samples.  ``pts``: the data or a sub-sample of it (its column sums are taken
+        as ``project_colsum`` takes them: the closed form for the linear-regression family on the standing data set,
+        the fused projection otherwise; ``persistent``: see ``_moments_for``); ``core``: the k pseudo-points (k x (D+1),
+        ndarray or device tensor), ``w`` their weights, ``scaling`` the sub-sample's N / n."""
+        torch = self._torch
+        if self._world > 1:
+            raise NotImplementedError("row-sharded BatchPSVI is not provided")
+        Z = self._dev(pts)
+        C = self._dev(core)
+        k, S = C.shape[0], self.theta.shape[0]
+        dz = self._grad_dz(C)
+        if k == 0:
+            return np.zeros(0), np.zeros((0, dz))
+        need = S * (k + 1) + S + k + k * dz
+        if getattr(self, "_psvi_buf", None) is None or self._psvi_buf.numel() < need:
+            self._psvi_buf = torch.empty(need, dtype=torch.float64, device=self.device)
+        buf = self._psvi_buf
+        col, cv = buf[:S], buf[S:S * (k + 1)]
+        out = buf[S * (k + 1):need]
+        if self._moments_for(pts, Z, persistent) is not None:
+            self._colsum_from_moments(Z, out=col)
+        else:
+            self._colsum_projected(Z, out=col)
+        common = self._common(C)
+        self._launch(self._lib.bcx_project_write_points, common + [cv.data_ptr(), S, 1], C)
+        wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.device)
+        work = self._psvi_scratch(k, S)
+        self._check(self._lib.bcx_psvi_gradient(*(common + [col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(), float(scaling),
+                                                            out.data_ptr(), work.data_ptr()])))
+        h = out.cpu().numpy()
+        return h[S:S + k].copy(), h[S + k:].reshape(k, dz).copy()
 
     def project_uncentred(self, pts):
         """The raw log-likelihoods ``loglikelihood(pts, samples)`` (N x S device tensor) WITHOUT the row-mean

@@ -1,0 +1,300 @@
+// psvi.hip -- the pseudo-point gradient of the batch pseudocoreset (BatchPSVI: coreset/bpsvi.py:42-60 of the reference, with
+// projector.py:19-27 and the family gradients of examples/common/model_lr.py:50-57, model_linreg.py:12-17, model_poiss.py:58-67).
+//
+// In every family the gradient of a point's log-likelihood with respect to the point is a scalar times the parameter:
+//     glls[i, s, :] = c(i, s) * tth_s,   tth_s = theta_s (logistic, Poisson) or [theta_s, 1] (linear regression, dz = D + 1),
+// with c from t = x_i . theta_s:  logistic  m = -t, c = e^m / (1 + e^m) for m < 100, else 1;
+//                                 linreg    c = (y_i - t) / sigsq;
+//                                 Poisson   s = log(max(t, 0) + log1p(e^-|t|)) for t > -100, else t;
+//                                           c = (y_i e^-s - 1)(1 - e^-e^s) where e^s > 1e-15, else y_i - e^s.
+// projector.py:26 centres glls over its LAST axis (the coordinates of the point), so the centred gradient is
+//     c(i, s) (tth_s - mean_j tth_s[j])
+// and the pseudo-point gradient of one ADAM step, bpsvi.py:51-55,
+//     ugrad = -diag(w) / S . (C o 1 resid^T) . Tc,      Tc[s, :] = tth_s - mean_j tth_s[j]
+// is two products of k x S x D; the k x S x dz tensor of the reference is never formed.
+//
+//   psvi_prep_kernel   resid = scaling colsum - w^T corevecs (bpsvi.py:50) and the coordinate means of tth_s
+//   psvi_wgrad_kernel  wgrad = -corevecs resid / S (bpsvi.py:51)
+//   psvi_coef_kernel   P[:, :D] Theta^T on v_mfma_f64_16x16x4_f64 (operands from global memory as proj.hip's 32 x 32-block
+//                      kernel stages them), the family's coefficient in the epilogue, times resid[s] (or not: the gradient write)
+//   psvi_ugrad_kernel  (C o resid) . Tc on v_mfma_f64_16x16x4_f64, Tc formed as the operand is read, times -w_i / S
+//   psvi_gwrite_kernel the centred k x S x dz gradients themselves (project(P, grad=True)): memory bound
+// Every sum has one fixed order and no atomics: the results are the same bit for bit from run to run.  The coefficients use
+// the device libm (exp / log / log1p): there are k x S of them, not N x S, so the table forms of proj_math.h save nothing
+// measurable here, and the libm forms stay closer to NumPy's.
+#include <string>
+#include "bcx_internal.h"
+#include "dev_util.h"
+
+enum { PS_LOGISTIC = 0, PS_POISSON = 1, PS_LINREG = 2 };
+
+void bcx_project_set_error(const std::string& msg);   // proj.hip: the message bcx_project_last_error() returns
+
+typedef double ps4d __attribute__((ext_vector_type(4)));
+
+template <int FAM>
+static __device__ __forceinline__ double psvi_coef(double t, double y, double rsig) {
+  if (FAM == PS_LOGISTIC) {                                    // model_lr.py:52-56
+    const double m = -t;
+    if (m < 100.0) {
+      const double e = exp(m);
+      return e / (1.0 + e);
+    }
+    return 1.0;
+  } else if (FAM == PS_POISSON) {                              // model_poiss.py:36-41 (compute_s), 62-66
+    double s = t;
+    if (s > -100.0) s = log(fmax(s, 0.0) + log1p(exp(-fabs(s))));
+    const double es = exp(s);
+    if (es > 1e-15) return (y * exp(-s) - 1.0) * (1.0 - exp(-es));
+    return y - es;
+  } else {                                                     // model_linreg.py:17
+    return rsig * (y - t);
+  }
+}
+
+// resid[s] = scaling colsum[s] - sum_i w_i cv[i, s] (cv == nullptr: resid untouched) and tmean[s] = mean_j tth_s[j].
+// A workgroup takes 16 columns; its 16 row slices (i = slice mod 16) are summed in a fixed order.
+__global__ __launch_bounds__(256) void psvi_prep_kernel(int k, int S, const double* __restrict__ colsum, double scaling,
+                                                        const double* __restrict__ cv, int64_t ldcv, const double* __restrict__ w,
+                                                        double* __restrict__ resid, const double* __restrict__ theta, int64_t ldt,
+                                                        int D, int dz, double* __restrict__ tmean) {
+  __shared__ double part[16][17];
+  const int c = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  const int s = blockIdx.x * 16 + c;
+  double acc = 0.0;
+  if (cv && s < S) {
+#pragma unroll 4
+    for (int i = sl; i < k; i += 16) acc = fma(w[i], cv[(int64_t)i * ldcv + s], acc);
+  }
+  part[sl][c] = acc;
+  double m = 0.0;
+  if (sl == 1 && s < S) {                                      // (another slice than the one that combines below)
+    const double* tp = theta + (int64_t)s * ldt;
+    for (int j = 0; j < D; ++j) m += tp[j];
+    if (dz > D) m += 1.0;
+    tmean[s] = m / (double)dz;
+  }
+  __syncthreads();
+  if (sl == 0 && cv && s < S) {
+    double t = part[0][c];
+    for (int q = 1; q < 16; ++q) t += part[q][c];
+    resid[s] = scaling * colsum[s] - t;
+  }
+}
+
+// wgrad[i] = -(cv[i, :] . resid) / S, one workgroup per row
+__global__ __launch_bounds__(256) void psvi_wgrad_kernel(int S, const double* __restrict__ cv, int64_t ldcv,
+                                                         const double* __restrict__ resid, double* __restrict__ wgrad) {
+  __shared__ double scratch[BCX_SCRATCH];
+  const double* row = cv + (int64_t)blockIdx.x * ldcv;
+  double v[1] = {0.0};
+  for (int s = threadIdx.x; s < S; s += 256) v[0] = fma(row[s], resid[s], v[0]);
+  block_allsum<1>(v, scratch);
+  if (threadIdx.x == 0) wgrad[blockIdx.x] = -v[0] / (double)S;
+}
+
+// C[i, s] = c(i, s) (* resid[s]) for a 32 x 32 block per workgroup, one 16 x 16 tile per wave.  Lane (li = lane % 16,
+// lk = lane / 16) feeds row li's values 8 lk .. 8 lk + 7 of each run of 32 of the inner dimension, one per MFMA step (both
+// operands take the inner index in the same order).  Accumulator register r: (row lk + 4 r, column li) of the wave's tile.
+template <int FAM>
+__global__ __launch_bounds__(256) void psvi_coef_kernel(const double* __restrict__ P, int k, int64_t ldp, int D, int ycol,
+                                                        const double* __restrict__ theta, int S, int64_t ldt, double rsig,
+                                                        const double* __restrict__ resid, double* __restrict__ C) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 15, lk = lane >> 4, rb = wave >> 1, cb = wave & 1;
+  const int arow = blockIdx.x * 32 + rb * 16 + li, bcol = blockIdx.y * 32 + cb * 16 + li;
+  const bool aok = arow < k, bok = bcol < S;
+  const double* ap = P + (int64_t)(aok ? arow : 0) * ldp;
+  const double* bp = theta + (int64_t)(bok ? bcol : 0) * ldt;
+  ps4d acc = (ps4d){0.0, 0.0, 0.0, 0.0};
+  for (int kb = 0; kb < D; kb += 32) {
+    double xa[8], xb[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int kk = kb + 8 * lk + q;
+      const bool ok = kk < D;
+      const double a = ap[ok ? kk : 0], b = bp[ok ? kk : 0];
+      xa[q] = (ok && aok) ? a : 0.0;
+      xb[q] = (ok && bok) ? b : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[t], xb[t], acc, 0, 0, 0);
+  }
+  const int col = bcol;
+  const double rs = (resid && bok) ? resid[col] : 1.0;
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = blockIdx.x * 32 + rb * 16 + lk + 4 * r;
+    if (row < k && bok) {
+      const double y = FAM == PS_LOGISTIC ? 0.0 : P[(int64_t)row * ldp + ycol];
+      const double c = psvi_coef<FAM>(acc[r], y, rsig);
+      C[(int64_t)row * S + col] = resid ? c * rs : c;
+    }
+  }
+}
+
+// ugrad[i, j] = -(w_i sum_s C[i, s] (tth_s[j] - tmean[s])) / S for j < dz: the same block / lane shape, inner index s
+template <bool LIN>
+__global__ __launch_bounds__(256) void psvi_ugrad_kernel(const double* __restrict__ C, int k, int S,
+                                                         const double* __restrict__ theta, int64_t ldt, int D, int dz,
+                                                         const double* __restrict__ tmean, const double* __restrict__ w,
+                                                         double* __restrict__ U) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int li = lane & 15, lk = lane >> 4, rb = wave >> 1, cb = wave & 1;
+  const int arow = blockIdx.x * 32 + rb * 16 + li, bcol = blockIdx.y * 32 + cb * 16 + li;
+  const bool aok = arow < k, bok = bcol < dz, one = LIN && bcol == D;
+  const double* ap = C + (int64_t)(aok ? arow : 0) * S;
+  const double* bp = theta + (bcol < D ? bcol : 0);
+  ps4d acc = (ps4d){0.0, 0.0, 0.0, 0.0};
+  for (int sb = 0; sb < S; sb += 32) {
+    double xa[8], xb[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) {
+      const int s = sb + 8 * lk + q;
+      const bool ok = s < S;
+      const int sc = ok ? s : 0;
+      const double a = ap[sc], th = bp[(int64_t)sc * ldt], m = tmean[sc];
+      xa[q] = (ok && aok) ? a : 0.0;
+      xb[q] = (ok && bok) ? (one ? 1.0 : th) - m : 0.0;
+    }
+#pragma unroll
+    for (int t = 0; t < 8; ++t) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(xa[t], xb[t], acc, 0, 0, 0);
+  }
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int row = blockIdx.x * 32 + rb * 16 + lk + 4 * r;
+    if (row < k && bok) U[(int64_t)row * dz + bcol] = -(w[row] * acc[r]) / (double)S;
+  }
+}
+
+// G[i, s, j] = C[i, s] (tth_s[j] - tmean[s]), k x S x dz, row-major
+template <bool LIN>
+__global__ __launch_bounds__(256) void psvi_gwrite_kernel(const double* __restrict__ C, int S, const double* __restrict__ theta,
+                                                          int64_t ldt, int D, int dz, const double* __restrict__ tmean,
+                                                          double* __restrict__ G, int64_t total) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    const int64_t row = e / dz;                                // i S + s
+    const int j = (int)(e - row * dz), s = (int)(row % S);
+    const double th = (LIN && j == D) ? 1.0 : theta[(int64_t)s * ldt + (j < D ? j : 0)];
+    G[e] = C[row] * (th - tmean[s]);
+  }
+}
+
+// ---- host side ----------------------------------------------------------------------------------------------------------------
+#define PS_HIP(call)                                                              \
+  do {                                                                            \
+    hipError_t _e = (call);                                                       \
+    if (_e != hipSuccess) {                                                       \
+      bcx_project_set_error(std::string(#call) + ": " + hipGetErrorString(_e));   \
+      return BCX_ERR_HIP;                                                         \
+    }                                                                             \
+  } while (0)
+
+static int ps_arg_error(const char* who, const char* what) {
+  bcx_project_set_error(std::string(who) + ": " + what);
+  return BCX_ERR_ARG;
+}
+
+// the checks both entries share; *dz: the length of a gradient row
+static int ps_check(const char* who, int32_t family, const void* P, int32_t k, int64_t ldp, int32_t D, int32_t ycol,
+                    const void* theta, int32_t S, int64_t ldt, double param, const void* work, int* dz) {
+  if (family < PS_LOGISTIC || family > PS_LINREG) return ps_arg_error(who, "unknown likelihood family");
+  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return ps_arg_error(who, "k (pseudo-points) must be in 1 .. 4096");
+  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return ps_arg_error(who, "S (samples) must be in 1 .. 8192");
+  if (D < 1 || D > BCX_PSVI_MAX_DIM) return ps_arg_error(who, "D (features) must be in 1 .. 1024");
+  if (!P || !theta || !work) return ps_arg_error(who, "null pointer");
+  if (ldp < D || ldt < D) return ps_arg_error(who, "leading dimension shorter than D");
+  if (family != PS_LOGISTIC && (ycol < 0 || ycol >= ldp)) return ps_arg_error(who, "response column required");
+  if (family == PS_LINREG && !(param != 0.0)) return ps_arg_error(who, "sigsq must be non-zero");
+  *dz = family == PS_LINREG ? D + 1 : D;
+  return BCX_OK;
+}
+
+static int ps_coef(hipStream_t st, int32_t family, const double* P, int k, int64_t ldp, int D, int ycol, const double* theta, int S,
+                   int64_t ldt, double param, const double* resid, double* C) {
+  const dim3 grid((k + 31) / 32, (S + 31) / 32);
+  const double rsig = family == PS_LINREG ? 1.0 / param : 0.0;
+  if (family == PS_LOGISTIC)
+    hipLaunchKernelGGL(psvi_coef_kernel<PS_LOGISTIC>, grid, dim3(256), 0, st, P, k, ldp, D, ycol, theta, S, ldt, rsig, resid, C);
+  else if (family == PS_POISSON)
+    hipLaunchKernelGGL(psvi_coef_kernel<PS_POISSON>, grid, dim3(256), 0, st, P, k, ldp, D, ycol, theta, S, ldt, rsig, resid, C);
+  else
+    hipLaunchKernelGGL(psvi_coef_kernel<PS_LINREG>, grid, dim3(256), 0, st, P, k, ldp, D, ycol, theta, S, ldt, rsig, resid, C);
+  PS_HIP(hipGetLastError());
+  return BCX_OK;
+}
+
+extern "C" int64_t bcx_psvi_gradient_scratch_bytes(int32_t k, int32_t S) {
+  if (k < 1 || k > BCX_PSVI_MAX_POINTS || S < 1 || S > BCX_PSVI_MAX_SAMPLES) return -1;
+  return ((int64_t)k * S + S) * (int64_t)sizeof(double);
+}
+
+extern "C" int bcx_project_grad_points(void* stream, int32_t family, const void* P_dev, int32_t k, int64_t ldp, int32_t D,
+                                       int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param, void* glls_dev,
+                                       void* work_dev) {
+  static const char* who = "bcx_project_grad_points";
+  int dz = 0;
+  int rc = ps_check(who, family, P_dev, k, ldp, D, ycol, theta_dev, S, ldt, param, work_dev, &dz);
+  if (rc) return rc;
+  if (!glls_dev) return ps_arg_error(who, "null output");
+  hipStream_t st = (hipStream_t)stream;
+  const double* P = (const double*)P_dev;
+  const double* theta = (const double*)theta_dev;
+  double* C = (double*)work_dev;
+  double* tmean = C + (int64_t)k * S;
+  hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)nullptr, 0.0,
+                     (const double*)nullptr, (int64_t)0, (const double*)nullptr, (double*)nullptr, theta, (int64_t)ldt, D, dz, tmean);
+  PS_HIP(hipGetLastError());
+  rc = ps_coef(st, family, P, k, ldp, D, ycol, theta, S, ldt, param, nullptr, C);
+  if (rc) return rc;
+  const int64_t total = (int64_t)k * S * dz;
+  const int64_t want = (total + 255) / 256;
+  const int blocks = (int)(want < 8192 ? want : 8192);
+  if (family == PS_LINREG)
+    hipLaunchKernelGGL(psvi_gwrite_kernel<true>, dim3(blocks), dim3(256), 0, st, C, S, theta, (int64_t)ldt, D, dz, tmean,
+                       (double*)glls_dev, total);
+  else
+    hipLaunchKernelGGL(psvi_gwrite_kernel<false>, dim3(blocks), dim3(256), 0, st, C, S, theta, (int64_t)ldt, D, dz, tmean,
+                       (double*)glls_dev, total);
+  PS_HIP(hipGetLastError());
+  return BCX_OK;
+}
+
+extern "C" int bcx_psvi_gradient(void* stream, int32_t family, const void* P_dev, int32_t k, int64_t ldp, int32_t D, int32_t ycol,
+                                 const void* theta_dev, int32_t S, int32_t ldt, double param, const void* colsum_dev,
+                                 const void* corevecs_dev, int64_t ldcv, const void* w_dev, double scaling, void* out_dev,
+                                 void* work_dev) {
+  static const char* who = "bcx_psvi_gradient";
+  int dz = 0;
+  int rc = ps_check(who, family, P_dev, k, ldp, D, ycol, theta_dev, S, ldt, param, work_dev, &dz);
+  if (rc) return rc;
+  if (!colsum_dev || !corevecs_dev || !w_dev || !out_dev) return ps_arg_error(who, "null pointer");
+  if (ldcv < S) return ps_arg_error(who, "corevecs leading dimension shorter than S");
+  hipStream_t st = (hipStream_t)stream;
+  const double* P = (const double*)P_dev;
+  const double* theta = (const double*)theta_dev;
+  const double* cv = (const double*)corevecs_dev;
+  const double* w = (const double*)w_dev;
+  double* resid = (double*)out_dev;
+  double* wgrad = resid + S;
+  double* ugrad = wgrad + k;
+  double* A = (double*)work_dev;
+  double* tmean = A + (int64_t)k * S;
+  hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)colsum_dev, scaling, cv, ldcv, w,
+                     resid, theta, (int64_t)ldt, D, dz, tmean);
+  PS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(psvi_wgrad_kernel, dim3(k), dim3(256), 0, st, S, cv, ldcv, (const double*)resid, wgrad);
+  PS_HIP(hipGetLastError());
+  rc = ps_coef(st, family, P, k, ldp, D, ycol, theta, S, ldt, param, resid, A);
+  if (rc) return rc;
+  const dim3 grid((k + 31) / 32, (dz + 31) / 32);
+  if (family == PS_LINREG)
+    hipLaunchKernelGGL(psvi_ugrad_kernel<true>, grid, dim3(256), 0, st, (const double*)A, k, S, theta, (int64_t)ldt, D, dz,
+                       (const double*)tmean, w, ugrad);
+  else
+    hipLaunchKernelGGL(psvi_ugrad_kernel<false>, grid, dim3(256), 0, st, (const double*)A, k, S, theta, (int64_t)ldt, D, dz,
+                       (const double*)tmean, w, ugrad);
+  PS_HIP(hipGetLastError());
+  return BCX_OK;
+}

@@ -394,6 +394,30 @@ const char* bcx_project_last_error(void);
  * flops 2 N D S of those launches (the roofline figure of bench.py --config c5 / c3). */
 int bcx_project_profile(int32_t on);
 int bcx_project_profile_read(double* ms_total, int64_t* launches, double* flops);
+/* ---- BatchPSVI: gradients of the projection with respect to the pseudo-points (csrc/psvi.hip) ----
+ * The rows P_dev (k x ldp doubles: the D features first; for family 1 / 2 the response in column ycol) are pseudo-points,
+ * theta_dev (S x ldt) the current samples, family / param as for bcx_project_write.  Every family's gradient of a point's
+ * log-likelihood is c(i, s) times theta_s (family 2: [theta_s, 1], so dz = D + 1; otherwise dz = D), see csrc/psvi.hip.
+ * Limits: 1 <= k <= BCX_PSVI_MAX_POINTS, 1 <= S <= BCX_PSVI_MAX_SAMPLES, 1 <= D <= BCX_PSVI_MAX_DIM; outside them an
+ * entry returns BCX_ERR_ARG with a message in bcx_project_last_error().  Asynchronous on `stream`; deterministic (fixed
+ * reduction orders, no atomics).  work_dev: bcx_psvi_gradient_scratch_bytes(k, S) bytes (-1: outside the limits). */
+#define BCX_PSVI_MAX_POINTS 4096
+#define BCX_PSVI_MAX_SAMPLES 8192
+#define BCX_PSVI_MAX_DIM 1024
+int64_t bcx_psvi_gradient_scratch_bytes(int32_t k, int32_t S);
+/* glls_dev (k x S x dz, row-major) = the gradient projection of the reference's project(pts, grad=True)
+ * (bayesiancoresets/projector.py:25-27: centred over the LAST axis, the coordinates of the point) with the family gradients
+ * of examples/common/model_lr.py:50-57, model_linreg.py:12-17 and model_poiss.py:58-67 (the intended c(i, s) theta_s). */
+int bcx_project_grad_points(void* stream, int32_t family, const void* P_dev, int32_t k, int64_t ldp, int32_t D, int32_t ycol,
+                            const void* theta_dev, int32_t S, int32_t ldt, double param, void* glls_dev, void* work_dev);
+/* One gradient evaluation of BatchPSVI (bayesiancoresets/coreset/bpsvi.py:47-55) from colsum_dev (S: the data's centred
+ * column sums, sum_n vecs[n]), corevecs_dev (k x ldcv: the centred projections of the pseudo-points, bcx_project_write_points
+ * with center = 1), w_dev (k weights) and scaling:  out_dev = [resid (S) | wgrad (k) | ugrad (k x dz)] with
+ *   resid = scaling colsum - w^T corevecs,  wgrad = -corevecs resid / S,  ugrad[i] = -(w_i / S) sum_s glls[i, s, :] resid[s]
+ * -- the k x S x dz gradients are never formed (two products on the fp64 matrix cores). */
+int bcx_psvi_gradient(void* stream, int32_t family, const void* P_dev, int32_t k, int64_t ldp, int32_t D, int32_t ycol,
+                      const void* theta_dev, int32_t S, int32_t ldt, double param, const void* colsum_dev, const void* corevecs_dev,
+                      int64_t ldcv, const void* w_dev, double scaling, void* out_dev, void* work_dev);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 
