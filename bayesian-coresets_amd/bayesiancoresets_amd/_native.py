@@ -36,6 +36,7 @@ SYMBOLS = (
     "bcx_project_colsum_moments_at", "bcx_project_points_colsum_moments", "bcx_linreg_posterior_draw", "bcx_sparsevi_adam_step",
     "bcx_linreg_posterior_apply", "bcx_linreg_posterior_apply_ok",
     "bcx_linreg_posterior_factor", "bcx_linreg_posterior_factor_scratch_bytes", "bcx_linreg_posterior_factor_status",
+    "bcx_linreg_posterior_factor_clear_status",
     "bcx_linreg_posterior_draw_factored",
     "bcx_sparsevi_adam_step_ws", "bcx_sparsevi_adam_scratch_bytes", "bcx_standard_normal", "bcx_column_means",
     "bcx_center_rows", "bcx_row_sumsq", "bcx_project_write_points",
@@ -167,6 +168,7 @@ def load():
     sigs["bcx_gram_check"] = [vp, vp]
     sigs["bcx_linreg_posterior_factor"] = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, dbl, vp, i64, vp, i64, vp, vp]
     sigs["bcx_linreg_posterior_factor_status"] = [vp, i32, vp]
+    sigs["bcx_linreg_posterior_factor_clear_status"] = [vp, i32, vp]
     sigs["bcx_standard_normal"] = [vp, ctypes.c_uint64, ctypes.c_uint64, i64, vp]
     sigs["bcx_column_means"] = [vp, vp, i32, i32, i32, i64, vp, i64]
     sigs["bcx_center_rows"] = [vp, vp, i64, i32, i64]

@@ -223,7 +223,11 @@ class SparseVICoreset(Coreset):
         out = w.cpu().numpy()
         check = getattr(plan, "check", None)
         if check is not None:
-            check()                                                               # (a factorisation that lost its workgroups raises)
+            check()                                                               # (a failed factorisation / fit at any step raises)
+        if not np.isfinite(out).all():
+            # the reference's loop ends with NaN weights here (its clamp, np.maximum, keeps a NaN, and so does the ADAM kernel's):
+            # an error instead
+            raise nat.EngineError(nat.ERR_STATE, "SparseVI: the weight optimisation ended with weights that are not finite")
         return out
 
     def error(self):

@@ -44,7 +44,7 @@ class LaplacePosteriorSampler(_DeviceNormals):
         self._seed, self._offset = (0 if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF, 0
         self._mu = torch.zeros(self.D, dtype=torch.float64, device=self.device)       # the last mode (seeds a plan's next step)
         self._tbar = torch.zeros(self.D, dtype=torch.float64, device=self.device)
-        self._status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._status = torch.zeros(3, dtype=torch.int32, device=self.device)     # [fit, Newton steps, worst fit since zeroed]
         self._none = torch.zeros(2, dtype=torch.float64, device=self.device)
         self._theta = {}
         self._pts_key, self._pts_dev = None, None
@@ -73,12 +73,16 @@ class LaplacePosteriorSampler(_DeviceNormals):
                 self._mu.data_ptr(), int(warm), self.tol, self.max_iter, R.data_ptr(), rbar.data_ptr(), theta.shape[0], self.ld,
                 theta.data_ptr(), self._tbar.data_ptr(), self._status.data_ptr()]
 
-    def check(self):
-        """Synchronises; raises if the last fit did not converge or met no positive definite Newton matrix."""
+    def check(self, worst=False):
+        """Synchronises; raises if the last fit (``worst``: any fit since the word was zeroed -- a plan zeroes it when it starts)
+        did not converge or met no positive definite Newton matrix (NaN weights included: where the reference would go on with
+        NaN draws, this is an error)."""
         st = self._status.cpu().numpy()
-        if st[0] != 0:
-            raise self._nat.EngineError(self._nat.ERR_STATE, "Laplace fit on the device: %s after %d Newton steps"
-                                        % ("iteration limit" if st[0] == 1 else "no positive definite Newton matrix", int(st[1])))
+        v = st[2] if worst else st[0]
+        if v != 0:
+            raise self._nat.EngineError(self._nat.ERR_STATE, "Laplace fit on the device: %s%s"
+                                        % ("iteration limit" if v == 1 else "no positive definite Newton matrix",
+                                           " at a step of the loop" if worst else " after %d Newton steps" % int(st[1])))
         return int(st[1])
 
     # -- the reference's sampler signature --------------------------------------------------------------------------------------
@@ -133,6 +137,7 @@ class _LaplacePlan(object):
     def __init__(self, sampler, n, pts_dev, noise):
         self.s, self.n, self.pts_dev = sampler, n, pts_dev
         self.theta = sampler._theta_buf(n)
+        sampler._status[2].zero_()                          # (check() then covers every fit of this plan)
         self.set_noise(noise)
 
     def set_noise(self, noise):
@@ -158,6 +163,6 @@ class _LaplacePlan(object):
         return self.buffers()
 
     def check(self):
-        """After the loop's read-back: the LAST fit's status (a fit that failed leaves NaNs or stale draws behind and fails
-        the ones after it)."""
-        self.s.check()
+        """After the loop's read-back: raises ``EngineError`` if ANY fit of the plan failed (a fit that failed leaves NaNs or
+        stale draws behind; a later warm-started fit may still converge)."""
+        self.s.check(worst=True)

@@ -146,8 +146,17 @@ class LinregPosteriorSampler(_DeviceNormals):
         return [stream, self.D, self.ld, f["U"].data_ptr(), self.ld, f["u"].data_ptr(), 0, 0, theta.shape[0], theta.data_ptr(),
                 (self._tbar if tbar is None else tbar).data_ptr()]
 
+    def clear_factor_status(self):
+        """Enqueues a clear of the factorisations' status word: the next ``factor_status`` covers every factorisation after it."""
+        stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
+        rc = self._lib.bcx_linreg_posterior_factor_clear_status(stream, self.D, self._factor_state()["work"].data_ptr())
+        if rc != 0:
+            raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+
     def factor_status(self):
-        """Synchronises; raises if the last factorisation's workgroups lost each other or met a non-positive pivot."""
+        """Synchronises; raises if any factorisation since ``clear_factor_status`` lost its workgroups or met a pivot that was
+        not positive (a NaN included: NaN weights or points -- where the reference would go on with NaN draws and weights,
+        this is an error)."""
         if self._factor is not None:
             stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
             rc = self._lib.bcx_linreg_posterior_factor_status(stream, self.D, self._factor["work"].data_ptr())
@@ -217,6 +226,9 @@ class LinregPosteriorSampler(_DeviceNormals):
         k = 0 if wts is None else len(wts)
         if not self.supports(n, k):
             raise ValueError("LinregPosteriorSampler: %d draws for %d weighted points (at most %d and %d)" % (n, k, self.SMAX, self.KMAX))
+        if k and not np.isfinite(np.asarray(wts, dtype=np.float64)).all():
+            # (the reference draws NaNs from NaN weights and SparseVI ends with NaN weights: here that is an error)
+            raise self._nat.EngineError(self._nat.ERR_STATE, "LinregPosteriorSampler: weights that are not finite")
         st, w_dev = None, self._none
         if k:
             st = self._points(pts)
@@ -224,6 +236,7 @@ class LinregPosteriorSampler(_DeviceNormals):
         theta = self._theta_buf(n)
         R = self._noise(n)
         if k and not st["low_rank"]:
+            self.clear_factor_status()
             rc = self._lib.bcx_linreg_posterior_factor(*self._factor_args(st, w_dev))
             if rc != 0:
                 raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
@@ -263,6 +276,8 @@ class _Plan(object):
         self._args, self._w_ptr, self._pre = None, None, None
         self.fast = bool(st["low_rank"] and s._lib.bcx_linreg_posterior_apply_ok(st["k"], s.ld))
         self.factored = not st["low_rank"]
+        if self.factored:
+            s.clear_factor_status()                         # (check() then covers every factorisation of this plan)
         self.set_noise(noise)
 
     def set_noise(self, noise):
@@ -327,6 +342,7 @@ class _Plan(object):
         return self.buffers()
 
     def check(self):
-        """After the loop's read-back: did every factorisation of the loop complete (csrc/lrpost.hip's status word)?"""
+        """After the loop's read-back: did every factorisation of the loop complete with positive pivots (csrc/lrpost.hip's
+        status word, the worst of all steps since the plan started)?  Raises ``EngineError`` otherwise."""
         if self.factored:
             self.s.factor_status()

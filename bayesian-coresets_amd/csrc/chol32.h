@@ -26,10 +26,12 @@ static __device__ __forceinline__ double lp_rsqrt(double d) {
 // plain loop, 6 us per tile), a readlane -> fma hop 25, a BROADCAST ds_read_b128 36 per wave (so multipliers through LDS are
 // slower than through v_readlane: 8 us per tile), a dependent v_mfma_f64_16x16x4 64.  The loop body is software-pipelined by
 // hand and pinned with scheduling barriers.  On return a[] holds L (lanes 0 .. 31) and X = L^-T (lanes 32 .. 63);
-// dmin: the smallest pivot met (not positive: the tile was not positive definite, a[] holds NaNs).
+// dmin: the smallest pivot met, NaN if any pivot was NaN (not positive: the tile was not positive definite, a[] holds NaNs).
+// fmin drops a NaN operand, so the NaN pivots are collected in a side flag off the dependent chain and folded in at the end.
 static __device__ __forceinline__ void chol32_factor(double (&a)[32], double& dmin) {
   double d = lp_readlane(a[0], 0);
   dmin = d;
+  bool dnan = d != d;
   double r = lp_rsqrt(d);
 #pragma unroll
   for (int c = 0; c < 32; ++c) {
@@ -40,6 +42,7 @@ static __device__ __forceinline__ void chol32_factor(double (&a)[32], double& dm
       __builtin_amdgcn_sched_barrier(0);
       d = lp_readlane(a[c + 1], c + 1);
       dmin = fmin(dmin, d);                         // (a non-positive pivot leaves NaNs behind; reported once, by the caller)
+      dnan |= d != d;
       r = lp_rsqrt(d);
 #pragma unroll
       for (int j0 = c + 2; j0 < 32; j0 += 8) {
@@ -52,6 +55,7 @@ static __device__ __forceinline__ void chol32_factor(double (&a)[32], double& dm
       __builtin_amdgcn_sched_barrier(0);
     }
   }
+  if (dnan) dmin = __builtin_nan("");
 }
 
 // ---- the same through a 16 + 16 split ---------------------------------------------------------------------------------------
@@ -63,7 +67,7 @@ static __device__ __forceinline__ void chol32_factor(double (&a)[32], double& dm
 typedef double c32_4d __attribute__((ext_vector_type(4)));
 typedef double c32_2d __attribute__((ext_vector_type(2)));
 template <int C0, int C1>
-static __device__ __forceinline__ void chol32_block(double (&a)[32], double& r, double& dmin) {
+static __device__ __forceinline__ void chol32_block(double (&a)[32], double& r, double& dmin, bool& dnan) {
 #pragma unroll
   for (int c = C0; c < C1; ++c) {
     a[c] *= r;
@@ -73,6 +77,7 @@ static __device__ __forceinline__ void chol32_block(double (&a)[32], double& r, 
       __builtin_amdgcn_sched_barrier(0);
       const double d = lp_readlane(a[c + 1], c + 1);
       dmin = fmin(dmin, d);
+      dnan |= d != d;
       r = lp_rsqrt(d);
 #pragma unroll
       for (int j0 = c + 2; j0 < C1; j0 += 8) {
@@ -90,8 +95,9 @@ static __device__ __forceinline__ void chol32_factor_split(double (&a)[32], doub
   const int lane = threadIdx.x & 63;
   double d = lp_readlane(a[0], 0);
   dmin = d;
+  bool dnan = d != d;
   double r = lp_rsqrt(d);
-  chol32_block<0, 16>(a, r, dmin);
+  chol32_block<0, 16>(a, r, dmin, dnan);
   // Y, element (row, c) at (c / 4) * 256 + row * 4 + c % 4: the operand slices (row l % 16 of a block of 16 rows, c = 4 t + l / 16)
   // are 64 consecutive doubles
 #pragma unroll
@@ -135,6 +141,8 @@ static __device__ __forceinline__ void chol32_factor_split(double (&a)[32], doub
   for (int c = 0; c < 16; ++c) a[16 + c] -= upd ? pr[c] : 0.0;
   d = lp_readlane(a[16], 16);
   dmin = fmin(dmin, d);
+  dnan |= d != d;
   r = lp_rsqrt(d);
-  chol32_block<16, 32>(a, r, dmin);
+  chol32_block<16, 32>(a, r, dmin, dnan);
+  if (dnan) dmin = __builtin_nan("");               // (as in chol32_factor: fmin dropped the NaN pivots)
 }

@@ -13,6 +13,10 @@ inline const char* bcx_dev_env(const char* name) {
   return on ? getenv(name) : nullptr;
 }
 
+// max(v, 0) by NumPy's rule (np.maximum, the reference's clamp): a NaN stays NaN.  fmax(v, 0) would turn it into 0 and a
+// failed step upstream into finite, wrong weights.
+__device__ __forceinline__ double bcx_clamp0(double v) { return (v >= 0.0 || v != v) ? v : 0.0; }
+
 #define BCX_WAVE 64
 #define BCX_SCRATCH 64   // doubles of LDS scratch for block reductions (NV <= 4, <= 16 waves)
 

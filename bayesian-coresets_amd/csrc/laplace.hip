@@ -32,7 +32,8 @@ struct LapArgs {
   const double* Rbar;   // ld: their column means
   double* theta;        // S x ld draws
   double* tbar;         // D: mean of the draws
-  int* status;          // [0] 0 ok / 1 iteration limit / 2 no positive definite Newton matrix; [1] Newton steps taken
+  int* status;          // [0] 0 ok / 1 iteration limit / 2 no positive definite Newton matrix; [1] Newton steps taken;
+                        // [2] the worst [0] of every call since the host zeroed it (a loop's failure cannot be overwritten)
   double tol;
   int family, k, D, ldp, S, ld, max_iter, warm;
 };
@@ -79,7 +80,7 @@ __global__ __launch_bounds__(LAP_THREADS) void laplace_sampler_kernel(LapArgs a)
   double* sh = sg + k;                               // k: w_j h_j
   for (int e = tid; e < k * D; e += LAP_THREADS) { const int j = e / D, c = e - j * D; sX[j * Dp + c] = a.pts[(size_t)j * a.ldp + c]; }
   for (int j = tid; j < k; j += LAP_THREADS) {
-    sw[j] = fmax(a.w[j], 0.0);
+    sw[j] = bcx_clamp0(a.w[j]);
     sy[j] = a.family == LAP_POISSON ? a.pts[(size_t)j * a.ldp + D] : 0.0;
   }
   if (tid < 32) s_th[tid] = (tid < D && a.warm) ? a.mu[tid] : 0.0;
@@ -196,7 +197,7 @@ __global__ __launch_bounds__(LAP_THREADS) void laplace_sampler_kernel(LapArgs a)
   bool have_W = false;
   if (status != 2) { assemble(); have_W = factor(); if (!have_W) status = 2; }
   if (tid < D) a.mu[tid] = s_th[tid];
-  if (tid == 0) { a.status[0] = status; a.status[1] = steps; }
+  if (tid == 0) { a.status[0] = status; a.status[1] = steps; a.status[2] = max(a.status[2], status); }
   if (!have_W) {                                     // (no factor: the draws are the mode -- the caller raises on the status)
     for (int e = tid; e < 32 * 33; e += LAP_THREADS) s_W[e] = 0.0;
     __syncthreads();

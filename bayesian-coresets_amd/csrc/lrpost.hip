@@ -71,7 +71,9 @@ struct LpArgs {
   double* AS;     // nt tiles: P_{p+1,p} - sum_{q <= p-2} L_{p+1,q} L_{p,q}^T        (assistant 1 -> chain)
   double* AD;     // nt tiles: P_{p+1,p+1} - sum_{q <= p-2} L_{p+1,q} L_{p+1,q}^T    (assistant 2 -> chain)
   double* rhs;    // 32 nt doubles: Sig0^-1 mu0 + X^T (w y) / sigsq, zero padded
-  int* flags;     // [4 nt]: the status word (0 ok, 1 a wait expired, 2 a pivot was not positive); the words before it are not used
+  int* flags;     // [4 nt]: this launch's wait word (1: a wait expired, the other waves stop waiting; cleared by lrp_form_kernel);
+                  // [4 nt + 1]: the status word, the worst of every launch since the host cleared it (0 ok, 1 a wait expired,
+                  // 2 a pivot was not positive or NaN; atomicMax, never cleared on the device); the words before them are not used
   // outputs
   double* U; int64_t ldu;      // D x ldu row-major: U = L^-T, upper triangular (the lower triangle is never written: the caller zeroes it once)
   double* uvec;                // D: u = L^-1 rhs  (mu_w = U u; the draws are U (u + r))
@@ -154,7 +156,8 @@ static __device__ __forceinline__ void lp_quad_store(double* tile, int rb, int c
 // both operands of the product are read along the contraction index: lane (i = lane % 16, g = lane / 16) takes the values
 // 8 g .. 8 g + 7 of each run of 32 points as four 16-byte loads, one value per MFMA step (any assignment of the inner index
 // to steps serves as long as both operands use the same one); three runs are in flight.  Workgroups after them, one per
-// block of 32 columns: that block of the right-hand side; the first of them clears the status word.
+// block of 32 columns: that block of the right-hand side; the first of them clears the wait word (not the status word: a
+// failure of any factorisation since the host cleared it stays visible, bcx_linreg_posterior_factor_clear_status).
 typedef double lp2d __attribute__((ext_vector_type(2)));
 static __device__ __forceinline__ void lp_fill_sent(double* tile, int tid) {
 #pragma unroll
@@ -168,12 +171,12 @@ __global__ __launch_bounds__(256) void lrp_form_kernel(LpArgs a) {
   const int kp = (k + 31) & ~31;
   if ((int)blockIdx.x >= ntop * a.ks) {
     const int j = blockIdx.x - ntop * a.ks;
-    if (j == 0) for (int e = tid; e < 4 * nt + 1; e += 256) a.flags[e] = 0;
+    if (j == 0) for (int e = tid; e < 4 * nt + 1; e += 256) a.flags[e] = 0;      // (not [4 nt + 1])
     lp_fill_sent(a.BL + ((size_t)nt * nt + j) * LP_TILE, tid);
     lp_fill_sent(a.XW + (size_t)j * LP_TILE, tid);
     lp_fill_sent(a.AS + (size_t)j * LP_TILE, tid);
     lp_fill_sent(a.AD + (size_t)j * LP_TILE, tid);
-    for (int e = tid; e < kp; e += 256) sw[e] = e < k ? fmax(a.w[e], 0.0) / a.sigsq * a.y[e] : 0.0;
+    for (int e = tid; e < kp; e += 256) sw[e] = e < k ? bcx_clamp0(a.w[e]) / a.sigsq * a.y[e] : 0.0;
     __syncthreads();
     // rhs0 + X^T (w y) / sigsq: a wave per column, lanes along the points
     for (int q = wave; q < 32; q += 4) {
@@ -200,7 +203,7 @@ __global__ __launch_bounds__(256) void lrp_form_kernel(LpArgs a) {
     if (i > j) lp_fill_sent(a.LT + (size_t)(i * nt + j) * LP_TILE, tid);
     lp_fill_sent(a.BL + (size_t)(j * nt + i) * LP_TILE, tid);
   }
-  for (int e = tid; e < kp; e += 256) sw[e] = e < k ? fmax(a.w[e], 0.0) / a.sigsq : 0.0;
+  for (int e = tid; e < kp; e += 256) sw[e] = e < k ? bcx_clamp0(a.w[e]) / a.sigsq : 0.0;
   const int rb = wave >> 1, cb = wave & 1;
   const int li = lane & 15, lk = lane >> 4;
   const int ra = i * 32 + rb * 16 + li;             // the A operand's row of P (a feature), this lane
@@ -275,11 +278,11 @@ struct LpSpin { long long t0; int n; bool dead; };
 static __device__ __forceinline__ bool lp_again(LpSpin& sp, const LpArgs& a) {     // after a failed check; false: give up
   if (sp.t0 < 0) sp.t0 = wall_clock64();
   __builtin_amdgcn_s_sleep(LP_SLEEP);
-  int* status = a.flags + 4 * a.nt;
+  int* wait = a.flags + 4 * a.nt;
   if (wall_clock64() - sp.t0 > a.timeout_ticks) {
-    if ((threadIdx.x & 63) == 0) atomicCAS(status, 0, 1);
+    if ((threadIdx.x & 63) == 0) { atomicCAS(wait, 0, 1); atomicMax(wait + 1, 1); }
     sp.dead = true;
-  } else if (((++sp.n) & 255) == 0 && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) sp.dead = true;
+  } else if (((++sp.n) & 255) == 0 && __hip_atomic_load(wait, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 1) sp.dead = true;
   return !sp.dead;
 }
 // The statements after PEEK_OK (re)load the wave's operands and clear the lane's `ok` where a value is missing; until every
@@ -471,7 +474,7 @@ __global__ __launch_bounds__(256) void lrp_chol_kernel(LpArgs a) {
       }
     }
     __syncthreads();
-    if (tid == 0 && s_bad) atomicExch(a.flags + 4 * nt, 2);
+    if (tid == 0 && s_bad) atomicMax(a.flags + 4 * nt + 1, 2);
     return;
   }
 
@@ -736,7 +739,7 @@ static int lrp_slices(int k) {                      // workgroups per tile of P:
   return runs >= 12 ? 4 : runs >= 8 ? 3 : runs >= 4 ? 2 : 1;
 }
 static int64_t lrp_tiles(int nt) { return (int64_t)(1 + LP_MAX_KS) * nt * nt + (int64_t)(nt + 1) * nt + 3 * nt; }
-static int64_t lrp_flag_bytes(int nt) { return (int64_t)(4 * nt + 1 + 15) / 16 * 16 * 4; }
+static int64_t lrp_flag_bytes(int nt) { return (int64_t)(4 * nt + 2 + 15) / 16 * 16 * 4; }
 #define LRP_DBG_BYTES(nt) ((int64_t)(LP_FIXED_WGS + LP_MAX_H) * (nt) * 8 * 8)
 
 extern "C" int64_t bcx_linreg_posterior_factor_scratch_bytes(int32_t D) {
@@ -784,14 +787,22 @@ extern "C" int bcx_linreg_posterior_factor(void* stream, int32_t k, int32_t D, i
   return BCX_OK;
 }
 
-// After a synchronisation of the stream: 0 ok, BCX_ERR_TIMEOUT a wait between the workgroups of lrp_chol_kernel expired (its
-// outputs are not valid), BCX_ERR_STATE a pivot was not positive (P not positive definite: NaN / negative weights upstream).
+static int* lrp_status_word(const void* work_dev, int nt) {
+  return (int*)((const double*)work_dev + lrp_tiles(nt) * LP_TILE + (int64_t)nt * 32) + 4 * nt + 1;
+}
+// Enqueues status word = 0 (before the first factorisation a status read covers: a loop's, or a single call's).
+extern "C" int bcx_linreg_posterior_factor_clear_status(void* stream, int32_t D, void* work_dev) {
+  if (D < 1 || D > LP_NB * LP_MAX_NT || !work_dev) { bcx_project_set_error("bcx_linreg_posterior_factor_clear_status: bad arguments"); return BCX_ERR_ARG; }
+  LRP_HIP(hipMemsetAsync(lrp_status_word(work_dev, (D + LP_NB - 1) / LP_NB), 0, sizeof(int), (hipStream_t)stream));
+  return BCX_OK;
+}
+// After a synchronisation of the stream, the worst of every factorisation since the last clear (reading does not clear): 0 ok,
+// BCX_ERR_TIMEOUT a wait between the workgroups of lrp_chol_kernel expired (its outputs are not valid), BCX_ERR_STATE a pivot
+// was not positive or NaN (P not positive definite: NaN / non-finite weights or points upstream).
 extern "C" int bcx_linreg_posterior_factor_status(void* stream, int32_t D, const void* work_dev) {
   if (D < 1 || D > LP_NB * LP_MAX_NT || !work_dev) { bcx_project_set_error("bcx_linreg_posterior_factor_status: bad arguments"); return BCX_ERR_ARG; }
-  const int nt = (D + LP_NB - 1) / LP_NB;
-  const int* flags = (const int*)((const double*)work_dev + lrp_tiles(nt) * LP_TILE + (int64_t)nt * 32);
   int v = 0;
-  LRP_HIP(hipMemcpyAsync(&v, flags + 4 * nt, sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  LRP_HIP(hipMemcpyAsync(&v, lrp_status_word(work_dev, (D + LP_NB - 1) / LP_NB), sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
   LRP_HIP(hipStreamSynchronize((hipStream_t)stream));
   if (v == 1) { bcx_project_set_error("linreg posterior factorisation: a wait between workgroups timed out (GPU shared or preempted)"); return BCX_ERR_TIMEOUT; }
   if (v == 2) { bcx_project_set_error("linreg posterior factorisation: the precision matrix is not positive definite"); return BCX_ERR_STATE; }

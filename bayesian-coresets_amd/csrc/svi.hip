@@ -123,11 +123,11 @@ __global__ __launch_bounds__(256) void lrs_draw_kernel(LrsArgs a) {
   // ---- the k x k system: every input straight from memory (no value waits for another) ----
   for (int e = tid; e < k * k; e += 256) {
     const int i = e / k, j = e - i * k;
-    const double si = sqrt(fmax(a.w[i], 0.0) / a.sigsq), sj = sqrt(fmax(a.w[j], 0.0) / a.sigsq);
+    const double si = sqrt(bcx_clamp0(a.w[i]) / a.sigsq), sj = sqrt(bcx_clamp0(a.w[j]) / a.sigsq);
     sL[i][j] = (i == j ? 1.0 : 0.0) + si * sj * a.K0[e];
   }
   if (tid < k) {
-    const double wi = fmax(a.w[tid], 0.0), si = sqrt(wi / a.sigsq);
+    const double wi = bcx_clamp0(a.w[tid]), si = sqrt(wi / a.sigsq);
     ss[tid] = si;
     sc[tid] = wi * a.y[tid] / a.sigsq;
     double t = a.xmu0[tid];
@@ -140,7 +140,7 @@ __global__ __launch_bounds__(256) void lrs_draw_kernel(LrsArgs a) {
       }
 #pragma unroll
       for (int q = 0; q < 8; ++q)
-        if (j0 + q < k) t += kk[q] * (fmax(ww[q], 0.0) * yy[q] / a.sigsq);
+        if (j0 + q < k) t += kk[q] * (bcx_clamp0(ww[q]) * yy[q] / a.sigsq);
     }
     sa[tid] = si * t;
   }
@@ -149,7 +149,7 @@ __global__ __launch_bounds__(256) void lrs_draw_kernel(LrsArgs a) {
     const bool ok = j < k && n0 + c < D;
     const double x = ok ? a.XS0[(size_t)j * ld + n0 + c] : 0.0;
     sXS[j][c] = x;
-    sB2[j][c] = ok ? sqrt(fmax(a.w[j], 0.0) / a.sigsq) * x : 0.0;
+    sB2[j][c] = ok ? sqrt(bcx_clamp0(a.w[j]) / a.sigsq) * x : 0.0;
   }
   const double mu0c = (tid < 16 && n0 + tid < D) ? a.mu0[n0 + tid] : 0.0;
   __syncthreads();
@@ -304,15 +304,15 @@ __global__ __launch_bounds__(256) void lrs_apply_kernel(LraArgs a) {
   for (int e = tid; e < k * ld; e += 256) {
     const int j = e / ld;
     sX[e] = a.X[e];
-    sB2[e] = sqrt(fmax(a.w[j], 0.0) / a.sigsq) * a.XS0[e];
+    sB2[e] = sqrt(bcx_clamp0(a.w[j]) / a.sigsq) * a.XS0[e];
   }
   for (int e = tid; e < k * k; e += 256) {
     const int i = e / k, j = e - i * k;
-    const double si = sqrt(fmax(a.w[i], 0.0) / a.sigsq), sj = sqrt(fmax(a.w[j], 0.0) / a.sigsq);
+    const double si = sqrt(bcx_clamp0(a.w[i]) / a.sigsq), sj = sqrt(bcx_clamp0(a.w[j]) / a.sigsq);
     sL[i][j] = (i == j ? 1.0 : 0.0) + si * sj * a.K0[e];
   }
   if (tid < k) {
-    const double wi = fmax(a.w[tid], 0.0), si = sqrt(wi / a.sigsq);
+    const double wi = bcx_clamp0(a.w[tid]), si = sqrt(wi / a.sigsq);
     ss[tid] = si;
     sc[tid] = wi * a.y[tid] / a.sigsq;
     double t = a.xmu0[tid];
@@ -325,7 +325,7 @@ __global__ __launch_bounds__(256) void lrs_apply_kernel(LraArgs a) {
       }
 #pragma unroll
       for (int q = 0; q < 8; ++q)
-        if (j0 + q < k) t += kk[q] * (fmax(ww[q], 0.0) * yy[q] / a.sigsq);
+        if (j0 + q < k) t += kk[q] * (bcx_clamp0(ww[q]) * yy[q] / a.sigsq);
     }
     sa[tid] = si * t;
   }
@@ -459,7 +459,7 @@ __global__ __launch_bounds__(256) void svi_adam_kernel(const double* __restrict_
     mom2[tid] = m2;
     const double* sc = sched + 3 * (size_t)step;
     const double stp = sc[0] * m1 / sc[1] / (eps + sqrt(m2 / sc[2]));
-    const double x = fmax(sw[tid] - stp, 0.0);
+    const double x = bcx_clamp0(sw[tid] - stp);
     w[tid] = x;
     if (trace) trace[(size_t)step * k + tid] = x;
   }
@@ -566,7 +566,7 @@ __global__ __launch_bounds__(256) void svi_adam_b_kernel(SvbArgs a) {
       a.mom2[j] = m2;
       const double* sc = a.sched + 3 * (size_t)a.step;
       const double stp = sc[0] * m1 / sc[1] / (a.eps + sqrt(m2 / sc[2]));
-      const double x = fmax(a.w[j] - stp, 0.0);
+      const double x = bcx_clamp0(a.w[j] - stp);
       a.w[j] = x;
       if (a.trace) a.trace[(size_t)a.step * a.k + j] = x;
     }

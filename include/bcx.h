@@ -338,14 +338,19 @@ int bcx_sparsevi_adam_step_ws(void* stream, int32_t k, int32_t S, const void* co
  * shared between streams.  Asynchronous on `stream`: P on the fp64 matrix cores, then ONE cooperative launch of <= 63
  * workgroups (blocked Cholesky whose row operations also produce L^-T and L^-1 rhs: csrc/lrpost.hip), then -- only when
  * mu_dev is given -- the product U u; the cooperative launch's workgroups hand tiles to each other and give up a wait after
- * 2 s: bcx_linreg_posterior_factor_status synchronises the stream and returns BCX_ERR_TIMEOUT for that, BCX_ERR_STATE if a
- * pivot was not positive, BCX_OK otherwise.
+ * 2 s.  work_dev holds a status word, the worst outcome of every factorisation since bcx_linreg_posterior_factor_clear_status
+ * (enqueued on `stream`; call it once before the first factorisation a status read is to cover -- a whole loop of them, or one
+ * call).  bcx_linreg_posterior_factor_status synchronises the stream and returns BCX_ERR_TIMEOUT if a wait expired, BCX_ERR_STATE
+ * if a pivot was not positive or NaN (NaN / non-finite weights or points: the weights are clamped by max(w, 0) with NumPy's
+ * rule, which keeps a NaN), BCX_OK otherwise; reading does not clear the word.  Where the reference would go on with NaN
+ * weights, the SparseVI loops of the package raise on this status (an error instead of NaN weights).
  * bcx_linreg_posterior_draw_factored: theta_dev (S x ld) = mup + R U^T = (R + 1 u^T) U^T for standard-normal R_dev (S x ld,
  * 16-byte aligned rows), tbar_dev (D) = mup + Rbar U^T for their column means Rbar_dev (ld) -- the mean of the draws. */
 int64_t bcx_linreg_posterior_factor_scratch_bytes(int32_t D);
 int bcx_linreg_posterior_factor(void* stream, int32_t k, int32_t D, int32_t ldx, const void* w_dev, const void* XT_dev,
                                 const void* y_dev, const void* S0inv_dev, int32_t lds0, const void* rhs0_dev, double sigsq,
                                 void* work_dev, int64_t work_bytes, void* U_dev, int64_t ldu, void* u_dev, void* mu_dev);
+int bcx_linreg_posterior_factor_clear_status(void* stream, int32_t D, void* work_dev);
 int bcx_linreg_posterior_factor_status(void* stream, int32_t D, const void* work_dev);
 int bcx_linreg_posterior_draw_factored(void* stream, int32_t D, int32_t ld, const void* U_dev, int64_t ldu, const void* u_dev,
                                        const void* R_dev, const void* Rbar_dev, int32_t S, void* theta_dev, void* tbar_dev);
@@ -357,8 +362,9 @@ int bcx_linreg_posterior_draw_factored(void* stream, int32_t D, int32_t ld, cons
  * the Cholesky factor L of the negative Hessian at the mode (Sigma = W^T W), R_dev (S x ld) standard normal numbers and Rbar_dev
  * their column means.  family 0: logistic, 1: Poisson (softplus rate).  ONE launch of one workgroup (csrc/laplace.hip), the
  * points resident in LDS: serves the (k, D) for which bcx_laplace_sampler_ok is non-zero (D <= 32, the points + four doubles
- * each within 96 KiB).  status_dev (2 int32): [0] 0 converged / 1 iteration limit / 2 no positive definite Newton matrix,
- * [1] Newton steps taken.  Asynchronous on `stream`. */
+ * each within 96 KiB).  status_dev (3 int32): [0] 0 converged / 1 iteration limit / 2 no positive definite Newton matrix (NaN
+ * weights included: they are clamped by max(w, 0) with NumPy's rule, which keeps a NaN), [1] Newton steps taken, [2] the
+ * worst [0] since the caller zeroed it (max over calls: a loop of calls reads it once).  Asynchronous on `stream`. */
 int bcx_laplace_sampler_ok(int32_t k, int32_t D);
 int64_t bcx_laplace_sampler_lds_bytes(int32_t k, int32_t D);
 int bcx_laplace_sampler(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,

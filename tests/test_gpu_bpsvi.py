@@ -112,6 +112,136 @@ def test_fused_gradient_matches_numpy(k, S, D, fam):
     assert np.array_equal(resid, resid2) and np.array_equal(wg, wg2) and np.array_equal(ug, ug2)
 
 
+# ---- 2b. the fused gradient at its edges: Poisson, strided layouts with NaN padding, branch thresholds, the size limits -----
+def _coef(fam, t, y, sigsq):
+    """c(i, s) of every family in NumPy, branch by branch as the reference writes it (model_lr.py:52-56; model_poiss.py:25-29
+    compute_s and :58-66 grad_z_log_likelihood; model_linreg.py:17)."""
+    if fam == 0:
+        m = -t
+        with np.errstate(over="ignore"):
+            e = np.exp(np.where(m < 100, m, 0.0))
+        return np.where(m < 100, e / (1 + e), 1.0)
+    if fam == 1:
+        s = t.copy()
+        big = s > -100
+        s[big] = np.log(np.maximum(s[big], 0) + np.log1p(np.exp(-np.fabs(s[big]))))
+        es = np.exp(s)
+        g = y - es
+        hi = es > 1e-15
+        g[hi] = (y[hi] * np.exp(-s[hi]) - 1.0) * (1.0 - np.exp(-es[hi]))
+        return g
+    return (y - t) / sigsq
+
+
+def _fused_strided(torch, fam, P, D, ycol, th, ldt, colsum, cv, ldcv, w, scaling, sigsq):
+    """bcx_psvi_gradient with P (k x ldp), theta (S x ldt) and corevecs (k x ldcv) as given, every element outside
+    the logical (k x cols, S x D, k x S) blocks set to NaN: a read of padding shows up in the output."""
+    from bayesiancoresets_amd import _native
+    lib = _native.load()
+    dev = torch.device("cuda", 0)
+    k, S = cv.shape
+    dz = D + 1 if fam == 2 else D
+    thp = np.full((S, ldt), np.nan)
+    thp[:, :D] = th
+    cvp = np.full((k, ldcv), np.nan)
+    cvp[:, :S] = cv
+    Pd, td, cd, vd, wd = (torch.from_numpy(np.ascontiguousarray(a)).to(dev) for a in (P, thp, colsum, cvp, w))
+    out = torch.full((S + k + k * dz + 8,), float("nan"), dtype=torch.float64, device=dev)
+    work = torch.full((int(lib.bcx_psvi_gradient_scratch_bytes(k, S)) // 8,), float("nan"), dtype=torch.float64, device=dev)
+    st = int(torch.cuda.current_stream(dev).cuda_stream)
+    rc = lib.bcx_psvi_gradient(st, fam, Pd.data_ptr(), k, P.shape[1], D, ycol, td.data_ptr(), S, ldt, sigsq,
+                               cd.data_ptr(), vd.data_ptr(), ldcv, wd.data_ptr(), scaling, out.data_ptr(), work.data_ptr())
+    assert rc == 0, lib.bcx_project_last_error().decode()
+    h = out.cpu().numpy()
+    assert np.isnan(h[S + k + k * dz:]).all()                  # (nothing written past the output)
+    return h[:S], h[S:S + k], h[S + k:S + k + k * dz].reshape(k, dz)
+
+
+def _want(fam, P, D, ycol, th, colsum, cv, w, scaling, sigsq):
+    """The NumPy fp64 product form of resid / wgrad / ugrad (the one test_fused_gradient_matches_numpy checks against the
+    reference's k x S x dz form where that is small)."""
+    k, S = cv.shape
+    r = scaling * colsum - w.dot(cv)
+    tt = np.hstack((th, np.ones((S, 1)))) if fam == 2 else th
+    t = P[:, :D].dot(th.T)
+    y = np.zeros_like(t) if fam == 0 else np.repeat(P[:, ycol:ycol + 1], S, axis=1)
+    A = _coef(fam, t, y, sigsq) * r[None, :]
+    return r, -cv.dot(r) / S, -(w[:, None] * (A.dot(tt) - A.dot(tt.mean(axis=1))[:, None])) / S
+
+
+def _check_fused(got, want, rtol=1e-10):
+    for g, wv in zip(got, want):
+        assert np.isfinite(g).all()
+        np.testing.assert_allclose(g, wv, rtol=rtol, atol=1e-12 * np.abs(wv).max())
+
+
+@pytest.mark.parametrize("fam", [0, 1, 2])
+@pytest.mark.parametrize("k,S,D", [(7, 40, 5), (33, 256, 301), (300, 1000, 64)])
+@pytest.mark.parametrize("layout", ["samplers", "wide"])
+def test_fused_gradient_strided_layouts(k, S, D, fam, layout):
+    """Family 1 (Poisson, with Poisson-count responses) beside 0 and 2, and the layouts the product passes: ldt = D + D % 2
+    (the samplers' draws) or wider, ldp > cols, ldcv > S, every padding element NaN."""
+    torch = _torch()
+    rs = np.random.RandomState(k + 5 * S + 11 * D + 101 * fam)
+    cols = D + (fam != 0)
+    ldp = cols + (3 if layout == "wide" else 1)
+    ldt = D + D % 2 if layout == "samplers" else D + 5
+    ldcv = S + (1 if layout == "samplers" else 17)
+    th = rs.randn(S, D) / np.sqrt(D)
+    P = np.full((k, ldp), np.nan)
+    P[:, :D] = rs.randn(k, D)
+    if fam == 1:
+        P[:, D] = rs.poisson(3.0, size=k)
+    elif fam == 2:
+        P[:, D] = rs.randn(k)
+    ycol = -1 if fam == 0 else D
+    colsum, cv, w = rs.randn(S) * 50, rs.randn(k, S), rs.rand(k) * 3
+    got = _fused_strided(torch, fam, P, D, ycol, th, ldt, colsum, cv, ldcv, w, 1.3, 0.6)
+    _check_fused(got, _want(fam, P, D, ycol, th, colsum, cv, w, 1.3, 0.6))
+
+
+def test_fused_gradient_at_the_branch_thresholds():
+    """x . theta placed exactly (one non-zero feature, products exact in fp64) on both sides of every branch of the
+    coefficient: logistic m = -t at 100, Poisson t at -100 and e^s at 1e-15 (t near log(1e-15): softplus(t) = e^t there)."""
+    torch = _torch()
+    D, S = 4, 64
+    e15 = np.log(1e-15)
+    ts = {0: [-100.0, -100.0 + 2 ** -40, -100.0 - 2 ** -40, -99.0, -101.0, -150.0, 30.0, 0.0],
+          1: [-100.0, -100.0 + 2 ** -40, -100.0 - 2 ** -40, -99.5, -100.5, e15, e15 * (1 + 1e-12), e15 * (1 - 1e-12), e15 - 0.5, e15 + 0.5,
+              -700.0, 0.0, 40.0]}
+    rs = np.random.RandomState(12)
+    for fam, tv in ts.items():
+        k = len(tv)
+        P = np.zeros((k, D + 1))
+        P[:, 0] = tv                                            # x = (t, 0, 0, 0): t = x . theta_s for theta_s[0] = 1
+        P[:, D] = rs.poisson(2.0, size=k)
+        th = np.zeros((S, D))
+        th[:, 0] = 1.0
+        th[1:, 1:] = rs.randn(S - 1, D - 1)                     # (zero features: no contribution to t, but to the gradient)
+        th[S // 2:, 0] = rs.choice([0.5, 2.0, 1.0 + 2 ** -20], size=S - S // 2)   # (exact products, t / 2, 2 t, ...)
+        colsum, cv, w = rs.randn(S) * 10, rs.randn(k, S), rs.rand(k) + 0.5
+        ycol = -1 if fam == 0 else D
+        got = _fused_strided(torch, fam, P, D, ycol, th, D + D % 2, colsum, cv, S, w, 1.0, 1.0)
+        _check_fused(got, _want(fam, P, D, ycol, th, colsum, cv, w, 1.0, 1.0))
+
+
+@pytest.mark.parametrize("fam", [0, 1])
+def test_fused_gradient_at_the_size_limits(fam):
+    """k = 4096 pseudo-points, S = 8192 samples, D = 1024 features (BCX_PSVI_MAX_*) against the NumPy fp64 product form."""
+    torch = _torch()
+    k, S, D = 4096, 8192, 1024
+    rs = np.random.RandomState(5 + fam)
+    th = rs.randn(S, D) / np.sqrt(D)
+    P = np.empty((k, D + 2))
+    P[:, :D] = rs.randn(k, D)
+    P[:, D] = rs.poisson(2.0, size=k)
+    P[:, D + 1] = np.nan
+    colsum, cv, w = rs.randn(S) * 50, rs.randn(k, S), rs.rand(k) * 3
+    ycol = -1 if fam == 0 else D
+    got = _fused_strided(torch, fam, P, D, ycol, th, D, colsum, cv, S, w, 1.1, 1.0)
+    _check_fused(got, _want(fam, P, D, ycol, th, colsum, cv, w, 1.1, 1.0))
+
+
 def test_limits_return_errors():
     torch = _torch()
     from bayesiancoresets_amd import _native

@@ -294,6 +294,7 @@ def test_posterior_factor_kernel(bc, D, k, prior):
     U, mu, uv = torch.zeros(D, ld, dtype=torch.float64, device="cuda"), torch.zeros(D, dtype=torch.float64, device="cuda"), torch.zeros(D, dtype=torch.float64, device="cuda")
     w_d, X_d, y_d, S_d, r_d = d(w if k else np.zeros(1)), d(XT), d(pts[:, -1] if k else np.zeros(1)), d(S0inv), d(S0inv.dot(mu0))
     st = int(torch.cuda.current_stream().cuda_stream)
+    assert lib.bcx_linreg_posterior_factor_clear_status(st, D, work.data_ptr()) == 0     # (the status word covers both calls)
     for rep in range(2):                                      # (the second call reuses the scratch: flags, tiles)
         rc = lib.bcx_linreg_posterior_factor(st, k, D, ldk, w_d.data_ptr(), X_d.data_ptr(), y_d.data_ptr(), S_d.data_ptr(), D, r_d.data_ptr(),
                                              sigsq, work.data_ptr(), work.numel() * 8, U.data_ptr(), ld, uv.data_ptr(), mu.data_ptr())
