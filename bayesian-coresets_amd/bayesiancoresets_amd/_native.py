@@ -26,8 +26,8 @@ SYMBOLS = (
     "bcx_create", "bcx_destroy", "bcx_last_error", "bcx_set_stream", "bcx_load_rows", "bcx_chunk_sums", "bcx_export_chunk_sums",
     "bcx_finalize", "bcx_build_begin", "bcx_step_scan", "bcx_step_apply", "bcx_build_enqueue", "bcx_build_poll",
     "bcx_step_scan_exact", "bcx_build_trace", "bcx_active_count", "bcx_get_weights", "bcx_error", "bcx_optimize",
-    "bcx_reset", "bcx_reached_numeric_limit", "bcx_get_vector", "bcx_get_norms", "bcx_argmax_correlation", "bcx_time_scan",
-    "bcx_stats", "bcx_profile_scan", "bcx_profile_read", "bcx_version",
+    "bcx_reset", "bcx_reached_numeric_limit", "bcx_get_vector", "bcx_get_norms", "bcx_get_stored_rows", "bcx_argmax_correlation", "bcx_time_scan",
+    "bcx_stats", "bcx_screen_stats", "bcx_screen_read", "bcx_profile_scan", "bcx_profile_read", "bcx_version",
     "bcx_project_write", "bcx_project_colsum", "bcx_project_select", "bcx_project_last_error",
     "bcx_build_enqueue_exact", "bcx_exchange_export", "bcx_exchange_attach", "bcx_exchange_probe", "bcx_exchange_disable", "bcx_exchange_set_timeout",
     "bcx_set_check_monotone", "bcx_project_profile", "bcx_project_profile_read", "bcx_exchange_stats", "bcx_load_rows_flags", "bcx_project_write_raw", "bcx_omp_stats", "bcx_project_select_ws", "bcx_project_select_scratch_bytes",
@@ -133,10 +133,13 @@ def load():
         "bcx_reached_numeric_limit": [vp, P(i32)],
         "bcx_get_vector": [vp, i32, vp],
         "bcx_get_norms": [vp, i64, i64, vp],
+        "bcx_get_stored_rows": [vp, i64, i64, vp, P(i32)],
         "bcx_argmax_correlation": [vp, vp, P(i64), P(dbl)],
         "bcx_time_scan": [vp, i32, i32, P(dbl), P(dbl)],
         "bcx_stats": [vp, P(i64), P(i64), P(i64)],
         "bcx_omp_stats": [vp, vp],
+        "bcx_screen_stats": [vp, vp],
+        "bcx_screen_read": [vp, i64, i64, vp, vp, vp, P(i32)],
         "bcx_profile_scan": [vp, i32],
         "bcx_profile_read": [vp, P(dbl), P(i64)],
         "bcx_build_enqueue_exact": [vp],
@@ -453,6 +456,17 @@ class Engine(object):
             self._check(self.lib.bcx_get_norms(self.h, begin, count, out.ctypes.data))
         return out
 
+    def stored_rows(self, begin=0, count=None):
+        """The normalised rows as stored on the device ([count, d] in the storage type)."""
+        count = self.n_local - begin if count is None else count
+        ld = ctypes.c_int32()
+        self._check(self.lib.bcx_get_stored_rows(self.h, begin, 0, None, ctypes.byref(ld)))
+        dt = {F64: np.float64, F16: np.float16}.get(self.cfg.store_dtype, np.float32)
+        out = np.empty((count, ld.value), dtype=dt)
+        if count:
+            self._check(self.lib.bcx_get_stored_rows(self.h, begin, count, out.ctypes.data, ctypes.byref(ld)))
+        return out[:, :self.d]
+
     def argmax_correlation(self, query):
         q = np.ascontiguousarray(query, dtype=np.float64)
         assert q.shape == (self.d,)
@@ -471,6 +485,30 @@ class Engine(object):
         a, b, c = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int64()
         self._check(self.lib.bcx_stats(self.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
         return {"exact_fallbacks": a.value, "candidates": b.value, "resolves": c.value}
+
+    SCREEN_DROP = {0: "in use", 1: "dropped by the overflow rule until reset()", 2: "no device memory for the shadow",
+                   3: "switched off or not applicable"}
+
+    def screen_stats(self):
+        """The 8-bit screening tier: iterations screened, rows that survived it (re-scored from the stored rows), capture
+        overflows and iterations redone with the storage-precision scan (not exact fallbacks), its state and footprint."""
+        out = (ctypes.c_int64 * 8)()
+        self._check(self.lib.bcx_screen_stats(self.h, out))
+        return {"active": bool(out[0]), "screened": out[1], "survivors": out[2], "overflows": out[3], "storage_redos": out[4],
+                "state": self.SCREEN_DROP.get(int(out[5]), "?"), "device_bytes": out[6], "build_us": out[7]}
+
+    def screen_read(self, begin=0, count=None):
+        """(codes uint8 [count, ld8], scales fp32 [count], bounds fp32 [count]) of the tier's shadow rows."""
+        count = self.n_local - begin if count is None else count
+        ld8 = (self.d + 15) // 16 * 16
+        codes = np.empty((count, ld8), dtype=np.uint8)
+        sc = np.empty(count, dtype=np.float32)
+        bd = np.empty(count, dtype=np.float32)
+        got = ctypes.c_int32()
+        self._check(self.lib.bcx_screen_read(self.h, begin, count, codes.ctypes.data, sc.ctypes.data, bd.ctypes.data,
+                                             ctypes.byref(got)))
+        assert got.value == ld8
+        return codes, sc, bd
 
     def omp_stats(self):
         out = (ctypes.c_int64 * 4)()

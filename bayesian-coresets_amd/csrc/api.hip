@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cmath>
 #include "bcx_internal.h"
+#include "dev_util.h"
 
 static thread_local std::string g_create_err;
 namespace {   // pinned upload buffers, one pair per device (defined with the upload code below)
@@ -35,7 +36,8 @@ static void free_all(bcx_solver* s) {
     if (p) (void)hipFree(p);
   for (size_t w = 0; w < s->peer_mbox.size(); ++w)
     if (s->peer_mbox[w] && s->peer_mbox[w] != s->mbox) (void)hipIpcCloseMemHandle(s->peer_mbox[w]);
-  void* xptrs[] = {s->mbox, s->peer_tab, s->xseq, s->xprobe, s->rec_gather, s->grid_counter, s->fin_part, s->gram_work, s->warm_buf, s->pflags, s->pdbg};
+  void* xptrs[] = {s->mbox, s->peer_tab, s->xseq, s->xprobe, s->rec_gather, s->grid_counter, s->fin_part, s->gram_work, s->warm_buf, s->pflags, s->pdbg,
+                   s->Aq, s->scr_sb, s->scr_partials, s->scr_stat};
   for (void* p : xptrs)
     if (p) (void)hipFree(p);
   for (auto& ev : s->prof_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -60,6 +62,7 @@ extern "C" int bcx_create(const bcx_config* cfg, bcx_solver** out) {
   bcx_solver* s = new bcx_solver();
   s->cfg = *cfg;
   if (s->cfg.refresh_every == 0) s->cfg.refresh_every = 64;
+  if (const char* e = bcx_dev_env("BCX_SCREEN8")) s->scr_enabled = atoi(e) != 0;   // dev: 0 = the parent's path (storage-precision scan only)
   hipError_t e = hipSetDevice(cfg->device);
   if (e != hipSuccess) { g_create_err = std::string("hipSetDevice: ") + hipGetErrorString(e); delete s; return BCX_ERR_HIP; }
   const int d = cfg->d;
@@ -287,6 +290,7 @@ static int load_rows(bcx_solver* s, const void* src, int32_t src_is_device, int3
     }
   }
   s->rows_loaded += rows;
+  s->scr_valid = false;      // the shadow (screen8.hip) is rebuilt from the new rows before the next enqueued iteration
   return BCX_OK;
 }
 
@@ -462,8 +466,18 @@ static int step_scan(bcx_solver* s, void* send_dev, int exact, bool with_tail) {
   return bcx_launch_resolve(s, send, exact);
 }
 
-extern "C" int bcx_step_scan(bcx_solver* s, void* send_dev) { return s ? step_scan(s, send_dev, 0, false) : BCX_ERR_ARG; }
-extern "C" int bcx_step_scan_exact(bcx_solver* s, void* send_dev) { return s ? step_scan(s, send_dev, 1, false) : BCX_ERR_ARG; }
+// the scan of one enqueued iteration: the 8-bit screen + refine (screen8.hip) or the storage-precision / exact scan
+static int front_scan(bcx_solver* s, int exact, bool tier) {
+  int rc;
+  if (exact && (rc = bcx_launch_resume_exact(s))) return rc;
+  if ((rc = prof_begin(s))) return rc;
+  if ((rc = (tier && !exact) ? bcx_launch_screen(s) : bcx_launch_scan(s, exact))) return rc;
+  return prof_end(s);
+}
+
+// (the host-driven step always takes the storage-precision scan: the tier's redo lives in bcx_build_poll's enqueue route)
+extern "C" int bcx_step_scan(bcx_solver* s, void* send_dev) { if (s) s->scr_batch = false; return s ? step_scan(s, send_dev, 0, false) : BCX_ERR_ARG; }
+extern "C" int bcx_step_scan_exact(bcx_solver* s, void* send_dev) { if (s) s->scr_batch = false; return s ? step_scan(s, send_dev, 1, false) : BCX_ERR_ARG; }
 
 extern "C" int bcx_step_apply(bcx_solver* s, const void* recv_dev) {
   if (!s) return BCX_ERR_ARG;
@@ -471,60 +485,66 @@ extern "C" int bcx_step_apply(bcx_solver* s, const void* recv_dev) {
 }
 
 // one whole iteration without the host: single shard, or row shards with an attached peer mailbox
-static int enqueue_one(bcx_solver* s, int exact) {
+static int enqueue_one(bcx_solver* s, int exact, bool tier) {
+  if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
+  int rc;
   if (s->cfg.world_size != 1) {
     if (!s->exchange_ready) {
       s->err = "bcx_build_enqueue on a row shard needs bcx_exchange_attach (or drive bcx_step_scan / bcx_step_apply)";
       return BCX_ERR_ARG;
     }
-    int rc;
-    if (exact && (rc = bcx_launch_resume_exact(s))) return rc;
-    if ((rc = prof_begin(s))) return rc;
-    if ((rc = bcx_launch_scan(s, exact))) return rc;
-    if ((rc = prof_end(s))) return rc;
+    if ((rc = front_scan(s, exact, tier))) return rc;
     return bcx_launch_tail_exchange(s, exact);
   }
+  if ((rc = front_scan(s, exact, tier))) return rc;
   if (s->cfg.alg == BCX_ALG_OMP) {
     // scan, then the fused resolve + OMP step (omp_lh.hip); where that does not apply: resolve_kernel + the multi-kernel step
-    int rc;
-    if (exact && (rc = bcx_launch_resume_exact(s))) return rc;
-    if ((rc = prof_begin(s))) return rc;
-    if ((rc = bcx_launch_scan(s, exact))) return rc;
-    if ((rc = prof_end(s))) return rc;
     rc = bcx_launch_omp_fused(s, exact);
     if (rc != 1) return rc;
     if ((rc = bcx_launch_resolve(s, s->rec_local, exact))) return rc;
     return bcx_launch_apply(s, s->rec_local);
   }
-  return step_scan(s, nullptr, exact, true);
+  return bcx_launch_tail(s, exact);   // resolve + apply in one launch (single shard, GIGA/FW)
 }
 
-extern "C" int bcx_build_enqueue(bcx_solver* s, int64_t itrs) {
-  if (!s) return BCX_ERR_ARG;
-  if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
+// `itrs` iterations through the 8-bit tier when it is on (default), else as the parent did
+static int enqueue_many(bcx_solver* s, int64_t itrs) {
+  int rc = bcx_screen_build(s);
+  if (rc != BCX_OK) return rc;
+  const bool tier = bcx_screen_on(s) && s->scr_valid;
   int64_t i = 0;
   // single shard, GIGA / FW, a few GB of rows: batches of iterations per launch with the tail's workgroup resident beside
-  // the scan's (persist.hip); everything else, and what that form declines: one launch per kernel
+  // the scan's (persist.hip, opt-in; it keeps the storage-precision scan); everything else, and what that form declines:
+  // one launch per kernel
   bool batches = s->cfg.world_size == 1 && s->cfg.alg != BCX_ALG_OMP;
+  s->scr_batch = false;
   while (i < itrs) {
     if (batches) {
       int64_t covered = 0;
-      const int rc = bcx_launch_persist(s, itrs - i, &covered);
+      rc = bcx_launch_persist(s, itrs - i, &covered);
       if (rc == BCX_OK) { i += covered; continue; }
       if (rc != 1) return rc;
       batches = false;
     }
-    const int rc = enqueue_one(s, 0);
+    s->scr_batch = tier;
+    rc = enqueue_one(s, 0, tier);
     if (rc != BCX_OK) return rc;
     ++i;
   }
   return BCX_OK;
 }
 
+extern "C" int bcx_build_enqueue(bcx_solver* s, int64_t itrs) {
+  if (!s) return BCX_ERR_ARG;
+  if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
+  return enqueue_many(s, itrs);
+}
+
 extern "C" int bcx_build_enqueue_exact(bcx_solver* s) {
   if (!s) return BCX_ERR_ARG;
   if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
-  return enqueue_one(s, 1);
+  s->scr_batch = false;
+  return enqueue_one(s, 1, false);
 }
 
 // ---- peer mailbox --------------------------------------------------------------------------------
@@ -650,6 +670,27 @@ extern "C" int bcx_build_poll(bcx_solver* s, int64_t* n_done, int32_t* need_exac
   DevState h;
   int rc = read_state(s, &h);
   if (rc != BCX_OK) return rc;
+  // A tier iteration that halted (its capture overflowed, or the survivors overflowed resolve_core's window) is redone HERE
+  // with the storage-precision scan -- one scan of the stored rows, not the fp64 exact scan, and not an exact fallback --
+  // and the rest of the call is enqueued again behind it.  The halt is replicated state, so every rank of a row-sharded
+  // build takes the same route.  Only a halt of the storage-precision iteration itself is reported as need_exact.
+  // Drop rule: 4 such halts within 256 screened iterations (far above the < 1 % the tier is built for: rows of low
+  // numerical rank, near-duplicates, GIGA past M > d) drop the tier until bcx_reset; a step then costs what it did without it.
+  while (h.halt == HALT_NEED_EXACT && s->scr_batch && s->scr_stat) {
+    unsigned long long st8[SCR_WORDS];
+    BCX_HIP(hipMemcpy(st8, s->scr_stat, sizeof st8, hipMemcpyDeviceToHost));
+    if (!st8[SCR_ARMED]) break;                       // the storage-precision redo itself halted
+    s->scr_halts += 1;
+    for (int i = 3; i > 0; --i) s->scr_ovf_at[i] = s->scr_ovf_at[i - 1];
+    s->scr_ovf_at[0] = st8[SCR_ITERS];
+    if (s->scr_halts >= 4 && s->scr_ovf_at[0] - s->scr_ovf_at[3] < 256) s->scr_dropped = 1;
+    if ((rc = bcx_launch_resume_store(s))) return rc;
+    if ((rc = enqueue_one(s, 0, false))) return rc;
+    const int64_t rest = h.itrs - h.it - 1;
+    if (rest > 0 && (rc = enqueue_many(s, rest))) return rc;
+    else if (rest <= 0) s->scr_batch = false;
+    if ((rc = read_state(s, &h))) return rc;
+  }
   if (h.halt == HALT_GRID_TIMEOUT) { s->err = "OMP step: grid barrier timed out"; return BCX_ERR_STATE; }
   if (h.halt == HALT_EXCHANGE_TIMEOUT) {
     // which peers' flags never arrived (recorded by the waiting lanes, csrc/resolve.hip mailbox_exchange)
@@ -671,7 +712,8 @@ extern "C" int bcx_build_poll(bcx_solver* s, int64_t* n_done, int32_t* need_exac
     // launches issued after the state machine stopped (end of call, latch) return at once: keep only launches that
     // did the scan -- one that "read" the shard faster than 1.5x the HBM peak cannot have (a whole batch may consist
     // of such launches, e.g. everything enqueued after a latch, so the test is absolute, not relative to the batch)
-    const double min_ms = (double)s->cfg.n_local * s->cfg.d * s->elem / 12.0e9;
+    // (with the 8-bit tier on, a launch reads one byte per element)
+    const double min_ms = (double)s->cfg.n_local * s->cfg.d * ((bcx_screen_on(s) && s->scr_valid) ? 1 : s->elem) / 12.0e9;
     for (size_t i = 0; i < s->prof_used; ++i) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, s->prof_events[i].first, s->prof_events[i].second) != hipSuccess) continue;
@@ -756,6 +798,9 @@ extern "C" int bcx_reset(bcx_solver* s) {
   h.err = h.bnorm; h.nw = 1.0; h.it = 0; h.itrs = 0;
   BCX_HIP(hipMemcpy(s->st, &h, sizeof h, hipMemcpyHostToDevice));
   BCX_HIP(hipMemset(s->xw, 0, (size_t)s->cfg.d * 8));
+  if (s->scr_dropped == 1) s->scr_dropped = 0;      // the overflow rule's drop lasts until here
+  s->scr_halts = 0;
+  for (int i = 0; i < 4; ++i) s->scr_ovf_at[i] = 0;
   // error() with an empty list must give ||b|| computed the same way as after finalize
   return bcx_launch_error_refresh(s);
 }
@@ -807,6 +852,19 @@ extern "C" int bcx_get_norms(bcx_solver* s, int64_t begin, int64_t count, double
   if (!s || !out || begin < 0 || begin + count > s->cfg.n_local) return BCX_ERR_ARG;
   BCX_HIP(hipStreamSynchronize(s->stream));
   BCX_HIP(hipMemcpy(out, s->norms + begin, (size_t)count * 8, hipMemcpyDeviceToHost));
+  return BCX_OK;
+}
+
+// The stored (normalised) rows [begin, begin + count) as the scan reads them: count x ld elements of the storage type
+// (ld = d rounded up to 16 bytes' worth of elements, returned in *ld_out; elements beyond d are padding).
+extern "C" int bcx_get_stored_rows(bcx_solver* s, int64_t begin, int64_t count, void* out, int32_t* ld_out) {
+  if (!s || begin < 0 || count < 0 || begin + count > s->cfg.n_local) return BCX_ERR_ARG;
+  if (ld_out) *ld_out = s->ld;
+  if (count == 0) return BCX_OK;
+  if (!out) return BCX_ERR_ARG;
+  BCX_HIP(hipSetDevice(s->cfg.device));
+  BCX_HIP(hipStreamSynchronize(s->stream));
+  BCX_HIP(hipMemcpy(out, (const char*)s->An + (size_t)begin * s->ld * s->elem, (size_t)count * s->ld * s->elem, hipMemcpyDeviceToHost));
   return BCX_OK;
 }
 
@@ -897,6 +955,53 @@ extern "C" int bcx_stats(bcx_solver* s, int64_t* exact_fallbacks, int64_t* candi
   if (exact_fallbacks) *exact_fallbacks = h.n_exact;
   if (candidates) *candidates = h.n_cand;
   if (resolves) *resolves = h.n_resolved;
+  return BCX_OK;
+}
+
+// The 8-bit screening tier (screen8.hip) since construction: out8 = {1 if the next enqueued iteration goes through it,
+// iterations screened, survivors re-scored from the stored rows (over the iterations that did not overflow), capture
+// overflows, iterations redone with the storage-precision scan (capture overflows + survivor storms in resolve), drop state
+// (0 in use, 1 dropped by the overflow rule until bcx_reset, 2 no memory for the shadow, 3 switched off or not applicable),
+// bytes of device memory the tier holds, microseconds the last build of the shadow took}
+extern "C" int bcx_screen_stats(bcx_solver* s, int64_t* out8) {
+  if (!s || !out8) return BCX_ERR_ARG;
+  unsigned long long st8[SCR_WORDS] = {0, 0, 0, 0, 0, 0, 0, 0};
+  if (s->scr_stat) {
+    BCX_HIP(hipSetDevice(s->cfg.device));
+    BCX_HIP(hipStreamSynchronize(s->stream));
+    BCX_HIP(hipMemcpy(st8, s->scr_stat, sizeof st8, hipMemcpyDeviceToHost));
+  }
+  const bool possible = s->scr_enabled && s->cfg.store_dtype != BCX_F64 && s->cfg.d <= 4096 && s->cfg.n_local > 0;
+  out8[0] = bcx_screen_on(s) ? 1 : 0;
+  out8[1] = (int64_t)st8[SCR_ITERS];
+  out8[2] = (int64_t)st8[SCR_SURVIVORS];
+  out8[3] = (int64_t)st8[SCR_OVERFLOWS];
+  out8[4] = (int64_t)st8[SCR_REDOS];
+  out8[5] = !possible ? 3 : s->scr_dropped;
+  out8[6] = s->Aq ? (int64_t)s->scr_cap_rows * (s->ld8 + 8) + (int64_t)BCX_MAX_PARTIALS * BCX_PARTIAL_BYTES + SCR_WORDS * 8 : 0;
+  out8[7] = (int64_t)(s->scr_build_ms * 1e3f);
+  return BCX_OK;
+}
+
+// Read back `count` rows of the shadow from local row `begin`: codes (count x ld8 bytes, ld8 = d rounded up to 16; returned
+// in *ld8_out), scales and bounds (count floats each).  Builds the shadow first if it is due.  BCX_ERR_STATE without a tier.
+extern "C" int bcx_screen_read(bcx_solver* s, int64_t begin, int64_t count, void* codes, float* scales, float* bounds, int32_t* ld8_out) {
+  if (!s || begin < 0 || count < 0 || begin + count > s->cfg.n_local) return BCX_ERR_ARG;
+  if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
+  BCX_HIP(hipSetDevice(s->cfg.device));
+  int rc = bcx_screen_build(s);
+  if (rc != BCX_OK) return rc;
+  if (!bcx_screen_on(s) || !s->scr_valid) { s->err = "bcx_screen_read: the 8-bit tier is not in use"; return BCX_ERR_STATE; }
+  BCX_HIP(hipStreamSynchronize(s->stream));
+  if (ld8_out) *ld8_out = s->ld8;
+  if (count == 0) return BCX_OK;
+  if (codes) BCX_HIP(hipMemcpy(codes, (const char*)s->Aq + (size_t)begin * s->ld8, (size_t)count * s->ld8, hipMemcpyDeviceToHost));
+  std::vector<float> sb((size_t)count * 2);
+  BCX_HIP(hipMemcpy(sb.data(), (const char*)s->scr_sb + (size_t)begin * 8, (size_t)count * 8, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < count; ++i) {
+    if (scales) scales[i] = sb[2 * i];
+    if (bounds) bounds[i] = sb[2 * i + 1];
+  }
   return BCX_OK;
 }
 

@@ -30,6 +30,15 @@ struct PartialView {
 };
 #define BCX_PARTIAL_BYTES 40   // per workgroup: 4 doubles + 2 int32
 #define BCX_MAX_PARTIALS 2048
+// 8-bit screening tier (screen8.hip): survivors per iteration that the refine kernel re-scores from the stored rows, and the
+// words of its device-side record
+#define BCX_SCREEN_MAX_SURV 256
+enum { SCR_ARMED = 0,       // the iteration in flight (or the one that halted) was screened by the tier
+       SCR_ITERS = 1,       // iterations screened
+       SCR_SURVIVORS = 2,   // rows re-scored from the stored rows, summed over the iterations that did not overflow
+       SCR_OVERFLOWS = 3,   // iterations whose capture overflowed (a third survivor in one wave, or too many)
+       SCR_REDOS = 4,       // halted tier iterations redone with the storage-precision scan
+       SCR_WORDS = 8 };
 static inline __host__ __device__ PartialView partial_view(void* base, int n) {
   PartialView v;
   v.U1 = (double*)base; v.U2 = v.U1 + n; v.U3 = v.U2 + n; v.L = v.U3 + n;
@@ -177,6 +186,20 @@ struct bcx_solver {
   unsigned* pflags = nullptr;    // [0] GO (tail -> scan workgroups), [1 + b] stamp of scan workgroup b; sequence numbers
   uint64_t pseq = 0;             // iterations enqueued that way so far (they never restart)
   long long* pdbg = nullptr;     // dev: time stamps of the last launch (BCX_PERSIST_DBG)
+  // 8-bit screening tier (screen8.hip)
+  void* Aq = nullptr;            // n_local x ld8 codes
+  void* scr_sb = nullptr;        // n_local x (fp32 scale, fp32 bound)
+  void* scr_partials = nullptr;  // per-wave partials of the screen kernel
+  unsigned long long* scr_stat = nullptr;   // SCR_* words
+  int ld8 = 0;
+  int64_t scr_cap_rows = 0;
+  bool scr_enabled = true;       // off: BCX_SCREEN8=0 (dev switch)
+  int scr_dropped = 0;           // 1: dropped by the overflow rule until bcx_reset, 2: no memory for the shadow
+  bool scr_valid = false;        // the shadow matches the stored rows
+  bool scr_batch = false;        // the iterations enqueued last went through the tier
+  float scr_build_ms = 0.f;
+  uint64_t scr_ovf_at[4] = {0, 0, 0, 0};   // SCR_ITERS stamps of the last four halts (drop rule, api.hip)
+  int64_t scr_halts = 0;
   // measurement
   bool profile = false;
   bool prof_now = false;
@@ -215,6 +238,11 @@ int bcx_gram_rows(hipStream_t st, const double* rows, int k, int d, int64_t ld, 
 unsigned long long bcx_gram_sk_epoch_now();
 int bcx_gram_sk_timed_out(hipStream_t st, const double* work, unsigned long long since);
 int bcx_scan_grid(const bcx_solver* s);
+// screen8.hip
+bool bcx_screen_on(const bcx_solver* s);
+int bcx_screen_build(bcx_solver* s);
+int bcx_launch_screen(bcx_solver* s);
+int bcx_launch_resume_store(bcx_solver* s);
 
 #ifdef BCX_TIMING
 #define BCX_STAMP(st, i) do { if (threadIdx.x == 0) (st)->dbg_t[i] = wall_clock64(); } while (0)

@@ -182,6 +182,9 @@ int bcx_reached_numeric_limit(bcx_solver* s, int32_t* limit);
 int bcx_get_vector(bcx_solver* s, int32_t which, double* out);
 /* Copy row norms of local rows [begin, begin+count) (Anorms, frankwolfe.py:10). */
 int bcx_get_norms(bcx_solver* s, int64_t begin, int64_t count, double* out);
+/* The stored (normalised) rows [begin, begin + count) as the scan reads them: count x ld elements of the storage type
+ * (fp32, fp16 or fp64; ld = d rounded up to a multiple of 16 bytes, returned in *ld_out; elements beyond d are padding). */
+int bcx_get_stored_rows(bcx_solver* s, int64_t begin, int64_t count, void* out, int32_t* ld_out);
 /* One N-way correlation scan with a caller-supplied query (d doubles, host): *idx = arg-max_n of
  * An[n] . query (first maximum, global row index), *score = its exact fp64 value.  The select step of
  * SparseVI on projected vectors (sparsevi.py:49-56).  FW / OMP handles only. */
@@ -192,6 +195,19 @@ int bcx_time_scan(bcx_solver* s, int32_t reps, int32_t exact, double* ms_per_lau
 /* Diagnostics since construction: iterations that fell back to the exact fp64 scan, candidate rows re-scored
  * in fp64 (total) and resolve passes (candidates / resolves = mean candidates per iteration). */
 int bcx_stats(bcx_solver* s, int64_t* exact_fallbacks, int64_t* candidates, int64_t* resolves);
+/* The 8-bit screening tier (default path of bcx_build_enqueue for fp32 / fp16 storage, d <= 4096): every greedy iteration
+ * streams a one-byte-per-element shadow of the stored rows, whose per-row error bound makes the scan a rigorous enclosure;
+ * the few rows it cannot exclude are re-scored from the stored rows, then in fp64 as before, so selections do not change.
+ * out8 = {1 if the next enqueued iteration goes through the tier, iterations screened, survivors re-scored from the stored
+ * rows, capture overflows, iterations redone with the storage-precision scan (these are NOT exact fallbacks), drop state
+ * (0 in use, 1 dropped until bcx_reset after 4 redone iterations within 256 screened ones, 2 no device memory for the
+ * shadow, 3 switched off or not applicable), device bytes held by the tier, microseconds the last shadow build took}.
+ * bcx_stats keeps its meaning: `candidates` counts rows re-scored in fp64. */
+int bcx_screen_stats(bcx_solver* s, int64_t* out8);
+/* Read back rows [begin, begin + count) of the shadow: codes (count x ld8 bytes, ld8 = d rounded up to 16, returned in
+ * *ld8_out; value = (code - 128) * scale), per-row scales and per-row upper bounds of ||stored row - dequantised row||_2.
+ * Builds the shadow if it is due (it is built before the first enqueued iteration after bcx_finalize). */
+int bcx_screen_read(bcx_solver* s, int64_t begin, int64_t count, void* codes, float* scales, float* bounds, int32_t* ld8_out);
 /* Sum of scan-kernel time recorded by hipEvents during bcx_build_enqueue: on = 1 times every scan launch,
  * on = N > 1 every N-th one (an event pair costs several microseconds of stream time), on = 0 stops. */
 /* OMP step diagnostics since construction: out4 = {steps taken, columns that left the passive set, from-scratch re-solves
