@@ -11,6 +11,7 @@ from .coreset import Coreset, HilbertCoreset, UniformSamplingCoreset, SparseVICo
 from .projector import BlackBoxProjector, Projector, DeviceProjector
 from .linreg_sampler import LinregPosteriorSampler
 from .laplace_sampler import LaplacePosteriorSampler
+from .gaussian_sampler import GaussianPosteriorSampler
 from . import snnls
 from . import util
 

@@ -42,6 +42,8 @@ SYMBOLS = (
     "bcx_center_rows", "bcx_row_sumsq", "bcx_project_write_points",
     "bcx_laplace_sampler", "bcx_laplace_sampler_ok", "bcx_laplace_sampler_lds_bytes",
     "bcx_project_grad_points", "bcx_psvi_gradient", "bcx_psvi_gradient_scratch_bytes",
+    "bcx_gaussian_operand", "bcx_gaussian_first_moment", "bcx_gaussian_first_moment_scratch_bytes", "bcx_gaussian_colsum_moments",
+    "bcx_gaussian_posterior_draw", "bcx_project_grad_points_gaussian", "bcx_psvi_gradient_gaussian",
 )
 
 
@@ -182,6 +184,14 @@ def load():
     sigs["bcx_row_sumsq"] = [vp, vp, i64, i32, i64, vp]
     sigs["bcx_project_grad_points"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp]
     sigs["bcx_psvi_gradient"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp, i64, vp, dbl, vp, vp]
+    sigs["bcx_gaussian_operand"] = [vp, vp, i32, i64, i32, vp, i64, vp, vp, i64, i32, vp]
+    sigs["bcx_gaussian_first_moment"] = [vp, vp, i64, i64, i32, vp, vp, i64]
+    lib.bcx_gaussian_first_moment_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_gaussian_first_moment_scratch_bytes.argtypes = [i64, i32]
+    sigs["bcx_gaussian_colsum_moments"] = [vp, vp, dbl, i32, vp, i32, i64, vp]
+    sigs["bcx_gaussian_posterior_draw"] = [vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
+    sigs["bcx_project_grad_points_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp]
+    sigs["bcx_psvi_gradient_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp, i64, vp, dbl, vp, vp]
     lib.bcx_psvi_gradient_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_psvi_gradient_scratch_bytes.argtypes = [i32, i32]
     sigs["bcx_linreg_posterior_draw_factored"] = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp]

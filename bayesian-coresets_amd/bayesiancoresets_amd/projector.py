@@ -53,20 +53,31 @@ class DeviceProjector(Projector):
     family: "logistic"  rows z = y*x,            model_lr.py:25-32
             "poisson"   rows z = [x, y],         model_poiss.py:25-38
             "linreg"    rows z = [x, y], sigsq,  model_linreg.py:4-10
+            "gaussian"  rows z = x, Siginv,      model_gaussian.py:4-10 (unknown mean, known covariance; ``sigsq`` is ignored)
+
+    The Gaussian family's centred log-likelihoods are linear in the point: with ``tbar`` the mean of the draws,
+    ``vecs[n, s] = (x_n - tbar) . g_s - d_s . g_s / 2`` minus the row mean, ``d_s = theta_s - tbar``, ``g_s = Siginv d_s`` -- the
+    expansion around the mean draw, which never forms the terms of size ``theta' Siginv theta`` that the literal
+    form subtracts from each other.  ``g_s`` and the per-draw bias are formed on the device whenever draws are installed
+    (csrc/gauss.hip) and are what the projection kernel reads; ``samples`` stays the draws themselves.
     """
-    FAMILIES = {"logistic": 0, "poisson": 1, "linreg": 2}
+    FAMILIES = {"logistic": 0, "poisson": 1, "linreg": 2, "gaussian": 3}
 
     def __init__(self, family, sampler, projection_dimension, sigsq=1.0, device=0, group=None, row_offset=0, colsum="auto",
-                 loglikelihood=None, grad_loglikelihood=None):
+                 loglikelihood=None, grad_loglikelihood=None, Siginv=None):
         """``group`` / ``row_offset``: row-sharded use (one process per GPU, every rank constructs the
         projector with the same sampler and seeds): ``pts`` passed to the fused consumers are this
         rank's rows starting at global row ``row_offset``; column sums are all-reduced and the arg-max
         is taken over all ranks (lowest global row wins ties).
 
-        ``colsum`` (family "linreg" only; the others always project): how ``project_colsum`` of a large data set is formed --
+        ``Siginv`` (family "gaussian"): the D x D inverse of the likelihood's covariance, symmetric positive definite; None is
+        the identity.
+
+        ``colsum`` (families "linreg" and "gaussian"; the others always project): how ``project_colsum`` of a large data set is formed --
         "mfma": one fused fp64-MFMA projection per call (2 N D S flops);
         "moments": in closed form from the (D+1) x (D+1) second moments of the data, formed once per data set
-        (csrc/moments.hip; O(S D^2) per call -- SparseVI asks for 1 + opt_itrs column sums of the SAME data per step);
+        (csrc/moments.hip; O(S D^2) per call -- SparseVI asks for 1 + opt_itrs column sums of the SAME data per step); family
+        "gaussian": from the FIRST moment alone, sum_n vecs[n, s] = (sum_n x_n) . g_s + N bias_s (csrc/gauss.hip; O(S D) per call);
         "auto" (default): moments, after checking them ONCE per data set against the projection kernel (relative
         disagreement <= 1e-9 of the largest column sum; otherwise that data set stays on the projection kernel).
 
@@ -99,6 +110,15 @@ class DeviceProjector(Projector):
         self._cache_val, self._cache_ref = None, None
         self._work = None
         self.loglikelihood, self.grad_loglikelihood = loglikelihood, grad_loglikelihood
+        self._gauss = self._fam == self.FAMILIES["gaussian"]
+        self._siginv, self._gop, self._gwork, self._gtbar = None, None, None, None
+        if Siginv is not None:
+            if not self._gauss:
+                raise ValueError("Siginv belongs to the family 'gaussian'")
+            Sg = np.ascontiguousarray(Siginv, dtype=np.float64)
+            if Sg.ndim != 2 or Sg.shape[0] != Sg.shape[1] or not np.allclose(Sg, Sg.T, rtol=1e-12, atol=0.0):
+                raise ValueError("Siginv must be a symmetric D x D matrix")
+            self._siginv = torch.from_numpy(Sg).to(self.device)
         self.update(np.array([]), np.array([]))
 
     # -- plumbing -----------------------------------------------------------
@@ -180,7 +200,7 @@ class DeviceProjector(Projector):
             theta moves with the weights, and the closed form (yy - 2 theta.X'y + theta'X'X theta) cancels as the
             residuals shrink; a disagreement > 1e-9 of the largest column sum retires it for this data set."""
         torch = self._torch
-        if self.colsum_mode == "mfma" or self._fam != self.FAMILIES["linreg"] or Z.shape[1] > 1024:
+        if self.colsum_mode == "mfma" or not (self._fam == self.FAMILIES["linreg"] or self._gauss) or Z.shape[1] > 1024:
             return None
         if self._world > 1 and not persistent:
             return None
@@ -207,8 +227,18 @@ class DeviceProjector(Projector):
             self._mom = None
             return None
         C = Z.shape[1]
-        M = torch.zeros((C, C), dtype=torch.float64, device=self.device)
-        if Z.shape[0]:
+        if self._gauss:
+            # the first moment is all the closed form needs: [sum_n x_n | N]
+            M = torch.zeros(C + 1, dtype=torch.float64, device=self.device)
+            if Z.shape[0]:
+                need = int(self._lib.bcx_gaussian_first_moment_scratch_bytes(int(Z.shape[0]), int(C)))
+                work = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
+                self._check(self._lib.bcx_gaussian_first_moment(self._stream(), Z.data_ptr(), Z.shape[0], Z.stride(0), C, M.data_ptr(),
+                                                                work.data_ptr(), work.numel() * 8))
+            M[C] = float(Z.shape[0])
+        else:
+            M = torch.zeros((C, C), dtype=torch.float64, device=self.device)
+        if Z.shape[0] and not self._gauss:
             need = int(self._lib.bcx_project_moments_scratch_bytes(int(Z.shape[0]), int(C)))
             work = torch.empty((need + 7) // 8, dtype=torch.float64, device=self.device)
             self._check(self._lib.bcx_project_moments(self._stream(), Z.data_ptr(), Z.shape[0], Z.stride(0), C, M.data_ptr(), C,
@@ -218,6 +248,7 @@ class DeviceProjector(Projector):
         torch.cuda.synchronize(self.device)
         t1 = time.perf_counter()
         self._mom, self._mom_ok = M, True
+        self._mom_rows = n_rows
         self.moments_info = {"rows": int(n_rows), "columns": int(C), "setup_ms": (t1 - t0) * 1e3, "checked": False}
         if self.colsum_mode == "auto":
             self._moments_check(Z, "checks")
@@ -240,6 +271,14 @@ class DeviceProjector(Projector):
         """``tbar`` (optional device vector, D doubles): the point the quadratic is expanded around -- the mean of the
         draws when their producer already has it (csrc/svi.hip); otherwise the library forms it."""
         torch = self._torch
+        if self._gauss:
+            S, D = self.theta.shape[0], Z.shape[1]
+            if self.theta.shape[1] != D:
+                raise ValueError("sampler returned %d-dimensional parameters for %d coordinates" % (self.theta.shape[1], D))
+            col = torch.empty(S, dtype=torch.float64, device=self.device) if out is None else out
+            self._check(self._lib.bcx_gaussian_colsum_moments(self._stream(), self._mom.data_ptr(), float(self._mom_rows), D,
+                                                              self.theta.data_ptr(), S, self.theta.stride(0), col.data_ptr()))
+            return col.cpu().numpy() if out is None else None
         S, D = self.theta.shape[0], Z.shape[1] - 1
         if self.theta.shape[1] != D:
             raise ValueError("sampler returned %d-dimensional parameters for %d features" % (self.theta.shape[1], D))
@@ -255,7 +294,7 @@ class DeviceProjector(Projector):
 
     def _dims(self, Z):
         cols = Z.shape[1]
-        if self._fam == 0:
+        if self._fam == 0 or self._gauss:
             return cols, -1
         return cols - 1, cols - 1
 
@@ -293,14 +332,48 @@ class DeviceProjector(Projector):
             buf = torch.zeros((t.shape[0], t.shape[1] + (t.shape[1] % 2)), dtype=torch.float64, device=self.device)
             buf[:, :t.shape[1]] = t
             t = buf[:, :t.shape[1]]
-        self.theta = t
+        self._draws = t
+        if self._gauss:
+            self._gauss_refresh()
+        else:
+            self.theta = t
+
+    def _gauss_refresh(self):
+        """Family "gaussian": the projection kernel's operand [Siginv (theta_s - tbar) | bias_s] (S x (D + 1), csrc/gauss.hip) from the
+        installed draws -- again after every in-place rewrite of them (``enqueue_step_plan``).  ``self.theta`` is its first D columns
+        (the bias sits behind them in the same rows); ``tbar`` is the producer's mean of the draws or is formed here."""
+        torch, t = self._torch, self._draws
+        S, D = t.shape
+        if self._siginv is not None and self._siginv.shape[0] != D:
+            raise ValueError("sampler returned %d-dimensional parameters, Siginv is %d x %d" % (D, self._siginv.shape[0], self._siginv.shape[0]))
+        ldg = D + 1 + ((D + 1) % 2)
+        if self._gop is None or tuple(self._gop.shape) != (S, ldg):
+            self._gop = torch.zeros((S, ldg), dtype=torch.float64, device=self.device)
+            self._gwork = torch.empty(D, dtype=torch.float64, device=self.device)
+        mean = self.theta_mean
+        self._check(self._lib.bcx_gaussian_operand(self._stream(), t.data_ptr(), S, t.stride(0), D,
+                                                   None if self._siginv is None else self._siginv.data_ptr(), D,
+                                                   None if mean is None else mean.data_ptr(), self._gop.data_ptr(), ldg, 0,
+                                                   self._gwork.data_ptr()))
+        self._gtbar = self._gwork if mean is None else mean
+        self.theta = self._gop[:, :D]
+
+    def _gauss_points(self, P):
+        """h_i = Siginv (p_i - tbar) with the mean of its coordinates behind it (k x (D + 1)): the points' side of the gradients."""
+        k, D = P.shape
+        ldh = D + 1 + ((D + 1) % 2)
+        H = self._torch.empty((k, ldh), dtype=self._torch.float64, device=self.device)
+        self._check(self._lib.bcx_gaussian_operand(self._stream(), P.data_ptr(), k, P.stride(0), D,
+                                                   None if self._siginv is None else self._siginv.data_ptr(), D, self._gtbar.data_ptr(),
+                                                   H.data_ptr(), ldh, 1, None))
+        return H
 
     def project(self, pts, grad=False):
         if grad:
             if self.loglikelihood is None or self.grad_loglikelihood is None:
                 return self._project_grad_device(pts)
             # (projector.py:19-29 on the host, at the samples the device holds)
-            samples = self.theta.cpu().numpy()
+            samples = self._draws.cpu().numpy()
             pts = np.atleast_2d(np.asarray(pts, dtype=np.float64))
             lls = self.loglikelihood(pts, samples)
             lls -= lls.mean(axis=1)[:, np.newaxis]
@@ -340,7 +413,12 @@ class DeviceProjector(Projector):
             common = self._common(P)
             self._launch(self._lib.bcx_project_write_points, common + [lls.data_ptr(), S, 1], P)
             work = self._psvi_scratch(k, S)
-            self._check(self._lib.bcx_project_grad_points(*(common + [glls.data_ptr(), work.data_ptr()])))
+            if self._gauss:
+                H = self._gauss_points(P)
+                self._check(self._lib.bcx_project_grad_points_gaussian(self._stream(), self.theta.data_ptr(), S, self.theta.stride(0), dz,
+                                                                       H.data_ptr(), k, H.stride(0), glls.data_ptr(), work.data_ptr()))
+            else:
+                self._check(self._lib.bcx_project_grad_points(*(common + [glls.data_ptr(), work.data_ptr()])))
         return lls, glls
 
     def psvi_gradient(self, pts, core, w, scaling=1.0, persistent=True):
@@ -372,8 +450,14 @@ class DeviceProjector(Projector):
         self._launch(self._lib.bcx_project_write_points, common + [cv.data_ptr(), S, 1], C)
         wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.device)
         work = self._psvi_scratch(k, S)
-        self._check(self._lib.bcx_psvi_gradient(*(common + [col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(), float(scaling),
-                                                            out.data_ptr(), work.data_ptr()])))
+        if self._gauss:
+            H = self._gauss_points(C)
+            self._check(self._lib.bcx_psvi_gradient_gaussian(self._stream(), self.theta.data_ptr(), S, self.theta.stride(0), dz, H.data_ptr(),
+                                                             k, H.stride(0), col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(),
+                                                             float(scaling), out.data_ptr(), work.data_ptr()))
+        else:
+            self._check(self._lib.bcx_psvi_gradient(*(common + [col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(), float(scaling),
+                                                                out.data_ptr(), work.data_ptr()])))
         h = out.cpu().numpy()
         return h[S:S + k].copy(), h[S + k:].reshape(k, dz).copy()
 
@@ -382,7 +466,11 @@ class DeviceProjector(Projector):
         subtraction of projector.py:21 -- for a consumer that centres while it reads: ``HilbertCoreset`` hands them to
         the solver's constructor pass with ``center_rows=True`` (csrc/ingest.hip: the row is in registers between the
         norm and the stores), so the N x S matrix is written once and read once and the separate centring pass
-        (another read + write of N x S) disappears.  ``project()`` is this followed by that pass."""
+        (another read + write of N x S) disappears.  ``project()`` is this followed by that pass.
+
+        Family "gaussian": the values leave out every term that is constant along a row (the normalising constant,
+        ``-x' Siginv x / 2`` and ``x . Siginv tbar``): the one consumer centres the rows while it ingests them, and values of
+        the size of the row's spread centre more accurately than values with a large common offset."""
         torch = self._torch
         Z = self._dev(pts)
         N, S = Z.shape[0], self.theta.shape[0]
@@ -465,7 +553,7 @@ class DeviceProjector(Projector):
         points into buf[S:], the latter as RAW log-likelihoods (uncentred: ``bcx_sparsevi_adam_step`` takes the row means),
         from argument lists built once.  The decisions of ``_moments_for`` are taken at every repetition as before."""
         self.use_draws(draws, mean=mean)
-        if self.theta.data_ptr() != draws.data_ptr():
+        if self._draws.data_ptr() != draws.data_ptr():
             # (use_draws copies rows that do not start on 16-byte boundaries: the copy would go stale at the next repetition)
             raise ValueError("enqueue_step_plan: the draws must be usable in place (device tensor, fp64, unit column stride, "
                              "even row stride, 16-byte aligned)")
@@ -478,6 +566,16 @@ class DeviceProjector(Projector):
         col = buf[:S]
         core_args = self._common(C) + [buf[S:].data_ptr(), S, 0]
         state = {"mom": None, "both": None}
+
+        def run_gauss():
+            self._gauss_refresh()              # (the draws were rewritten in place: the operand follows them)
+            if self._moments_for(pts, Z, persistent) is not None:
+                self._colsum_from_moments(Z, out=col)
+            else:
+                self._colsum_projected(Z, out=col)
+            self._check(lib.bcx_project_write_points(*core_args))
+        if self._gauss:
+            return run_gauss, buf, k
 
         def run():
             if self._moments_for(pts, Z, persistent) is not None:

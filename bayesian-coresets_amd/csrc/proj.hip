@@ -1,9 +1,10 @@
 // proj.hip -- device-native log-likelihood projection:
 //   vecs[n][s] = loglik(z_n, theta_s) - mean_s' loglik(z_n, theta_s')        projector.py:19-21
-// for the three example likelihoods of the reference
+// for the four example likelihoods of the reference
 //   logistic regression   examples/common/model_lr.py:25-32
 //   Poisson (softplus)    examples/common/model_poiss.py:25-38
 //   Gaussian linear regr. examples/common/model_linreg.py:4-10
+//   Gaussian mean         examples/common/model_gaussian.py:4-10   (FAM_GAUSSIAN: see loglik_col)
 // as one fused kernel: Z . Theta^T on the fp64 matrix cores (v_mfma_f64_16x16x4_f64; operands staged through LDS by
 // LDS-DMA, 128 x 64 or 128 x 128 workgroup tiles) with the likelihood as the epilogue, and three
 // consumers that never need the N x S matrix twice:
@@ -23,14 +24,15 @@
 #include "proj_math.h"
 #include "moments_quad.h"
 
-enum { FAM_LOGISTIC = 0, FAM_POISSON = 1, FAM_LINREG = 2 };
+enum { FAM_LOGISTIC = 0, FAM_POISSON = 1, FAM_LINREG = 2, FAM_GAUSSIAN = 3 };
 enum { PMODE_WRITE = 0, PMODE_COLSUM = 1, PMODE_SELECT = 2 };
 
 typedef double pv4d __attribute__((ext_vector_type(4)));
 
 struct ProjArgs {
   const double* Z;      // N x ldz: features in columns [0, D), response (if any) in column ycol
-  const double* theta;  // S x ldt
+  const double* theta;  // S x ldt (FAM_GAUSSIAN: the operand of csrc/gauss.hip -- Siginv (theta_s - tbar) in columns [0, D), the
+                        // column's bias in column D)
   int64_t N;
   int64_t ldz;
   int ldt, D, S, ycol;
@@ -87,6 +89,23 @@ template <int FAM> __device__ __forceinline__ double loglik(double m, double y, 
     // MFMAs run on instead of seven.
     return fma(-((m - y) * m), param, c0);
   }
+}
+
+// The Gaussian-mean family (model_gaussian.py:4-10).  Everything of log p(x_n | theta_s) that depends on the point alone
+// cancels in the row centring, and what is left is LINEAR in the product: with tbar the mean of the draws,
+//   g_s = Siginv (theta_s - tbar),   bias_s = -(tbar + (theta_s - tbar) / 2) . g_s
+//   value[n][s] = x_n . g_s + bias_s  =  (x_n - tbar) . g_s - (theta_s - tbar)' Siginv (theta_s - tbar) / 2
+// (the expansion around the mean draw: the terms of size theta' Siginv theta that the literal form subtracts from each other
+// never appear).  Rows of Z are the points (no response column); the kernel's Theta operand holds g_s with bias_s behind it in
+// column D (csrc/gauss.hip forms both), which the MFMA loop never reads (pieces beyond D are zero-filled), so the epilogue is
+// one addition of a per-column value.
+template <int FAM> __device__ __forceinline__ double pj_bias(const ProjArgs& p, int col) {
+  if constexpr (FAM == FAM_GAUSSIAN) return p.theta[(int64_t)(col < p.S ? col : p.S - 1) * p.ldt + p.D];
+  else return 0.0;
+}
+template <int FAM> __device__ __forceinline__ double loglik_col(double m, double y, double param, double c0, double bias, pj_tab_t tab) {
+  if constexpr (FAM == FAM_GAUSSIAN) return m + bias;
+  else return loglik<FAM>(m, y, param, c0, tab);
 }
 
 // loglik - shift.  For the column sums of the linear-regression family the shift is the likelihood at a zero linear
@@ -587,10 +606,11 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
 #pragma unroll
         for (int tc = 0; tc < NCT; ++tc) {
           const int col = cg * COLS + 16 * tc + li;
+          const double cbias = pj_bias<FAM>(p, col);
 #pragma unroll
           for (int e = 0; e < 8; ++e) {
             const int64_t row = r0 + 16 * (e >> 2) + lk + 4 * (e & 3);
-            if (col < S && row < p.N) p.out[row * p.ldo + col] = loglik<FAM>(acc[e >> 2][tc][e & 3], yv[e], parg, cp[e], tab);
+            if (col < S && row < p.N) p.out[row * p.ldo + col] = loglik_col<FAM>(acc[e >> 2][tc][e & 3], yv[e], parg, cp[e], cbias, tab);
           }
         }
       } else if constexpr (MODE == PMODE_WRITE) {
@@ -627,13 +647,14 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const bool cvalid = cg * COLS + 16 * tc + lk + 4 * r < S;
+              const double cbias = pj_bias<FAM>(p, cg * COLS + 16 * tc + lk + 4 * r);
 #pragma unroll
               for (int tr = 0; tr < 2; ++tr) {
-                const double v = loglik<FAM>(acc[tr][tc][r], y2[tr], parg, c2[tr], tab);
+                const double v = loglik_col<FAM>(acc[tr][tc][r], y2[tr], parg, c2[tr], cbias, tab);
                 if (cvalid && rok[tr]) orow[tr][16 * tc + 4 * r] = v;
               }
               // (transcendental epilogues: two values per scheduling region, as in the column sums of this tile)
-              __builtin_amdgcn_sched_barrier(0);
+              if (FAM != FAM_GAUSSIAN) __builtin_amdgcn_sched_barrier(0);
             }
           }
         } else {
@@ -713,7 +734,8 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
             else if (MODE == PMODE_COLSUM) pq[tr] = 0.0;            // (linear regression: closed form of value - shift, loglik_shifted)
             else {
               const double m0 = acc[tr][0][0];
-              const double l0 = (FAM == FAM_LINREG) ? (yq[tr] - m0) * m0 : loglik<FAM>(m0, yq[tr], parg, cq[tr], tab);
+              const double l0 = (FAM == FAM_LINREG) ? (yq[tr] - m0) * m0
+                                                    : loglik_col<FAM>(m0, yq[tr], parg, cq[tr], pj_bias<FAM>(p, cg * COLS), tab);
               pq[tr] = __shfl(l0, li, BCX_WAVE);
             }
           }
@@ -740,6 +762,7 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
               const int col = cg * COLS + 16 * tc + lk + 4 * r;
               const bool cvalid = col < S;
               const double rsd = (MODE == PMODE_SELECT && cvalid) ? p.resid[col] : 0.0;
+              const double cbias = pj_bias<FAM>(p, col);
               double csum = 0.0, cprod = 1.0;
 #pragma unroll
               for (int tr = 0; tr < 2; ++tr) {
@@ -751,7 +774,8 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
                   csum += ok ? lin : 0.0;
                   cprod *= ok ? f : 1.0;
                 } else {
-                  const double v = ok ? loglik_shifted<FAM, MODE>(acc[tr][tc][r], yq[tr], parg, cq[tr], pq[tr], tab) : 0.0;
+                  const double v = !ok ? 0.0 : FAM == FAM_GAUSSIAN ? (acc[tr][tc][r] + cbias) - pq[tr]
+                                                                   : loglik_shifted<FAM, MODE>(acc[tr][tc][r], yq[tr], parg, cq[tr], pq[tr], tab);
                   if (MODE == PMODE_COLSUM) csum += v;
                   else { rs[tr] += v; rq[tr] += v * v; rd[tr] += v * rsd; }
                 }
@@ -762,7 +786,7 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
               // per scheduling region -- given more, the compiler interleaves many evaluations and runs out of registers.
               // (SELECT on the 64-column tile used to be fenced the same way; with the table forms it is not, and went
               // from 39.9 to 46.1 TFLOP/s for the logistic family.)
-              if (NCT > 4 && FAM != FAM_LINREG) __builtin_amdgcn_sched_barrier(0);
+              if (NCT > 4 && FAM != FAM_LINREG && FAM != FAM_GAUSSIAN) __builtin_amdgcn_sched_barrier(0);
             }
           }
           if (MODE == PMODE_COLSUM) {
@@ -947,7 +971,7 @@ __global__ __launch_bounds__(1024) void proj_small_kernel(ProjArgs p, int center
 #pragma unroll
     for (int q = 0; q < 4; ++q) m[q] = wave_allsum(m[q]);
     const double mine = lane == 0 ? m[0] : lane == 1 ? m[1] : lane == 2 ? m[2] : m[3];
-    if (lane < 4 && s0 + lane < s_end) svals[s0 + lane - s_begin] = loglik<FAM>(mine, yv, parg, c0, tab);
+    if (lane < 4 && s0 + lane < s_end) svals[s0 + lane - s_begin] = loglik_col<FAM>(mine, yv, parg, c0, pj_bias<FAM>(p, s0 + lane), tab);
   }
   __syncthreads();
   const int mine_n = s_end - s_begin;
@@ -1047,7 +1071,7 @@ static __device__ __forceinline__ void proj_mid_body(const ProjArgs& p, const in
         c0 = fma(-(y * y), parg, clin);
         yv = 2.0 * y;
       }
-      p.out[row * p.ldo + col] = loglik<FAM>(acc[r], yv, parg, c0, tab);
+      p.out[row * p.ldo + col] = loglik_col<FAM>(acc[r], yv, parg, c0, pj_bias<FAM>(p, col), tab);
     }
   }
 }
@@ -1295,6 +1319,8 @@ static int proj_nct(int mode, int family, int S, bool aligned, int D) {
   // of per-column global loads (no change in the spills; Poisson + 1 %, linreg - 0.5 %), and recomputing the request pointers
   // at every stage instead of carrying them (frees 12 VGPRs and the parked ones of the other 128-column instantiations, but
   // costs 2-4 % in every instantiation).  Neither is in.)
+  // (the Gaussian-mean family's SELECT on the 128-column tile spills 68 VGPRs -- the per-column bias loads on top of the
+  // linear-regression instantiation's 254 -- and stays on the 64-column tile: 195 VGPRs)
   if (mode == PMODE_SELECT && family == FAM_LINREG && aligned && sel8) return (S + 127) / 128 * 128 == (S + 63) / 64 * 64 ? 8 : 4;
   // WRITE on the 128-column tile (round 4, transposed product: two data rows per lane; 16-byte aligned rows only): on one
   // box, N = 2M, S = 256, D = 300 / 301: linreg 56.3 against 51.5 TFLOP/s, logistic 51.6 / 48.6, Poisson 48.3 / 43.9.  Short
@@ -1357,8 +1383,10 @@ template <int MODE> static int launch_family(int family, dim3 grid, size_t extra
     if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8, true>(true, grid, shmem, st, p);
     if (nct == 8 && family == FAM_LOGISTIC) return launch_one<FAM_LOGISTIC, MODE, 8, true>(true, grid, shmem, st, p);
     if (nct == 8 && family == FAM_POISSON) return launch_one<FAM_POISSON, MODE, 8, true>(true, grid, shmem, st, p);
+    if (nct == 8 && family == FAM_GAUSSIAN) return launch_one<FAM_GAUSSIAN, MODE, 8, true>(true, grid, shmem, st, p);
   }
   if constexpr (MODE == PMODE_COLSUM) {
+    if (nct == 8 && family == FAM_GAUSSIAN) return launch_one<FAM_GAUSSIAN, MODE, 8>(aligned, grid, shmem, st, p);
     if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8>(aligned, grid, shmem, st, p);
     if (nct == 8 && family == FAM_LOGISTIC) return launch_one<FAM_LOGISTIC, MODE, 8, true>(true, grid, shmem, st, p);
     if (nct == 8 && family == FAM_POISSON) return launch_one<FAM_POISSON, MODE, 8, true>(true, grid, shmem, st, p);
@@ -1367,6 +1395,7 @@ template <int MODE> static int launch_family(int family, dim3 grid, size_t extra
     case FAM_LOGISTIC: return launch_one<FAM_LOGISTIC, MODE, 4>(aligned, grid, shmem, st, p);
     case FAM_POISSON: return launch_one<FAM_POISSON, MODE, 4>(aligned, grid, shmem, st, p);
     case FAM_LINREG: return launch_one<FAM_LINREG, MODE, 4>(aligned, grid, shmem, st, p);
+    case FAM_GAUSSIAN: return launch_one<FAM_GAUSSIAN, MODE, 4>(aligned, grid, shmem, st, p);
     default: g_proj_err = "unknown likelihood family"; return BCX_ERR_ARG;
   }
 }
@@ -1378,9 +1407,15 @@ static int fill(ProjArgs& p, int family, const void* Z, int64_t N, int64_t ldz, 
     g_proj_err = "bcx_project: bad arguments";
     return BCX_ERR_ARG;
   }
-  if (family != FAM_LOGISTIC && (ycol < 0 || ycol >= ldz)) { g_proj_err = "bcx_project: response column required"; return BCX_ERR_ARG; }
+  if (family < FAM_LOGISTIC || family > FAM_GAUSSIAN) { g_proj_err = "bcx_project: unknown likelihood family"; return BCX_ERR_ARG; }
+  const bool has_y = family == FAM_POISSON || family == FAM_LINREG;
+  if (has_y && (ycol < 0 || ycol >= ldz)) { g_proj_err = "bcx_project: response column required"; return BCX_ERR_ARG; }
+  if (family == FAM_GAUSSIAN && ldt < D + 1) {
+    g_proj_err = "bcx_project: family 3 takes the S x (D + 1) operand of bcx_gaussian_operand (ldt >= D + 1)";
+    return BCX_ERR_ARG;
+  }
   p.Z = (const double*)Z; p.theta = (const double*)theta; p.N = N; p.ldz = ldz; p.ldt = ldt; p.D = D; p.S = S;
-  p.ycol = family == FAM_LOGISTIC ? -1 : ycol; p.param = param;
+  p.ycol = has_y ? ycol : -1; p.param = param;
   p.out = nullptr; p.ldo = 0; p.rowsum = nullptr; p.colpart = nullptr; p.resid = nullptr; p.resid_sum = 0.0;
   p.best_val = nullptr; p.best_idx = nullptr; p.team = 0; p.part = nullptr; p.tab = nullptr;
   return BCX_OK;
@@ -1412,7 +1447,8 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
       if (al) hipLaunchKernelGGL((proj_small_kernel<F, true>), sgrid, dim3(1024), lds, st, p, cen);                     \
       else hipLaunchKernelGGL((proj_small_kernel<F, false>), sgrid, dim3(1024), lds, st, p, cen);                      \
     } while (0)
-    if (family == FAM_LOGISTIC) PJ_SMALL(FAM_LOGISTIC); else if (family == FAM_POISSON) PJ_SMALL(FAM_POISSON); else PJ_SMALL(FAM_LINREG);
+    if (family == FAM_LOGISTIC) PJ_SMALL(FAM_LOGISTIC); else if (family == FAM_POISSON) PJ_SMALL(FAM_POISSON);
+    else if (family == FAM_GAUSSIAN) PJ_SMALL(FAM_GAUSSIAN); else PJ_SMALL(FAM_LINREG);
 #undef PJ_SMALL
     PROJ_HIP(hipGetLastError());
     return BCX_OK;
@@ -1430,7 +1466,8 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
       if (al) hipLaunchKernelGGL((proj_mid_kernel<F, true>), mgrid, dim3(256), tabd * sizeof(double), st, p);           \
       else hipLaunchKernelGGL((proj_mid_kernel<F, false>), mgrid, dim3(256), tabd * sizeof(double), st, p);            \
     } while (0)
-    if (family == FAM_LOGISTIC) PJ_MID(FAM_LOGISTIC); else if (family == FAM_POISSON) PJ_MID(FAM_POISSON); else PJ_MID(FAM_LINREG);
+    if (family == FAM_LOGISTIC) PJ_MID(FAM_LOGISTIC); else if (family == FAM_POISSON) PJ_MID(FAM_POISSON);
+    else if (family == FAM_GAUSSIAN) PJ_MID(FAM_GAUSSIAN); else PJ_MID(FAM_LINREG);
 #undef PJ_MID
     PROJ_HIP(hipGetLastError());
   } else {

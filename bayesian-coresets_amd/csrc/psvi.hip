@@ -19,6 +19,13 @@
 //                      kernel stages them), the family's coefficient in the epilogue, times resid[s] (or not: the gradient write)
 //   psvi_ugrad_kernel  (C o resid) . Tc on v_mfma_f64_16x16x4_f64, Tc formed as the operand is read, times -w_i / S
 //   psvi_gwrite_kernel the centred k x S x dz gradients themselves (project(P, grad=True)): memory bound
+// PS_GAUSSIAN (the Gaussian-mean family, model_gaussian.py:12-15) does not have that shape: grad_x loglik = Siginv theta_s - Siginv x_i
+// is a DIFFERENCE of a term of the draw and a term of the point.  With g_s = Siginv (theta_s - tbar) (the projection's operand,
+// csrc/gauss.hip) and h_i = Siginv (p_i - tbar) it is g_s - h_i, and centred over the coordinates
+//     glls[i, s, :] = (g_s - mean_j g_s) - (h_i - mean_j h_i),
+//     ugrad[i, :]   = -(w_i / S) ( sum_s resid_s (g_s - mean_j g_s)  -  (sum_s resid_s) (h_i - mean_j h_i) ):
+// the first term does not depend on the point -- one S x D product with a vector, no k x S x D work at all.
+//   psvi_gauss_gwrite_kernel / psvi_gauss_ugrad_kernel; own entry points (they take h, not the points).
 // Every sum has one fixed order and no atomics: the results are the same bit for bit from run to run.  The coefficients use
 // the device libm (exp / log / log1p): there are k x S of them, not N x S, so the table forms of proj_math.h save nothing
 // measurable here, and the libm forms stay closer to NumPy's.
@@ -26,7 +33,7 @@
 #include "bcx_internal.h"
 #include "dev_util.h"
 
-enum { PS_LOGISTIC = 0, PS_POISSON = 1, PS_LINREG = 2 };
+enum { PS_LOGISTIC = 0, PS_POISSON = 1, PS_LINREG = 2, PS_GAUSSIAN = 3 };
 
 void bcx_project_set_error(const std::string& msg);   // proj.hip: the message bcx_project_last_error() returns
 
@@ -199,6 +206,7 @@ static int ps_arg_error(const char* who, const char* what) {
 // the checks both entries share; *dz: the length of a gradient row
 static int ps_check(const char* who, int32_t family, const void* P, int32_t k, int64_t ldp, int32_t D, int32_t ycol,
                     const void* theta, int32_t S, int64_t ldt, double param, const void* work, int* dz) {
+  if (family == PS_GAUSSIAN) return ps_arg_error(who, "family 3 (Gaussian mean) has entry points of its own: bcx_project_grad_points_gaussian / bcx_psvi_gradient_gaussian");
   if (family < PS_LOGISTIC || family > PS_LINREG) return ps_arg_error(who, "unknown likelihood family");
   if (k < 1 || k > BCX_PSVI_MAX_POINTS) return ps_arg_error(who, "k (pseudo-points) must be in 1 .. 4096");
   if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return ps_arg_error(who, "S (samples) must be in 1 .. 8192");
@@ -295,6 +303,103 @@ extern "C" int bcx_psvi_gradient(void* stream, int32_t family, const void* P_dev
   else
     hipLaunchKernelGGL(psvi_ugrad_kernel<false>, grid, dim3(256), 0, st, (const double*)A, k, S, theta, (int64_t)ldt, D, dz,
                        (const double*)tmean, w, ugrad);
+  PS_HIP(hipGetLastError());
+  return BCX_OK;
+}
+
+// ---- PS_GAUSSIAN -----------------------------------------------------------------------------------------------------------------------
+// G[i, s, j] = (g_s[j] - gmean[s]) - (H[i][j] - H[i][D]),  k x S x D row-major.  H[i][D]: the mean of row i's coordinates (csrc/gauss.hip).
+__global__ __launch_bounds__(256) void psvi_gauss_gwrite_kernel(const double* __restrict__ op, int64_t ldt, const double* __restrict__ gmean,
+                                                                const double* __restrict__ H, int64_t ldh, int S, int D,
+                                                                double* __restrict__ G, int64_t total) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += stride) {
+    const int64_t row = e / D;                                 // i S + s
+    const int j = (int)(e - row * D), s = (int)(row % S);
+    const int64_t i = row / S;
+    G[e] = (op[(int64_t)s * ldt + j] - gmean[s]) - (H[i * ldh + j] - H[i * ldh + D]);
+  }
+}
+
+// U[i, j] = -(w_i / S) (v_j - rs (H[i][j] - H[i][D])),  v_j = sum_s resid_s (g_s[j] - gmean[s]),  rs = sum_s resid_s.
+// A workgroup takes 64 coordinates: thread (c = tid % 64, q = tid / 64) sums the samples q, q + 4, ...; the four classes are added 0..3.
+__global__ __launch_bounds__(256) void psvi_gauss_ugrad_kernel(const double* __restrict__ op, int64_t ldt, const double* __restrict__ gmean,
+                                                               const double* __restrict__ resid, const double* __restrict__ H, int64_t ldh,
+                                                               const double* __restrict__ w, int k, int S, int D, double* __restrict__ U) {
+  __shared__ double seg[4][64], rseg[4];
+  const int c = threadIdx.x & 63, q = threadIdx.x >> 6, j = blockIdx.x * 64 + c;
+  double acc = 0.0, racc = 0.0;
+  for (int s = q; s < S; s += 4) {
+    const double r = resid[s];
+    racc += r;
+    if (j < D) acc = fma(r, op[(int64_t)s * ldt + j] - gmean[s], acc);
+  }
+  seg[q][c] = acc;
+  if (c == 0) rseg[q] = racc;
+  __syncthreads();
+  if (j >= D) return;
+  const double v = ((seg[0][c] + seg[1][c]) + seg[2][c]) + seg[3][c];
+  const double rs = ((rseg[0] + rseg[1]) + rseg[2]) + rseg[3];
+  for (int i = q; i < k; i += 4) {
+    const double* h = H + (int64_t)i * ldh;
+    U[(int64_t)i * D + j] = -(w[i] * (v - rs * (h[j] - h[D]))) / (double)S;
+  }
+}
+
+static int ps_gauss_check(const char* who, const void* op, int32_t S, int64_t ldt, int32_t D, const void* H, int32_t k, int64_t ldh,
+                          const void* work) {
+  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return ps_arg_error(who, "k (pseudo-points) must be in 1 .. 4096");
+  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return ps_arg_error(who, "S (samples) must be in 1 .. 8192");
+  if (D < 1 || D > BCX_PSVI_MAX_DIM) return ps_arg_error(who, "D (coordinates) must be in 1 .. 1024");
+  if (!op || !H || !work) return ps_arg_error(who, "null pointer");
+  if (ldt < D + 1 || ldh < D + 1) return ps_arg_error(who, "operands of bcx_gaussian_operand required (leading dimensions >= D + 1)");
+  return BCX_OK;
+}
+
+extern "C" int bcx_project_grad_points_gaussian(void* stream, const void* operand_dev, int32_t S, int64_t ldt, int32_t D, const void* H_dev,
+                                                int32_t k, int64_t ldh, void* glls_dev, void* work_dev) {
+  static const char* who = "bcx_project_grad_points_gaussian";
+  int rc = ps_gauss_check(who, operand_dev, S, ldt, D, H_dev, k, ldh, work_dev);
+  if (rc) return rc;
+  if (!glls_dev) return ps_arg_error(who, "null output");
+  hipStream_t st = (hipStream_t)stream;
+  const double* op = (const double*)operand_dev;
+  double* gmean = (double*)work_dev + (int64_t)k * S;       // (the place the other families keep it: same scratch size)
+  hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)nullptr, 0.0,
+                     (const double*)nullptr, (int64_t)0, (const double*)nullptr, (double*)nullptr, op, ldt, D, D, gmean);
+  PS_HIP(hipGetLastError());
+  const int64_t total = (int64_t)k * S * D;
+  const int64_t want = (total + 255) / 256;
+  const int blocks = (int)(want < 8192 ? want : 8192);
+  hipLaunchKernelGGL(psvi_gauss_gwrite_kernel, dim3(blocks), dim3(256), 0, st, op, ldt, (const double*)gmean, (const double*)H_dev, ldh,
+                     (int)S, (int)D, (double*)glls_dev, total);
+  PS_HIP(hipGetLastError());
+  return BCX_OK;
+}
+
+extern "C" int bcx_psvi_gradient_gaussian(void* stream, const void* operand_dev, int32_t S, int64_t ldt, int32_t D, const void* H_dev,
+                                          int32_t k, int64_t ldh, const void* colsum_dev, const void* corevecs_dev, int64_t ldcv,
+                                          const void* w_dev, double scaling, void* out_dev, void* work_dev) {
+  static const char* who = "bcx_psvi_gradient_gaussian";
+  int rc = ps_gauss_check(who, operand_dev, S, ldt, D, H_dev, k, ldh, work_dev);
+  if (rc) return rc;
+  if (!colsum_dev || !corevecs_dev || !w_dev || !out_dev) return ps_arg_error(who, "null pointer");
+  if (ldcv < S) return ps_arg_error(who, "corevecs leading dimension shorter than S");
+  hipStream_t st = (hipStream_t)stream;
+  const double* op = (const double*)operand_dev;
+  const double* cv = (const double*)corevecs_dev;
+  const double* w = (const double*)w_dev;
+  double* resid = (double*)out_dev;
+  double* wgrad = resid + S;
+  double* ugrad = wgrad + k;
+  double* gmean = (double*)work_dev + (int64_t)k * S;
+  hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)colsum_dev, scaling, cv, ldcv, w,
+                     resid, op, ldt, D, D, gmean);
+  PS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(psvi_wgrad_kernel, dim3(k), dim3(256), 0, st, S, cv, ldcv, (const double*)resid, wgrad);
+  PS_HIP(hipGetLastError());
+  hipLaunchKernelGGL(psvi_gauss_ugrad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, op, ldt, (const double*)gmean, (const double*)resid,
+                     (const double*)H_dev, ldh, w, (int)k, (int)S, (int)D, ugrad);
   PS_HIP(hipGetLastError());
   return BCX_OK;
 }

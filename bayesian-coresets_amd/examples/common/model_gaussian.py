@@ -17,6 +17,12 @@ def log_likelihood(x, th, Siginv, logdetSig):
     return -0.5 * x.shape[1] * np.log(2.0 * np.pi) - 0.5 * logdetSig - 0.5 * (quad_x[:, None] + quad_t[None, :] - 2.0 * xs.dot(th.T))
 
 
+def grad_x_log_likelihood(x, th, Siginv):
+    """N x S x D gradients of the log-likelihoods with respect to the points (model_gaussian.py:12-15): Siginv (theta_s - x_n)."""
+    x, th = np.atleast_2d(x), np.atleast_2d(th)
+    return th.dot(Siginv)[None, :, :] - x.dot(Siginv)[:, None, :]
+
+
 def weighted_posterior(mu0, Sig0inv, Siginv, x, w):
     """(mu, U) with Sigma = U U^T."""
     w = np.asarray(w, dtype=np.float64)

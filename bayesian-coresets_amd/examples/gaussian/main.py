@@ -9,8 +9,13 @@ black-box projectors (`SVI`: refreshed at the weighted coreset posterior; `GIGA-
 `GIGA-REAL`: from the posterior of a sqrt(N)-point subsample), their exact tangent-space counterparts (`*-EXACT`:
 common/model_gaussian.py `tangent_space_projector`), `US`, the incremental build over the size schedule and the closed-form
 evaluation -- reverse / forward KL to the true posterior, relative errors of mean and covariance -- stored with the
-arguments in results/<arg-hash>.csv.  This likelihood is not one of the device projector's families: the projection is the
-reference's NumPy callback (`bc.BlackBoxProjector`), the greedy construction runs on the device engine."""
+arguments in results/<arg-hash>.csv.
+
+`--projector callback` (default): the projection is the reference's NumPy callback (`bc.BlackBoxProjector`), the greedy
+construction runs on the device engine.  `--projector device`: the projection is the device projector's "gaussian" family
+(`bc.DeviceProjector`, csrc/proj.hip); `SVI` then draws from `bc.GaussianPosteriorSampler` and enqueues its whole ADAM loop,
+`GIGA-OPT` / `GIGA-REAL` keep their fixed NumPy samplers, and `PSVI` (the batch pseudocoreset, device projector only) builds
+every size from a fresh object, as the reference's `build` re-initialises its points."""
 import argparse
 import os
 import sys
@@ -66,6 +71,12 @@ def run(a):
             prj.update(np.ones(at.shape[0]), at)
         return prj
 
+    device = a.projector == "device"
+    if a.alg == "PSVI" and not device:
+        raise SystemExit("--alg PSVI needs --projector device (BatchPSVICoreset has no host path)")
+    if device:
+        bb = lambda sampler: bc.DeviceProjector("gaussian", sampler, a.proj_dim, Siginv=Siginv)
+        sampler_w = bc.GaussianPosteriorSampler(mu0, Sig0inv, Siginv, seed=a.trial)
     sched = eval(a.step_sched)
     build = {
         "SVI": lambda: bc.SparseVICoreset(x, bb(sampler_w), opt_itrs=a.opt_itrs, step_sched=sched),
@@ -75,6 +86,7 @@ def run(a):
         "GIGA-REAL": lambda: bc.HilbertCoreset(x, bb(fixed(muh, Uh))),
         "GIGA-REAL-EXACT": lambda: bc.HilbertCoreset(x, exact(xhat)),
         "US": lambda: bc.UniformSamplingCoreset(x),
+        "PSVI": lambda: bc.BatchPSVICoreset(x, bb(sampler_w), opt_itrs=a.opt_itrs, step_sched=sched),
     }
     alg = build[a.alg]()
     n = Ms.shape[0]
@@ -83,7 +95,11 @@ def run(a):
     for m in range(n):
         print("M = %d: coreset construction, %s %d" % (Ms[m], a.alg, a.trial))
         c0, t0 = time.process_time(), time.perf_counter()
-        alg.build(int(Ms[m] if m == 0 else Ms[m] - Ms[m - 1]))
+        if a.alg == "PSVI":
+            alg = build[a.alg]()                                   # bpsvi.py:15-22: every build starts afresh, at the full size
+            alg.build(int(Ms[m]))
+        else:
+            alg.build(int(Ms[m] if m == 0 else Ms[m] - Ms[m - 1]))
         cputs[m] = time.process_time() - c0 + (cputs[m - 1] if m else 0.0)
         walls[m] = time.perf_counter() - t0 + (walls[m - 1] if m else 0.0)
         wts, pts, idcs = alg.get()
@@ -109,7 +125,8 @@ def parser():
     rp.set_defaults(func=run)
     ap.add_argument("--data_num", type=int, default=1000)
     ap.add_argument("--data_dim", type=int, default=200)
-    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "SVI-EXACT", "GIGA-OPT", "GIGA-OPT-EXACT", "GIGA-REAL", "GIGA-REAL-EXACT", "US"])
+    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "SVI-EXACT", "GIGA-OPT", "GIGA-OPT-EXACT", "GIGA-REAL", "GIGA-REAL-EXACT", "US", "PSVI"])
+    ap.add_argument("--projector", type=str, default="callback", choices=["callback", "device"])
     ap.add_argument("--proj_dim", type=int, default=100)
     ap.add_argument("--coreset_size_max", type=int, default=200)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)
@@ -122,8 +139,16 @@ def parser():
     return ap
 
 
+def parse(argv=None):
+    ap = parser()
+    args = ap.parse_args(argv)
+    if args.alg == "PSVI" and args.projector != "device":
+        ap.error("--alg PSVI needs --projector device")
+    return args
+
+
 if __name__ == "__main__":
-    args = parser().parse_args()
+    args = parse()
     if not hasattr(args, "func"):
         parser().error("choose a sub-command: run")
     args.func(args)

@@ -440,6 +440,43 @@ int bcx_project_grad_points(void* stream, int32_t family, const void* P_dev, int
 int bcx_psvi_gradient(void* stream, int32_t family, const void* P_dev, int32_t k, int64_t ldp, int32_t D, int32_t ycol,
                       const void* theta_dev, int32_t S, int32_t ldt, double param, const void* colsum_dev, const void* corevecs_dev,
                       int64_t ldcv, const void* w_dev, double scaling, void* out_dev, void* work_dev);
+/* ---- The Gaussian-mean family (family id 3; reference: examples/common/model_gaussian.py; csrc/gauss.hip) ----
+ * Rows are the points x (N x D, no response column), Siginv the inverse of the known likelihood covariance.  With tbar the mean
+ * of the draws the centred log-likelihoods are linear in x: vecs[n, s] = x_n . g_s + bias_s - (row mean),
+ * g_s = Siginv (theta_s - tbar), bias_s = -(tbar + (theta_s - tbar) / 2) . g_s.  The projection entry points above take family 3
+ * with ycol ignored and theta_dev = the S x (D + 1) OPERAND [g_s | bias_s] (ldt >= D + 1; `param` unused); values omit what is
+ * constant along a row (it cancels in every centred result).  bcx_project_points_colsum_moments, bcx_project_grad_points and
+ * bcx_psvi_gradient refuse family 3 (BCX_ERR_ARG).
+ * bcx_gaussian_operand: out_dev (n x ldo, ldo >= D + 1) = Siginv (row - tbar) in columns [0, D) for the n rows of rows_dev, and in
+ * column D  mode 0: the bias above (rows are draws)   mode 1: the mean of the D coordinates (rows are points: the gradient entries).
+ * Siginv_dev: D x D symmetric (leading dimension ldsig) or NULL = identity.  tbar_dev NULL: the mean of the rows themselves, formed
+ * in work_dev (D doubles).  D <= 4096. */
+int bcx_gaussian_operand(void* stream, const void* rows_dev, int32_t n, int64_t ldx, int32_t D, const void* Siginv_dev, int64_t ldsig,
+                         const void* tbar_dev, void* out_dev, int64_t ldo, int32_t mode, void* work_dev);
+/* xsum_dev (D) = sum_n x_n in one fixed order; work_dev: bcx_gaussian_first_moment_scratch_bytes(N, D) bytes. */
+int64_t bcx_gaussian_first_moment_scratch_bytes(int64_t N, int32_t D);
+int bcx_gaussian_first_moment(void* stream, const void* Z_dev, int64_t N, int64_t ldz, int32_t D, void* xsum_dev, void* work_dev,
+                              int64_t work_bytes);
+/* The centred column sums of the projected data in closed form: colsum_dev[s] = xsum . g_s + n_rows bias_s, minus the mean over s. */
+int bcx_gaussian_colsum_moments(void* stream, const void* xsum_dev, double n_rows, int32_t D, const void* operand_dev, int32_t S,
+                                int64_t ldt, void* colsum_dev);
+/* S draws of the weighted posterior (model_gaussian.py:23-30): precision Sig0inv + (sum w) Siginv.  The caller forms once
+ * Siginv = L L', L^-1 Sig0inv L^-T = V diag(lam) V', W = L^-T V (W_dev, WT_dev: D x D row-major and its transpose), c0 = Sig0inv mu0.
+ * theta_dev (S x ld) = mu_w + (R scale) W', scale = (lam + sum w)^-1/2, R_dev (S x ld) normal numbers, Rbar_dev (ld) their column
+ * means; tbar_dev (D) = the mean of the draws.  w_dev / pts_dev (k x ldp) are read from device memory (k = 0: the prior).
+ * state_dev: 2 D doubles of scratch.  status_dev (int32): set to 1 when some lam + sum w is not positive (NaN weights included);
+ * never cleared by the library.  D <= 1024. */
+int bcx_gaussian_posterior_draw(void* stream, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                                const void* c0_dev, const void* Siginv_dev, const void* W_dev, const void* WT_dev, const void* lam_dev,
+                                const void* R_dev, const void* Rbar_dev, int32_t S, int32_t ld, void* theta_dev, void* tbar_dev,
+                                void* state_dev, void* status_dev);
+/* The two BatchPSVI entries for family 3 (csrc/psvi.hip): operand_dev as above, H_dev (k x ldh) = bcx_gaussian_operand(points,
+ * mode 1) at the same tbar.  glls_dev: k x S x D.  out_dev / work_dev / limits as for bcx_psvi_gradient (dz = D). */
+int bcx_project_grad_points_gaussian(void* stream, const void* operand_dev, int32_t S, int64_t ldt, int32_t D, const void* H_dev,
+                                     int32_t k, int64_t ldh, void* glls_dev, void* work_dev);
+int bcx_psvi_gradient_gaussian(void* stream, const void* operand_dev, int32_t S, int64_t ldt, int32_t D, const void* H_dev, int32_t k,
+                               int64_t ldh, const void* colsum_dev, const void* corevecs_dev, int64_t ldcv, const void* w_dev,
+                               double scaling, void* out_dev, void* work_dev);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 
