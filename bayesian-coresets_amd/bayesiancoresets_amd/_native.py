@@ -44,6 +44,7 @@ SYMBOLS = (
     "bcx_project_grad_points", "bcx_psvi_gradient", "bcx_psvi_gradient_scratch_bytes",
     "bcx_gaussian_operand", "bcx_gaussian_first_moment", "bcx_gaussian_first_moment_scratch_bytes", "bcx_gaussian_colsum_moments",
     "bcx_gaussian_posterior_draw", "bcx_project_grad_points_gaussian", "bcx_psvi_gradient_gaussian",
+    "bcx_psvi_adam_step",
 )
 
 
@@ -192,6 +193,7 @@ def load():
     sigs["bcx_gaussian_posterior_draw"] = [vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
     sigs["bcx_project_grad_points_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp]
     sigs["bcx_psvi_gradient_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp, i64, vp, dbl, vp, vp]
+    sigs["bcx_psvi_adam_step"] = [vp, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i32, dbl, dbl, dbl, vp, i64, vp, vp]
     lib.bcx_psvi_gradient_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_psvi_gradient_scratch_bytes.argtypes = [i32, i32]
     sigs["bcx_linreg_posterior_draw_factored"] = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp]

@@ -14,6 +14,10 @@ returns (wgrad, ugrad).  The host keeps the ADAM state, the sampler calls and th
 ``choice`` once per build, then per step the sampler (projector.update) and, with ``n_subsample_opt``, one ``randint``.
 A NumPy sampler therefore reproduces the reference's trajectory.
 
+With one of the package's device samplers (``enqueue_plan_moving``) and the full data set at every step, the whole loop is
+enqueued instead (``_optimize_enqueued``): weights, points and ADAM moments stay on the device, the sampler draws from them there,
+``bcx_psvi_adam_step`` takes the step, and the host reads (w, P) back once after ``opt_itrs`` steps.
+
 There is no host path: any other projector raises NotImplementedError.  The Poisson family's gradient has D entries for
 points of D + 1 columns, where the reference fails reshaping it (bpsvi.py:56): ``build`` raises ValueError before any
 draw."""
@@ -22,6 +26,7 @@ import numpy as np
 from .coreset import Coreset
 from ..util.opt import nn_opt
 from ..projector import DeviceProjector
+from .. import _native as nat
 
 
 class BatchPSVICoreset(Coreset):
@@ -65,6 +70,10 @@ class BatchPSVICoreset(Coreset):
 
     # ---- bpsvi.py:42-60 ----------------------------------------------------------------------------------------------
     def _optimize(self):
+        plan = self._enqueue_plan()
+        if plan is not None:
+            self.wts, self.pts = self._optimize_enqueued(plan)
+            return
         k, d = self.wts.shape[0], self.pts.shape[1]
         prj, n, nsub = self.ll_projector, self.data.shape[0], self.n_subsample_opt
 
@@ -85,6 +94,57 @@ class BatchPSVICoreset(Coreset):
         x0 = np.hstack((self.wts, self.pts.reshape(k * d)))
         x = nn_opt(x0, grd, nn_idcs=np.arange(k), opt_itrs=self.opt_itrs, step_sched=self.step_sched)
         self.wts, self.pts = x[:k], x[k:].reshape((k, d))
+
+    # ---- the same loop with the weights AND the points resident on the device (csrc/psvi.hip psvi_adam_kernel) ------------------
+    ENQUEUE = True      # False: always the host loop above (tests compare the two)
+
+    def _enqueue_plan(self):
+        """A moving-points draw plan when the whole ADAM loop can be enqueued: device projector on one rank, the full data set at
+        every step (a per-step sub-sample is a host ``randint`` + gather), and a sampler that can draw from weights and points that
+        live on the device and move (``enqueue_plan_moving``: the package's three device samplers)."""
+        prj = self.ll_projector
+        k = self.wts.shape[0]
+        if not (self.ENQUEUE and isinstance(prj, DeviceProjector) and prj._world == 1 and self.n_subsample_opt is None
+                and self.opt_itrs > 0 and 1 <= k <= 4096 and prj.projection_dimension <= 8192 and prj.family != "poisson"):
+            return None
+        make = getattr(prj.sampler, "enqueue_plan_moving", None)
+        return None if make is None else make(prj.projection_dimension, k, self.pts.shape[1], self.opt_itrs)
+
+    def _optimize_enqueued(self, plan, b1=0.9, b2=0.999, eps=1e-8):
+        """nn_opt (util/opt.py:4-28) with grd = bpsvi.py:47-55 and nn_idcs = arange(k), enqueued on the projector's stream: per step
+        the sampler's draw at the device-resident weights and points, the gradient left on the device
+        (``psvi_gradient_enqueue``) and ``bcx_psvi_adam_step`` on x = [w | P].  One upload before the loop (the schedule is
+        evaluated on the host up front), one read-back after it."""
+        prj = self.ll_projector
+        torch = prj._torch
+        k, d, T = self.wts.shape[0], self.pts.shape[1], self.opt_itrs
+        ldp, kq = plan.ldp, k + k % 2
+        sched = np.array([(self.step_sched(i), 1.0 - b1 ** (i + 1), 1.0 - b2 ** (i + 1)) for i in range(T)], dtype=np.float64)
+        nm = kq + k * ldp
+        state = torch.from_numpy(np.concatenate((np.asarray(self.wts, dtype=np.float64), np.zeros(kq - k + 2 * nm), sched.ravel()))).to(prj.device)
+        w, m1, m2, sched_d = state[:k], state[kq:kq + nm], state[kq + nm:kq + 2 * nm], state[kq + 2 * nm:]
+        plan.set_points(self.pts)
+        P = plan.points
+        theta, mean = plan.buffers()
+        run, out, dz = prj.psvi_gradient_enqueue(self.data, P, w, 1.0, True, theta, mean)      # bpsvi.py:47-55
+        if dz != d:
+            raise ValueError("pseudo-point gradient has %d entries for points of %d columns" % (dz, d))
+        mir = plan.mirror
+        adam = prj._lib.bcx_psvi_adam_step
+        args = [prj._stream(), k, d, out.data_ptr(), prj.projection_dimension, w.data_ptr(), P.data_ptr(), ldp, m1.data_ptr(),
+                m2.data_ptr(), sched_d.data_ptr(), 0, b1, b2, eps, None if mir is None else mir[0].data_ptr(),
+                0 if mir is None else mir[1], None if mir is None else mir[2].data_ptr(), None]
+        for i in range(T):
+            plan.draw(w, i)                                                       # bpsvi.py:26
+            run()
+            args[11] = i
+            prj._check(adam(*args))
+        res = torch.cat((w, P.reshape(-1))).cpu().numpy()
+        plan.check()                                                              # (a failed factorisation / fit at any step raises)
+        if not np.isfinite(res).all():
+            # the reference's loop ends with NaN weights / points here (np.maximum keeps a NaN, and so does the ADAM kernel): an error
+            raise nat.EngineError(nat.ERR_STATE, "BatchPSVI: the optimisation ended with weights or points that are not finite")
+        return res[:k].copy(), res[k:].reshape(k, d).copy()
 
     def error(self):
         return 0.0   # as in the reference (bpsvi.py:62-63: the KL estimate is not implemented)

@@ -19,7 +19,7 @@ A precision that is not positive (weights summing to -min(lam) or less, NaN weig
 call form, from ``check()`` after an enqueued loop.  There is no CPU fallback."""
 import numpy as np
 
-from .linreg_sampler import _DeviceNormals
+from .linreg_sampler import _DeviceNormals, _MovingPoints
 
 
 class GaussianPosteriorSampler(_DeviceNormals):
@@ -133,6 +133,13 @@ class GaussianPosteriorSampler(_DeviceNormals):
             return None                                     # (the caller's host loop draws step by step)
         return _Plan(self, n, self._points(pts), self._noise_block(steps, n))
 
+    def enqueue_plan_moving(self, n, k, d, steps):
+        """A plan for ``steps`` draws at k points that live on the device and are REWRITTEN IN PLACE between the draws
+        (``BatchPSVICoreset``'s enqueued loop; ``plan.points``: the k x d view to write them to); None when it cannot be served."""
+        if d != self.D or k < 1 or not self.supports(n, k) or steps * (n + 1) * self.ld * 8 > self.NOISE_BUDGET:
+            return None
+        return _MovingPlan(self, n, k, self._noise_block(steps, n))
+
 
 class _Plan(object):
     """The draws of ``steps`` consecutive sampler calls at the same points, from weights that live on the device; the normal
@@ -166,3 +173,11 @@ class _Plan(object):
     def check(self):
         """After the loop's read-back: was the precision positive definite at every step?  Raises ``EngineError`` otherwise."""
         self.s.status()
+
+
+class _MovingPlan(_MovingPoints, _Plan):
+    """``_Plan`` over a point buffer of its own that others rewrite (the draw kernel reads the points at every call)."""
+
+    def __init__(self, sampler, n, k, noise):
+        self._alloc_points(sampler._torch, sampler.device, k, sampler.D)
+        _Plan.__init__(self, sampler, n, self.points, noise)

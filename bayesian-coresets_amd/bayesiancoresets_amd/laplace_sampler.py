@@ -17,7 +17,7 @@ Limits: D <= 32 parameters, the points within 96 KiB of LDS (``supports``); beyo
 loop then runs) and the call form raises.  There is no CPU fallback."""
 import numpy as np
 
-from .linreg_sampler import _DeviceNormals
+from .linreg_sampler import _DeviceNormals, _MovingPoints
 
 FAMILIES = {"logistic": 0, "poisson": 1}
 
@@ -129,6 +129,13 @@ class LaplacePosteriorSampler(_DeviceNormals):
             return None
         return _LaplacePlan(self, n, self._points(pts), self._noise_block(steps, n))
 
+    def enqueue_plan_moving(self, n, k, d, steps):
+        """A plan for ``steps`` draws at k points that live on the device and are REWRITTEN IN PLACE between the draws
+        (``BatchPSVICoreset``'s enqueued loop; ``plan.points``: the k x d view to write them to); None when it cannot be served."""
+        if d != self.cols or k < 1 or not self.supports(n, k) or 2 * steps * (n + 1) * self.ld * 8 > self.NOISE_BUDGET:
+            return None
+        return _MovingLaplacePlan(self, n, k, self._noise_block(steps, n))
+
 
 class _LaplacePlan(object):
     """The draws of ``steps`` consecutive sampler calls at the same points, from weights that live on the device; every step
@@ -152,6 +159,7 @@ class _LaplacePlan(object):
         a = self._a
         if a is None or self._w_ptr != w_dev.data_ptr():
             a = self._a = s._args(self.pts_dev.shape[0], w_dev, self.pts_dev, False, self.noise, self.rbar, self.theta)
+            a[6] = max(a[6], self.pts_dev.stride(0))        # (the row stride: the points may be a view of padded rows)
             self._w_ptr = w_dev.data_ptr()
             self._r0, self._rstep = self.noise.data_ptr(), self.noise.stride(0) * 8
             self._b0, self._bstep = self.rbar.data_ptr(), self.rbar.stride(0) * 8
@@ -166,3 +174,12 @@ class _LaplacePlan(object):
         """After the loop's read-back: raises ``EngineError`` if ANY fit of the plan failed (a fit that failed leaves NaNs or
         stale draws behind; a later warm-started fit may still converge)."""
         self.s.check(worst=True)
+
+
+class _MovingLaplacePlan(_MovingPoints, _LaplacePlan):
+    """``_LaplacePlan`` over a point buffer of its own that others rewrite (the kernel stages the points at every call); every
+    step after the first still starts at the mode of the step before."""
+
+    def __init__(self, sampler, n, k, noise):
+        self._alloc_points(sampler._torch, sampler.device, k, sampler.cols)
+        _LaplacePlan.__init__(self, sampler, n, self.points, noise)

@@ -262,6 +262,42 @@ class LinregPosteriorSampler(_DeviceNormals):
             return None                                     # (the caller's host loop draws step by step)
         return _Plan(self, n, self._points(pts), self._noise_block(steps, n))
 
+    # -- BatchPSVI's device-resident loop: the points move too -------------------------------------------------------------------
+    def enqueue_plan_moving(self, n, k, d, steps):
+        """A plan for ``steps`` draws at k points of d columns that live on the device and are REWRITTEN IN PLACE between the
+        draws (``BatchPSVICoreset``'s enqueued loop); None when this sampler cannot serve it.  Always the D x D form, whatever k:
+        the rank-k form's K0, X U0, X Sig0 are host products of the points and cannot follow them."""
+        if d != self.D + 1 or self.D > self.DMAX or not (1 <= k <= self.KMAX and 1 <= n <= self.SMAX):
+            return None
+        if 3 * steps * (n + 1) * self.ld * 8 > self.NOISE_BUDGET or steps * (n + 1) > self.ROWS_MAX:
+            return None                                     # (the caller's host loop draws step by step)
+        return _MovingPlan(self, n, k, self._noise_block(steps, n))
+
+
+class _MovingPoints(object):
+    """What the moving-points plans of the three samplers share: the k x d points in a k x ldp device buffer (ldp even: rows on
+    16-byte boundaries, the layout the projection / gradient entries and ``bcx_psvi_adam_step`` take).  ``points`` is the k x d
+    view, ``mirror`` None or (XT, ldk, y): a second copy of the points that the ADAM entry keeps in step."""
+    mirror = None
+
+    def _alloc_points(self, torch, device, k, d):
+        self.ldp = d + (d % 2)
+        self._pbuf = torch.zeros((k, self.ldp), dtype=torch.float64, device=device)
+        self.points = self._pbuf[:, :d]
+
+    def set_points(self, pts):
+        """Overwrite the points (k x d ndarray or tensor) in place, the mirror included."""
+        torch = self.s._torch
+        t = pts if isinstance(pts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pts, dtype=np.float64))
+        t = t.to(self.points.device, dtype=torch.float64)
+        if tuple(t.shape) != tuple(self.points.shape):
+            raise ValueError("points are %s, the plan holds %s" % (tuple(t.shape), tuple(self.points.shape)))
+        self.points.copy_(t)
+        if self.mirror is not None:
+            XT, _, y = self.mirror
+            XT[:, :t.shape[0]].copy_(t[:, :-1].t())
+            y.copy_(t[:, -1])
+
 
 class _Plan(object):
     """The draws of ``steps`` consecutive sampler calls at the same points, from weights that live on the device.  The
@@ -346,3 +382,17 @@ class _Plan(object):
         status word, the worst of all steps since the plan started)?  Raises ``EngineError`` otherwise."""
         if self.factored:
             self.s.factor_status()
+
+
+class _MovingPlan(_MovingPoints, _Plan):
+    """``_Plan`` in its D x D form over point buffers of its own: ``XT`` (features BY points, D x ldk, the padding zero) and ``y``
+    are what every step's factorisation reads (csrc/lrpost.hip), rewritten by the ADAM entry together with the row-major points."""
+
+    def __init__(self, sampler, n, k, noise):
+        torch, D = sampler._torch, sampler.D
+        self._alloc_points(torch, sampler.device, k, D + 1)
+        ldk = (k + 31) // 32 * 32
+        blob = torch.zeros(k + k % 2 + D * ldk, dtype=torch.float64, device=sampler.device)
+        st = {"k": k, "y": blob[:k], "XT": blob[k + k % 2:], "ldk": ldk, "blob": blob, "low_rank": False}
+        self.mirror = (st["XT"].view(D, ldk), ldk, st["y"])
+        _Plan.__init__(self, sampler, n, st, noise)

@@ -427,39 +427,72 @@ class DeviceProjector(Projector):
         as ``project_colsum`` takes them: the closed form for the linear-regression family on the standing data set,
         the fused projection otherwise; ``persistent``: see ``_moments_for``); ``core``: the k pseudo-points (k x (D+1),
         ndarray or device tensor), ``w`` their weights, ``scaling`` the sub-sample's N / n."""
-        torch = self._torch
         if self._world > 1:
             raise NotImplementedError("row-sharded BatchPSVI is not provided")
-        Z = self._dev(pts)
         C = self._dev(core)
+        if C.shape[0] == 0:
+            return np.zeros(0), np.zeros((0, self._grad_dz(C)))
+        wd = self._torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.device)
+        run, out, dz = self._psvi_gradient_steps(pts, C, wd, scaling, persistent, None, False)
+        run()
+        k, S = C.shape[0], self.theta.shape[0]
+        h = out.cpu().numpy()
+        return h[S:S + k].copy(), h[S + k:].reshape(k, dz).copy()
+
+    def _psvi_gradient_steps(self, pts, C, wd, scaling, persistent, tbar, refresh):
+        """``(run, out, dz)``: ``run()`` enqueues one gradient of BatchPSVI's objective at the current samples, the device points ``C``
+        (k x d, k >= 1) and the device weights ``wd`` into ``out`` = [resid (S) | wgrad (k) | ugrad (k x dz)], nothing read back; the
+        argument lists are built once.  ``refresh``: the draws are rewritten in place between the calls (the Gaussian family's operand
+        follows them); ``tbar``: the mean of the draws where their producer has it (``_colsum_from_moments``)."""
+        torch, lib = self._torch, self._lib
+        Z = self._dev(pts)
         k, S = C.shape[0], self.theta.shape[0]
         dz = self._grad_dz(C)
-        if k == 0:
-            return np.zeros(0), np.zeros((0, dz))
         need = S * (k + 1) + S + k + k * dz
         if getattr(self, "_psvi_buf", None) is None or self._psvi_buf.numel() < need:
             self._psvi_buf = torch.empty(need, dtype=torch.float64, device=self.device)
         buf = self._psvi_buf
         col, cv = buf[:S], buf[S:S * (k + 1)]
         out = buf[S * (k + 1):need]
-        if self._moments_for(pts, Z, persistent) is not None:
-            self._colsum_from_moments(Z, out=col)
-        else:
-            self._colsum_projected(Z, out=col)
         common = self._common(C)
-        self._launch(self._lib.bcx_project_write_points, common + [cv.data_ptr(), S, 1], C)
-        wd = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.device)
+        core_args = common + [cv.data_ptr(), S, 1]
         work = self._psvi_scratch(k, S)
-        if self._gauss:
-            H = self._gauss_points(C)
-            self._check(self._lib.bcx_psvi_gradient_gaussian(self._stream(), self.theta.data_ptr(), S, self.theta.stride(0), dz, H.data_ptr(),
-                                                             k, H.stride(0), col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(),
-                                                             float(scaling), out.data_ptr(), work.data_ptr()))
-        else:
-            self._check(self._lib.bcx_psvi_gradient(*(common + [col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(), float(scaling),
-                                                                out.data_ptr(), work.data_ptr()])))
-        h = out.cpu().numpy()
-        return h[S:S + k].copy(), h[S + k:].reshape(k, dz).copy()
+        grad_args = common + [col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(), float(scaling), out.data_ptr(), work.data_ptr()]
+
+        def run():
+            if self._gauss and refresh:
+                self._gauss_refresh()          # (the draws were rewritten in place: the operand follows them)
+            if self._moments_for(pts, Z, persistent) is not None:
+                self._colsum_from_moments(Z, out=col, tbar=tbar)
+            else:
+                self._colsum_projected(Z, out=col)
+            if self._gauss:
+                self._launch(lib.bcx_project_write_points, self._common(C) + core_args[-3:], C)
+                H = self._gauss_points(C)
+                self._check(lib.bcx_psvi_gradient_gaussian(self._stream(), self.theta.data_ptr(), S, self.theta.stride(0), dz, H.data_ptr(),
+                                                           k, H.stride(0), col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(),
+                                                           float(scaling), out.data_ptr(), work.data_ptr()))
+            else:
+                self._check(lib.bcx_project_write_points(*core_args))
+                self._check(lib.bcx_psvi_gradient(*grad_args))
+        return run, out, dz
+
+    def psvi_gradient_enqueue(self, pts, core, w, scaling, persistent, draws, mean):
+        """For a loop that repeats ``psvi_gradient(pts, core, w)`` at draws, points and weights that are all rewritten IN PLACE on
+        the device between the repetitions (``BatchPSVICoreset``'s device-resident optimisation): installs ``draws`` / ``mean``
+        once, as ``enqueue_step_plan`` does, and returns ``(run, out, dz)`` -- ``run()`` enqueues one gradient into the device buffer
+        ``out`` = [resid (S) | wgrad (k) | ugrad (k x dz)], the layout ``bcx_psvi_adam_step`` reads; nothing is read back.
+        ``core`` (k x d, k >= 1) and ``w`` (k) are device tensors.  The decisions of ``_moments_for`` are taken at every repetition."""
+        if self._world > 1:
+            raise NotImplementedError("row-sharded BatchPSVI is not provided")
+        self.use_draws(draws, mean=mean)
+        if self._draws.data_ptr() != draws.data_ptr():
+            raise ValueError("psvi_gradient_enqueue: the draws must be usable in place (device tensor, fp64, unit column stride, "
+                             "even row stride, 16-byte aligned)")
+        C = self._dev(core)
+        if C.data_ptr() != core.data_ptr() or C.shape[0] < 1:
+            raise ValueError("psvi_gradient_enqueue: the points must be a non-empty fp64 tensor on the projector's device, unit column stride")
+        return self._psvi_gradient_steps(pts, C, w, scaling, persistent, mean, True)
 
     def project_uncentred(self, pts):
         """The raw log-likelihoods ``loglikelihood(pts, samples)`` (N x S device tensor) WITHOUT the row-mean

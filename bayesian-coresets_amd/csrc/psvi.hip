@@ -403,3 +403,110 @@ extern "C" int bcx_psvi_gradient_gaussian(void* stream, const void* operand_dev,
   PS_HIP(hipGetLastError());
   return BCX_OK;
 }
+
+// ---- the ADAM step of BatchPSVI's device-resident loop ---------------------------------------------------------------------------
+// One step of nn_opt (util/opt.py:15-23) on x = [w (k) | P (k x d)] with nn_idcs = arange(k) (bpsvi.py:57-60): elementwise,
+//     m1 = b1 m1 + (1 - b1) g,  m2 = b2 m2 + (1 - b2) g^2,  x -= step m1 / c1 / (eps + sqrt(m2 / c2)),  w = max(w, 0) (a NaN stays)
+// with g read where bcx_psvi_gradient left it ([resid (S) | wgrad (k) | ugrad (k x d)]) and (step, c1, c2) = sched[3 i ..].
+// A workgroup takes 32 rows x 16 columns of P; lane (r = lane % 8, c = lane / 8) of wave v takes row 8 v + r, columns 2 c, 2 c + 1:
+// eight lanes read 128 adjacent bytes of a row (one 16-byte load each from P, m1, m2; from g too where its address allows --
+// the gradient rows are d doubles apart, not ldp), and the mirror for the linreg sampler's D x D form (XT: features BY points,
+// ldk apart; y: the last column) receives, for one column, the 8 adjacent rows of a wave as 64 adjacent bytes.  The workgroups of
+// the first column block also step the 32 weights of their rows.  Every load of a thread is issued before its arithmetic; no
+// LDS, no atomics.  The moments are laid out as the state is: [k weights, padded to even | k x ldp].
+struct PsaArgs {
+  const double* g; const double* sched;
+  double* w; double* P; double* m1; double* m2; double* XT; double* y; double* trace;
+  int64_t ldp, ldk;
+  int k, d, S, step;
+  double b1, b2, eps;
+};
+
+typedef double ps2d __attribute__((ext_vector_type(2)));
+
+static __device__ __forceinline__ double psa_step(double x, double g, double& m1, double& m2, double b1, double b2, double eps,
+                                                  double stp, double c1, double c2) {
+  m1 = b1 * m1 + (1.0 - b1) * g;
+  m2 = b2 * m2 + (1.0 - b2) * (g * g);
+  return x - stp * m1 / c1 / (eps + sqrt(m2 / c2));
+}
+
+__global__ __launch_bounds__(256) void psvi_adam_kernel(PsaArgs a) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int i = blockIdx.y * 32 + wave * 8 + (lane & 7), j = blockIdx.x * 16 + 2 * (lane >> 3);
+  const int k = a.k, d = a.d;
+  if (i >= k || j >= d) return;
+  const bool two = j + 1 < d, wt = j == 0;
+  const int64_t kq = (int64_t)k + (k & 1);
+  const int64_t po = (int64_t)i * a.ldp + j, go = (int64_t)a.S + k + (int64_t)i * d + j;
+  // loads
+  const ps2d x = *(const ps2d*)(a.P + po);                       // (d odd: the second value of the last pair is the row's padding)
+  const ps2d m1v = *(const ps2d*)(a.m1 + kq + po), m2v = *(const ps2d*)(a.m2 + kq + po);
+  double g0, g1 = 0.0;
+  if (two && (((uintptr_t)(a.g + go)) & 15) == 0) {
+    const ps2d gv = *(const ps2d*)(a.g + go);
+    g0 = gv[0]; g1 = gv[1];
+  } else {
+    g0 = a.g[go];
+    if (two) g1 = a.g[go + 1];
+  }
+  double xw = 0.0, gw = 0.0, mw1 = 0.0, mw2 = 0.0;
+  if (wt) { xw = a.w[i]; gw = a.g[a.S + i]; mw1 = a.m1[i]; mw2 = a.m2[i]; }
+  const double* sc = a.sched + 3 * (int64_t)a.step;
+  const double stp = sc[0], c1 = sc[1], c2 = sc[2];
+  // arithmetic
+  double n1a = m1v[0], n2a = m2v[0], n1b = m1v[1], n2b = m2v[1];
+  const double xa = psa_step(x[0], g0, n1a, n2a, a.b1, a.b2, a.eps, stp, c1, c2);
+  double xb = x[1];
+  if (two) xb = psa_step(x[1], g1, n1b, n2b, a.b1, a.b2, a.eps, stp, c1, c2);
+  // stores
+  if (two) {
+    *(ps2d*)(a.P + po) = (ps2d){xa, xb};
+    *(ps2d*)(a.m1 + kq + po) = (ps2d){n1a, n1b};
+    *(ps2d*)(a.m2 + kq + po) = (ps2d){n2a, n2b};
+  } else {
+    a.P[po] = xa; a.m1[kq + po] = n1a; a.m2[kq + po] = n2a;
+  }
+  if (a.XT) {                                                    // columns 0 .. d - 2 are the features, d - 1 the response
+    if (j < d - 1) a.XT[(int64_t)j * a.ldk + i] = xa; else a.y[i] = xa;
+    if (two) { if (j + 1 < d - 1) a.XT[(int64_t)(j + 1) * a.ldk + i] = xb; else a.y[i] = xb; }
+  }
+  double* tr = a.trace ? a.trace + (int64_t)a.step * ((int64_t)k * (1 + d)) : nullptr;
+  if (tr) {
+    tr[(int64_t)k + (int64_t)i * d + j] = xa;
+    if (two) tr[(int64_t)k + (int64_t)i * d + j + 1] = xb;
+  }
+  if (wt) {
+    const double xn = bcx_clamp0(psa_step(xw, gw, mw1, mw2, a.b1, a.b2, a.eps, stp, c1, c2));
+    a.w[i] = xn; a.m1[i] = mw1; a.m2[i] = mw2;
+    if (tr) tr[i] = xn;
+  }
+}
+
+extern "C" int bcx_psvi_adam_step(void* stream, int32_t k, int32_t d, const void* grad_dev, int32_t S, void* w_dev, void* P_dev,
+                                  int64_t ldp, void* mom1_dev, void* mom2_dev, const void* sched_dev, int32_t step, double b1,
+                                  double b2, double eps, void* XT_dev, int64_t ldk, void* y_dev, void* trace_dev) {
+  static const char* who = "bcx_psvi_adam_step";
+  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return ps_arg_error(who, "k (pseudo-points) must be in 1 .. 4096");
+  if (d < 1 || d > BCX_PSVI_ADAM_MAX_COLS) return ps_arg_error(who, "d (columns of a point) must be in 1 .. 4096");
+  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return ps_arg_error(who, "S (samples) must be in 1 .. 8192");
+  if (step < 0) return ps_arg_error(who, "step must not be negative");
+  if (!grad_dev || !w_dev || !P_dev || !mom1_dev || !mom2_dev || !sched_dev) return ps_arg_error(who, "null pointer");
+  if (ldp < d || (ldp & 1)) return ps_arg_error(who, "ldp must be even and at least d (rows of the points start on 16-byte boundaries)");
+  if (((uintptr_t)P_dev | (uintptr_t)mom1_dev | (uintptr_t)mom2_dev) & 15) return ps_arg_error(who, "points and moments must be 16-byte aligned");
+  if (((uintptr_t)grad_dev | (uintptr_t)w_dev | (uintptr_t)sched_dev | (uintptr_t)trace_dev) & 7) return ps_arg_error(who, "misaligned pointer");
+  if (XT_dev) {
+    if (!y_dev) return ps_arg_error(who, "the mirror needs both XT and y");
+    if (d < 2) return ps_arg_error(who, "the mirror needs a feature and the response (d >= 2)");
+    if (ldk < ((int64_t)k + 31) / 32 * 32) return ps_arg_error(who, "ldk must be at least k rounded up to 32");
+    if (((uintptr_t)XT_dev | (uintptr_t)y_dev) & 7) return ps_arg_error(who, "misaligned pointer");
+  }
+  PsaArgs a;
+  a.g = (const double*)grad_dev; a.sched = (const double*)sched_dev;
+  a.w = (double*)w_dev; a.P = (double*)P_dev; a.m1 = (double*)mom1_dev; a.m2 = (double*)mom2_dev;
+  a.XT = (double*)XT_dev; a.y = (double*)y_dev; a.trace = (double*)trace_dev;
+  a.ldp = ldp; a.ldk = ldk; a.k = k; a.d = d; a.S = S; a.step = step; a.b1 = b1; a.b2 = b2; a.eps = eps;
+  hipLaunchKernelGGL(psvi_adam_kernel, dim3((d + 15) / 16, (k + 31) / 32), dim3(256), 0, (hipStream_t)stream, a);
+  PS_HIP(hipGetLastError());
+  return BCX_OK;
+}

@@ -477,6 +477,23 @@ int bcx_project_grad_points_gaussian(void* stream, const void* operand_dev, int3
 int bcx_psvi_gradient_gaussian(void* stream, const void* operand_dev, int32_t S, int64_t ldt, int32_t D, const void* H_dev, int32_t k,
                                int64_t ldh, const void* colsum_dev, const void* corevecs_dev, int64_t ldcv, const void* w_dev,
                                double scaling, void* out_dev, void* work_dev);
+/* One ADAM step of BatchPSVI's device-resident loop (csrc/psvi.hip psvi_adam_kernel): the reference's nn_opt
+ * (bayesiancoresets/util/opt.py:15-23) on the state x = [w (k) | P (k x d)] with nn_idcs = arange(k) (coreset/bpsvi.py:57-60: only
+ * the weights are clamped at 0, by NumPy's rule, which keeps a NaN):
+ *     m1 = b1 m1 + (1 - b1) g,  m2 = b2 m2 + (1 - b2) g^2,  x -= sched[3 i] m1 / sched[3 i + 1] / (eps + sqrt(m2 / sched[3 i + 2]))
+ * grad_dev: the out_dev of bcx_psvi_gradient[_gaussian] as it stands, [resid (S) | wgrad (k) | ugrad (k x d)] (d is the gradient's
+ * dz: a caller whose points have another column count has no step to take).  w_dev: k weights; P_dev: the points, k x ldp, ldp
+ * even and P_dev 16-byte aligned (what the projection / gradient entries read); mom1_dev / mom2_dev: laid out as the state is,
+ * [k doubles, padded to an even count | k x ldp], 16-byte aligned, zero before step 0.  sched_dev / step: as bcx_sparsevi_adam_step.
+ * XT_dev / y_dev (both or neither): a second copy of the new points in the form bcx_linreg_posterior_factor reads -- features BY
+ * points (XT: (d - 1) x ldk, ldk >= k rounded up to 32; entries beyond column k are never written, so padding that is zero stays
+ * zero) and the last column as y (k) -- written by the same launch, the same bits.  trace_dev: NULL or steps x k (1 + d) doubles
+ * receiving [w | P (k x d, dense)] after each step.  1 <= k <= BCX_PSVI_MAX_POINTS, 1 <= d <= BCX_PSVI_ADAM_MAX_COLS,
+ * 1 <= S <= BCX_PSVI_MAX_SAMPLES; BCX_ERR_ARG otherwise.  One launch, elementwise, no atomics; asynchronous on `stream`. */
+#define BCX_PSVI_ADAM_MAX_COLS 4096
+int bcx_psvi_adam_step(void* stream, int32_t k, int32_t d, const void* grad_dev, int32_t S, void* w_dev, void* P_dev, int64_t ldp,
+                       void* mom1_dev, void* mom2_dev, const void* sched_dev, int32_t step, double b1, double b2, double eps,
+                       void* XT_dev, int64_t ldk, void* y_dev, void* trace_dev);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 

@@ -9,8 +9,13 @@ Shapes:
   i    linreg   N = 5M, D = 301, S = 256, k = 300, LinregPosteriorSampler, colsum "auto"
   ii   logistic N = 1M, D = 10,  S = 512, k = 100, LaplacePosteriorSampler
   iii  the fused gradient entry alone (bcx_psvi_gradient) at k = 1024, S = 1024, D = 512: 4 k S D flops over its time
+--loop (shapes i, ii): "host" times the host loop as above (BatchPSVICoreset.ENQUEUE = False); "enqueued" the device-resident loop
+(coreset/bpsvi.py _optimize_enqueued) -- nothing synchronises inside it, so a step is the distance between two events recorded on
+the stream after consecutive draws, and the wall time of the whole loop over its steps is given next to it; "both" (default)
+alternates host, enqueued, host, enqueued in one process on the same data and reports every run ("host_runs" / "enqueued_runs";
+the line's own step_ms ... are the first host run's).
 Prints one JSON line per shape (and writes them to --out).
-    python tools/bpsvi_bench.py [--shape all|i|ii|iii] [--steps 20] [--warmup 5] [--out profiles/bpsvi_bench.jsonl]"""
+    python tools/bpsvi_bench.py [--shape all|i|ii|iii] [--loop both|host|enqueued] [--steps 20] [--warmup 5] [--out profiles/bpsvi_bench.jsonl]"""
 import argparse
 import json
 import os
@@ -47,6 +52,7 @@ def step_breakdown(torch, bc, family, Z, smp, S, k, steps, warmup, sigsq=1.0, co
     prj.psvi_gradient = timed(prj.psvi_gradient, "psvi")
     np.random.seed(1)
     alg = bc.BatchPSVICoreset(Z, prj, warmup + steps, step_sched=lambda i: 0.1 / (1.0 + i))
+    alg.ENQUEUE = False
     marks.clear(); parts.clear()                       # (the projector's first draw at construction)
     t0 = time.perf_counter()
     alg.build(k)
@@ -64,21 +70,89 @@ def step_breakdown(torch, bc, family, Z, smp, S, k, steps, warmup, sigsq=1.0, co
             "build_s": time.perf_counter() - t0, "moments": prj.moments_info, "finite": bool(np.isfinite(alg.pts).all())}
 
 
-def shape_i(torch, bc, steps, warmup):
+class _StampedPlan(object):
+    """A moving-points plan whose draws leave an event on the stream (no synchronisation)."""
+
+    def __init__(self, torch, plan):
+        self._torch, self._plan, self.events = torch, plan, []
+
+    def __getattr__(self, name):
+        return getattr(self._plan, name)
+
+    def draw(self, w_dev, i):
+        e = self._torch.cuda.Event(enable_timing=True)
+        e.record()
+        self.events.append(e)
+        return self._plan.draw(w_dev, i)
+
+
+def enqueued_steps(torch, bc, family, Z, smp, S, k, steps, warmup, sigsq=1.0, colsum="auto"):
+    prj = bc.DeviceProjector(family, smp, S, sigsq=sigsq, colsum=colsum)
+    np.random.seed(1)
+    alg = bc.BatchPSVICoreset(Z, prj, warmup + steps + 1, step_sched=lambda i: 0.1 / (1.0 + i))
+    keep, inner = {}, alg._enqueue_plan
+
+    def wrapped():
+        plan = inner()
+        if plan is None:
+            raise SystemExit("bpsvi_bench: the enqueued loop does not serve this shape")
+        keep["plan"] = _StampedPlan(torch, plan)
+        return keep["plan"]
+    alg._enqueue_plan = wrapped
+    wall = {}
+    opt = alg._optimize_enqueued
+
+    def timed(plan):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        r = opt(plan)
+        torch.cuda.synchronize()
+        wall["s"] = time.perf_counter() - t
+        return r
+    alg._optimize_enqueued = timed
+    t0 = time.perf_counter()
+    alg.build(k)
+    torch.cuda.synchronize()
+    ev = keep["plan"].events
+    a = np.array([ev[i].elapsed_time(ev[i + 1]) for i in range(warmup, warmup + steps)])
+    return {"step_ms": float(np.median(a)), "step_ms_min": float(a.min()), "step_ms_max": float(a.max()),
+            "loop_wall_ms_per_step": wall["s"] * 1e3 / (warmup + steps + 1), "build_s": time.perf_counter() - t0,
+            "moments": dict(prj.moments_info), "finite": bool(np.isfinite(alg.pts).all())}
+
+
+def both_loops(torch, bc, loop, family, Z, make, S, k, steps, warmup):
+    """host / enqueued alternating, twice each (``loop`` = "both"), or one kind twice."""
+    runs = {"host": [], "enqueued": []}
+    for _ in range(2):
+        if loop in ("both", "host"):
+            runs["host"].append(step_breakdown(torch, bc, family, Z, make(), S, k, steps, warmup))
+        if loop in ("both", "enqueued"):
+            runs["enqueued"].append(enqueued_steps(torch, bc, family, Z, make(), S, k, steps, warmup))
+    r = dict(runs["host"][0]) if runs["host"] else {}
+    r["loop"] = loop
+    if runs["host"]:
+        r["host_runs"] = runs["host"]
+        r["host_step_ms"] = [x["step_ms"] for x in runs["host"]]
+    if runs["enqueued"]:
+        r["enqueued_runs"] = runs["enqueued"]
+        r["enqueued_step_ms"] = [x["step_ms"] for x in runs["enqueued"]]
+    return r
+
+
+def shape_i(torch, bc, steps, warmup, loop="both"):
     N, D, S, k = 5_000_000, 301, 256, 300
     g = torch.Generator(device="cuda"); g.manual_seed(1)
     Z = torch.empty((N, D + 1), dtype=torch.float64, device="cuda")
     Z[:, :D] = torch.randn(N, D, dtype=torch.float64, device="cuda", generator=g)
     th = torch.randn(D, dtype=torch.float64, device="cuda", generator=g)
     Z[:, D] = Z[:, :D] @ th + torch.randn(N, dtype=torch.float64, device="cuda", generator=g)
-    smp = bc.LinregPosteriorSampler(np.zeros(D), np.eye(D), 1.0, seed=2)
-    r = step_breakdown(torch, bc, "linreg", Z, smp, S, k, steps, warmup)
+    r = both_loops(torch, bc, loop, "linreg", Z, lambda: bc.LinregPosteriorSampler(np.zeros(D), np.eye(D), 1.0, seed=2), S, k, steps, warmup)
     r.update({"shape": "i", "family": "linreg", "N": N, "D": D, "S": S, "k": k, "colsum": "auto",
               "gradient_flops": 2.0 * k * S * D + 2.0 * k * S * (D + 1)})
     return r
 
 
-def shape_ii(torch, bc, steps, warmup):
+def shape_ii(torch, bc, steps, warmup, loop="both"):
     N, D, S, k = 1_000_000, 10, 512, 100
     g = torch.Generator(device="cuda"); g.manual_seed(3)
     X = torch.randn(N, D, dtype=torch.float64, device="cuda", generator=g)
@@ -87,8 +161,7 @@ def shape_ii(torch, bc, steps, warmup):
     y = torch.where(torch.rand(N, dtype=torch.float64, device="cuda", generator=g) <= p, 1.0, -1.0)
     Z = (y[:, None] * X).contiguous()
     del X
-    smp = bc.LaplacePosteriorSampler("logistic", D, seed=4)
-    r = step_breakdown(torch, bc, "logistic", Z, smp, S, k, steps, warmup)
+    r = both_loops(torch, bc, loop, "logistic", Z, lambda: bc.LaplacePosteriorSampler("logistic", D, seed=4), S, k, steps, warmup)
     r.update({"shape": "ii", "family": "logistic", "N": N, "D": D, "S": S, "k": k, "gradient_flops": 4.0 * k * S * D})
     return r
 
@@ -127,6 +200,7 @@ def shape_iii(torch, reps=50):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shape", default="all", choices=("all", "i", "ii", "iii"))
+    ap.add_argument("--loop", default="both", choices=("both", "host", "enqueued"))
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--out", default=None)
@@ -139,9 +213,9 @@ def main():
     if a.shape in ("all", "iii"):
         lines.append(shape_iii(torch))
     if a.shape in ("all", "ii"):
-        lines.append(shape_ii(torch, bc, a.steps, a.warmup))
+        lines.append(shape_ii(torch, bc, a.steps, a.warmup, a.loop))
     if a.shape in ("all", "i"):
-        lines.append(shape_i(torch, bc, a.steps, a.warmup))
+        lines.append(shape_i(torch, bc, a.steps, a.warmup, a.loop))
     for r in lines:
         print(json.dumps(r), flush=True)
     if a.out:
