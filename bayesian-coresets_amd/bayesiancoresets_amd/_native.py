@@ -45,6 +45,7 @@ SYMBOLS = (
     "bcx_gaussian_operand", "bcx_gaussian_first_moment", "bcx_gaussian_first_moment_scratch_bytes", "bcx_gaussian_colsum_moments",
     "bcx_gaussian_posterior_draw", "bcx_project_grad_points_gaussian", "bcx_psvi_gradient_gaussian",
     "bcx_psvi_adam_step",
+    "bcx_project_colsum_rows", "bcx_project_select_rows_ws", "bcx_project_select_rows_scratch_bytes", "bcx_gather_rows",
 )
 
 
@@ -160,6 +161,9 @@ def load():
     sigs["bcx_project_colsum"] = proj_common + [vp, vp]
     sigs["bcx_project_select"] = proj_common + [vp, dbl, vp, vp]
     sigs["bcx_project_select_ws"] = proj_common + [vp, dbl, vp, vp, i64]
+    sigs["bcx_project_colsum_rows"] = proj_common + [vp, i64, vp, vp]
+    sigs["bcx_project_select_rows_ws"] = proj_common + [vp, i64, vp, dbl, vp, vp, i64]
+    sigs["bcx_gather_rows"] = [vp, vp, i64, i32, vp, i64, vp, i64]
     sigs["bcx_project_profile"] = [i32]
     sigs["bcx_project_profile_read"] = [P(dbl), P(i64), P(dbl)]
     sigs["bcx_project_moments"] = [vp, vp, i64, i64, i32, vp, i64, vp, i64]
@@ -210,6 +214,8 @@ def load():
     lib.bcx_project_colsum_moments_scratch_bytes.argtypes = [i32, i32]
     lib.bcx_project_select_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_project_select_scratch_bytes.argtypes = [i32, i64, i32]
+    lib.bcx_project_select_rows_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_project_select_rows_scratch_bytes.argtypes = [i32, i64, i32]
     lib.bcx_project_last_error.restype = ctypes.c_char_p
     lib.bcx_project_last_error.argtypes = []
     for name, args in sigs.items():

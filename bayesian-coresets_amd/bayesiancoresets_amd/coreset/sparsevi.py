@@ -11,7 +11,10 @@ N-sized work runs on the GPU:
 * with any other projector (user callbacks produce a host array) the projected vectors are handed to
   the same device engine as the Hilbert coresets: one ingest pass gives the row norms and column sums,
   one correlation scan gives the arg-max (``bcx_argmax_correlation``).
-Random subsampling (``n_subsample_select`` / ``n_subsample_opt``) follows sparsevi.py:32-35.
+Random subsampling (``n_subsample_select`` / ``n_subsample_opt``) follows sparsevi.py:32-35.  By default the drawn rows are
+gathered (``data[sub]``) and handed over as a fresh array at every step; with ``subsample="device"`` the data set is made resident
+once and the same draws are handed to the projector as ``rows=`` -- the gathered fused consumers of csrc/proj.hip, same bits --
+and the ADAM loop can be enqueued on an index table drawn up front (``_enqueue_plan_subsampled``).
 """
 import numpy as np
 
@@ -23,11 +26,24 @@ from .. import _native as nat
 
 class SparseVICoreset(Coreset):
     def __init__(self, data, ll_projector, n_subsample_select=None, n_subsample_opt=None, opt_itrs=100,
-                 step_sched=lambda i: 1.0 / (1.0 + i), *, row_offset=0, group=None, **kw):
+                 step_sched=lambda i: 1.0 / (1.0 + i), *, row_offset=0, group=None, subsample="host", **kw):
         """``row_offset`` / ``group`` (keyword-only extension): row-sharded construction, one process per
         GPU.  ``data`` is then this rank's contiguous block of rows starting at global row
         ``row_offset``, the projector must be a ``DeviceProjector`` built with the same ``group`` and
-        ``row_offset``, and every rank must seed NumPy identically (the sampler is replicated)."""
+        ``row_offset``, and every rank must seed NumPy identically (the sampler is replicated).
+
+        ``subsample`` (keyword-only): where the rows of a ``n_subsample_select`` / ``n_subsample_opt`` draw are taken from --
+        "host" (default): ``data[sub]``, a fresh array per step; "device": the data set stays resident on the projector's device
+        and every step projects the drawn rows in place (``DeviceProjector``'s ``rows=``).  Same ``np.random.randint`` calls in
+        the same order, same results bit for bit (``colsum`` "auto" / "mfma"); needs a ``DeviceProjector`` and one rank."""
+        if subsample not in ("host", "device"):
+            raise ValueError("subsample must be 'host' or 'device'")
+        if subsample == "device" and not isinstance(ll_projector, DeviceProjector):
+            raise ValueError("subsample='device' needs a DeviceProjector")
+        if subsample == "device" and (group is not None or getattr(ll_projector, "_world", 1) > 1):
+            raise ValueError("subsample='device' is provided on one rank only (row-sharded sub-sampling gathers on the host)")
+        self.subsample = subsample
+        self._data_dev = None
         self.row_offset, self.group = int(row_offset), group
         self._sharded = group is not None
         if self._sharded and not isinstance(ll_projector, DeviceProjector):
@@ -75,6 +91,13 @@ class SparseVICoreset(Coreset):
         pos = np.flatnonzero((sub >= lo) & (sub < lo + self.data.shape[0]))
         return pos, sub, self.data[sub[pos] - lo], scaling
 
+    def _resident(self):
+        """The data set on the projector's device, made resident once (``subsample="device"``): a device tensor passes
+        through, a host array is uploaded once and kept here -- also below the projector's own caching threshold."""
+        if self._data_dev is None:
+            self._data_dev = self.ll_projector._dev(self.data)
+        return self._data_dev
+
     def _engine_for(self, vecs):
         """Hand host-resident projected vectors to the device engine: norms + column sums in one pass."""
         n, s = vecs.shape
@@ -113,6 +136,13 @@ class SparseVICoreset(Coreset):
     def _residual(self, n_subsample, w):
         """(resid, sub_idcs, points, engine-or-None, corevecs) after updating the projector at (w, pts)."""
         self.ll_projector.update(w, self.pts)                                     # sparsevi.py:25
+        if self.subsample == "device" and n_subsample is not None:
+            # the same draw, projected where the rows are (no data[sub]); pts stays None: _select hands `sub` on as well
+            sub = np.random.randint(self.n_global, size=n_subsample)             # sparsevi.py:33
+            colsum, corevecs = self.ll_projector.colsum_and_core(self._resident(), self._core_points_device(), persistent=False,
+                                                                 rows=sub)
+            resid = (self.n_global / n_subsample) * colsum - w.dot(corevecs)      # sparsevi.py:47 / :72
+            return resid, (None, sub), None, None, corevecs
         pos, sub, pts, scaling = self._subsample(n_subsample)
         eng = None
         if isinstance(self.ll_projector, DeviceProjector):
@@ -133,7 +163,9 @@ class SparseVICoreset(Coreset):
     def _select(self):
         resid, (pos, sub), pts, eng, corevecs = self._residual(self.n_subsample_select, self.wts)
         S = resid.shape[0]
-        if eng is None:
+        if eng is None and pts is None:
+            best, row = self.ll_projector.project_select(self._resident(), resid, rows=sub)     # (row: the position in sub)
+        elif eng is None:
             best, row = self.ll_projector.project_select(pts, resid, row_ids=pos)
         elif eng.has_zero_row:
             # corrs = vecs.dot(resid) / ||vecs|| / S is NaN at a zero row and NumPy's argmax returns the first NaN
@@ -177,6 +209,10 @@ class SparseVICoreset(Coreset):
         if plan is not None:
             self.wts = self._optimize_enqueued(plan)
             return
+        plan = self._enqueue_plan_subsampled()
+        if plan is not None:
+            self.wts = self._optimize_enqueued(plan, n_sub=self.n_subsample_opt)
+            return
 
         def grd(w):
             resid, sub, pts, eng, corevecs = self._residual(self.n_subsample_opt, w)
@@ -197,10 +233,27 @@ class SparseVICoreset(Coreset):
         make = getattr(prj.sampler, "enqueue_plan", None)
         return None if make is None else make(prj.projection_dimension, self.pts, self.opt_itrs)
 
-    def _optimize_enqueued(self, plan, b1=0.9, b2=0.999, eps=1e-8):
+    INDEX_BUDGET = 1 << 30      # bytes of pre-drawn row indices (opt_itrs x n_subsample_opt int64) an enqueued loop may hold
+
+    def _enqueue_plan_subsampled(self):
+        """The same for ``subsample="device"`` with ``n_subsample_opt``: the conditions of ``_enqueue_plan`` with the per-step
+        sub-sample in the place of the full data set, plus the index table of the whole loop fitting INDEX_BUDGET (beyond it the
+        host loop draws and projects step by step).  ``_enqueue_plan`` itself keeps returning None with ``n_subsample_opt``."""
+        prj = self.ll_projector
+        if not (self.ENQUEUE and self.subsample == "device" and isinstance(prj, DeviceProjector) and self.n_subsample_opt is not None
+                and self.opt_itrs > 0 and 0 < self.wts.shape[0] <= 4096 and prj.projection_dimension <= 8192
+                and 8 * self.opt_itrs * self.n_subsample_opt <= self.INDEX_BUDGET):
+            return None
+        make = getattr(prj.sampler, "enqueue_plan", None)
+        return None if make is None else make(prj.projection_dimension, self.pts, self.opt_itrs)
+
+    def _optimize_enqueued(self, plan, b1=0.9, b2=0.999, eps=1e-8, n_sub=None):
         """nn_opt (util/opt.py:4-28) with grd = sparsevi.py:69-76, enqueued: per step the sampler's draw kernel at the current
         device weights, the two projections (column sums of the data, the coreset points), and one kernel for
-        resid / gradient / ADAM moments / step / clamp.  The host evaluates the schedule up front and reads the weights once."""
+        resid / gradient / ADAM moments / step / clamp.  The host evaluates the schedule up front and reads the weights once.
+        ``n_sub``: every step sums a fresh sub-sample of that many rows, scaled by N / n_sub.  The host draws the loop's indices up
+        front by the host loop's own calls -- one ``randint(n, size=n_sub)`` per step, in step order (the device samplers never touch
+        NumPy's stream) -- and uploads them once; step i projects the rows of table row i where they are."""
         prj = self.ll_projector
         torch = prj._torch
         k, S, T = self.wts.shape[0], prj.projection_dimension, self.opt_itrs
@@ -208,16 +261,22 @@ class SparseVICoreset(Coreset):
         state = torch.from_numpy(np.concatenate((np.asarray(self.wts, dtype=np.float64), np.zeros(2 * k), sched.ravel()))).to(prj.device)
         w, m1, m2, sched_d = state[:k], state[k:2 * k], state[2 * k:3 * k], state[3 * k:]
         theta, mean = plan.buffers()
-        run, buf, _ = prj.enqueue_step_plan(self.data, self._core_points_device(), True, theta, mean)    # sparsevi.py:35-41
+        scaling = 1.0
+        if n_sub is None:
+            run, buf, _ = prj.enqueue_step_plan(self.data, self._core_points_device(), True, theta, mean)    # sparsevi.py:35-41
+        else:
+            table = np.stack([np.random.randint(self.n_global, size=n_sub) for _ in range(T)])           # sparsevi.py:33, T calls
+            scaling = self.n_global / n_sub
+            run, buf, _ = prj.enqueue_step_plan(self._resident(), self._core_points_device(), False, theta, mean, rows=table)
         # (more than 16 weights: the ADAM step is two launches over slabs of weights and needs scratch, csrc/svi.hip)
         need = int(prj._lib.bcx_sparsevi_adam_scratch_bytes(k, S))
         work = torch.empty(max(need // 8, 1), dtype=torch.float64, device=prj.device)
-        adam, args = prj._lib.bcx_sparsevi_adam_step_ws, [prj._stream(), k, S, buf.data_ptr(), 1.0, buf[S:].data_ptr(), S, w.data_ptr(),
+        adam, args = prj._lib.bcx_sparsevi_adam_step_ws, [prj._stream(), k, S, buf.data_ptr(), scaling, buf[S:].data_ptr(), S, w.data_ptr(),
                                                           m1.data_ptr(), m2.data_ptr(), sched_d.data_ptr(), 0, b1, b2, eps, None, 1,
                                                           work.data_ptr(), work.numel() * 8]
         for i in range(T):
             plan.draw(w, i)                                                       # sparsevi.py:25
-            run()
+            run() if n_sub is None else run(i)
             args[11] = i
             prj._check(adam(*args))
         out = w.cpu().numpy()

@@ -180,7 +180,7 @@ class DeviceProjector(Projector):
         """Give back the device scratch the fused consumers keep between calls (select: 32 bytes per row and 64-column
         group; column sums: 2048 x S doubles; the read-back buffer) -- e.g. between experiments on data sets of different
         sizes.  The next call allocates what it needs again."""
-        self._work, self._sel_work, self._cc_buf, self._mom_work = None, None, None, None
+        self._work, self._sel_work, self._cc_buf, self._mom_work, self._gather_buf = None, None, None, None, None
 
     # -- second moments of a data set (linear-regression family): csrc/moments.hip -----------------------------------
     MOMENTS_RECHECK_EVERY = 64      # "auto": closed-form column sums are re-validated against the projection this often
@@ -421,29 +421,33 @@ class DeviceProjector(Projector):
                 self._check(self._lib.bcx_project_grad_points(*(common + [glls.data_ptr(), work.data_ptr()])))
         return lls, glls
 
-    def psvi_gradient(self, pts, core, w, scaling=1.0, persistent=True):
+    def psvi_gradient(self, pts, core, w, scaling=1.0, persistent=True, *, rows=None):
         """One gradient of BatchPSVI's objective (bpsvi.py:47-55) with ONE device->host copy: ``(wgrad, ugrad)`` as host
         arrays (k and k x dz), at the current samples.  ``pts``: the data or a sub-sample of it (its column sums are taken
         as ``project_colsum`` takes them: the closed form for the linear-regression family on the standing data set,
         the fused projection otherwise; ``persistent``: see ``_moments_for``); ``core``: the k pseudo-points (k x (D+1),
-        ndarray or device tensor), ``w`` their weights, ``scaling`` the sub-sample's N / n."""
+        ndarray or device tensor), ``w`` their weights, ``scaling`` the sub-sample's N / n.  ``rows``: as ``project_colsum`` -- the
+        sub-sample as positions into the standing ``pts``."""
         if self._world > 1:
             raise NotImplementedError("row-sharded BatchPSVI is not provided")
         C = self._dev(core)
         if C.shape[0] == 0:
             return np.zeros(0), np.zeros((0, self._grad_dz(C)))
         wd = self._torch.from_numpy(np.ascontiguousarray(w, dtype=np.float64)).to(self.device)
-        run, out, dz = self._psvi_gradient_steps(pts, C, wd, scaling, persistent, None, False)
-        run()
+        Z = self._dev(pts)
+        table = None if rows is None else self._rows_dev(rows, Z)[None, :]
+        run, out, dz = self._psvi_gradient_steps(pts, C, wd, scaling, persistent, None, False, table)
+        run(0) if table is not None else run()
         k, S = C.shape[0], self.theta.shape[0]
         h = out.cpu().numpy()
         return h[S:S + k].copy(), h[S + k:].reshape(k, dz).copy()
 
-    def _psvi_gradient_steps(self, pts, C, wd, scaling, persistent, tbar, refresh):
+    def _psvi_gradient_steps(self, pts, C, wd, scaling, persistent, tbar, refresh, table=None):
         """``(run, out, dz)``: ``run()`` enqueues one gradient of BatchPSVI's objective at the current samples, the device points ``C``
         (k x d, k >= 1) and the device weights ``wd`` into ``out`` = [resid (S) | wgrad (k) | ugrad (k x dz)], nothing read back; the
         argument lists are built once.  ``refresh``: the draws are rewritten in place between the calls (the Gaussian family's operand
-        follows them); ``tbar``: the mean of the draws where their producer has it (``_colsum_from_moments``)."""
+        follows them); ``tbar``: the mean of the draws where their producer has it (``_colsum_from_moments``).  ``table`` (T x n_sub
+        validated device indices): ``run(i)`` takes the column sums of the rows ``pts[table[i]]``, by projection."""
         torch, lib = self._torch, self._lib
         Z = self._dev(pts)
         k, S = C.shape[0], self.theta.shape[0]
@@ -459,10 +463,14 @@ class DeviceProjector(Projector):
         work = self._psvi_scratch(k, S)
         grad_args = common + [col.data_ptr(), cv.data_ptr(), S, wd.data_ptr(), float(scaling), out.data_ptr(), work.data_ptr()]
 
-        def run():
+        def run(i=None):
             if self._gauss and refresh:
                 self._gauss_refresh()          # (the draws were rewritten in place: the operand follows them)
-            if self._moments_for(pts, Z, persistent) is not None:
+            if table is not None:
+                if not 0 <= i < table.shape[0]:
+                    raise IndexError("step %d of an index table of %d rows" % (i, table.shape[0]))
+                self._colsum_rows_enqueue(Z, table.data_ptr() + 8 * table.shape[1] * i, int(table.shape[1]), col)
+            elif self._moments_for(pts, Z, persistent) is not None:
                 self._colsum_from_moments(Z, out=col, tbar=tbar)
             else:
                 self._colsum_projected(Z, out=col)
@@ -477,12 +485,13 @@ class DeviceProjector(Projector):
                 self._check(lib.bcx_psvi_gradient(*grad_args))
         return run, out, dz
 
-    def psvi_gradient_enqueue(self, pts, core, w, scaling, persistent, draws, mean):
+    def psvi_gradient_enqueue(self, pts, core, w, scaling, persistent, draws, mean, *, rows=None):
         """For a loop that repeats ``psvi_gradient(pts, core, w)`` at draws, points and weights that are all rewritten IN PLACE on
         the device between the repetitions (``BatchPSVICoreset``'s device-resident optimisation): installs ``draws`` / ``mean``
         once, as ``enqueue_step_plan`` does, and returns ``(run, out, dz)`` -- ``run()`` enqueues one gradient into the device buffer
         ``out`` = [resid (S) | wgrad (k) | ugrad (k x dz)], the layout ``bcx_psvi_adam_step`` reads; nothing is read back.
-        ``core`` (k x d, k >= 1) and ``w`` (k) are device tensors.  The decisions of ``_moments_for`` are taken at every repetition."""
+        ``core`` (k x d, k >= 1) and ``w`` (k) are device tensors.  The decisions of ``_moments_for`` are taken at every repetition.
+        ``rows`` (T x n_sub index table): repetition ``i`` is ``run(i)``, on the rows ``pts[rows[i]]``."""
         if self._world > 1:
             raise NotImplementedError("row-sharded BatchPSVI is not provided")
         self.use_draws(draws, mean=mean)
@@ -492,7 +501,8 @@ class DeviceProjector(Projector):
         C = self._dev(core)
         if C.data_ptr() != core.data_ptr() or C.shape[0] < 1:
             raise ValueError("psvi_gradient_enqueue: the points must be a non-empty fp64 tensor on the projector's device, unit column stride")
-        return self._psvi_gradient_steps(pts, C, w, scaling, persistent, mean, True)
+        table = None if rows is None else self._rows_dev(rows, self._dev(pts), ndim=2)
+        return self._psvi_gradient_steps(pts, C, w, scaling, persistent, mean, True, table)
 
     def project_uncentred(self, pts):
         """The raw log-likelihoods ``loglikelihood(pts, samples)`` (N x S device tensor) WITHOUT the row-mean
@@ -512,6 +522,80 @@ class DeviceProjector(Projector):
             self._launch(self._lib.bcx_project_write_raw, self._common(Z) + [out.data_ptr(), S], Z)
         return out
 
+    # -- indexed rows of a standing data set (``rows=``): csrc/proj.hip, the GATHER instantiations ------------------------------
+    def _rows_dev(self, rows, Z, ndim=1):
+        """The index table ``rows`` (host int array or device tensor; ``ndim`` 2: one row of it per step) as a contiguous int64
+        device tensor, after checking every index against the rows of ``Z`` -- the kernels do not.  One rank only."""
+        torch = self._torch
+        if self._world > 1:
+            raise ValueError("rows=: sub-sampled steps on indexed rows are provided on one rank only (a row-sharded projector takes "
+                             "the gathered copy, as before)")
+        n = int(Z.shape[0])
+        if isinstance(rows, torch.Tensor):
+            if rows.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+                raise ValueError("rows= must hold integers")
+            r = rows.to(self.device, dtype=torch.int64).contiguous()
+            if r.numel():
+                lo, hi = (int(v) for v in torch.stack((r.min(), r.max())).cpu())
+        else:
+            h = np.asarray(rows)
+            if h.size and not np.issubdtype(h.dtype, np.integer):
+                raise ValueError("rows= must hold integers")
+            h = np.ascontiguousarray(h, dtype=np.int64)
+            if h.size:
+                lo, hi = int(h.min()), int(h.max())
+            r = torch.from_numpy(h).to(self.device)
+        if r.dim() != ndim:
+            raise ValueError("rows= must be %d-dimensional here" % ndim)
+        if r.numel() and (lo < 0 or hi >= n):
+            raise ValueError("rows= holds an index outside [0, %d)" % n)
+        return r
+
+    ROWS_FORCE_COPY = False     # dev / tests: always the fallback below (device gather + the contiguous entry: the same bits)
+
+    def _rows_fused(self, Z):
+        """Whether the gathered kernel serves this data set: its requests carry 32-bit offsets from the base, in 16-byte units
+        for 16-byte aligned rows and in elements otherwise (include/bcx.h).  Beyond that reach the rows are copied on the device
+        (``bcx_gather_rows``, a buffer kept between calls) and the contiguous entry is taken: same bits, nothing on the host."""
+        t = self.theta
+        al = Z.data_ptr() % 16 == 0 and Z.stride(0) % 2 == 0 and t.data_ptr() % 16 == 0 and t.stride(0) % 2 == 0
+        last = max(int(Z.shape[0]) - 1, 0) * int(Z.stride(0))
+        return not self.ROWS_FORCE_COPY and (last >> 1 if al else last) <= 0xffffffff
+
+    def _gather(self, Z, rows_ptr, n_rows):
+        """Z[rows] as a device matrix with Z's leading dimension and 16-byte alignment class (the launch plan and the bits of the
+        contiguous entries depend on both), in a buffer kept between calls."""
+        torch = self._torch
+        ld, off = int(Z.stride(0)), (Z.data_ptr() % 16) // 8
+        need = n_rows * ld + 1
+        if getattr(self, "_gather_buf", None) is None or self._gather_buf.numel() < need:
+            self._gather_buf = torch.empty(need, dtype=torch.float64, device=self.device)
+        G = self._gather_buf[off:off + n_rows * ld].view(n_rows, ld)[:, :Z.shape[1]]
+        self._check(self._lib.bcx_gather_rows(self._stream(), Z.data_ptr(), ld, int(Z.shape[1]), rows_ptr, n_rows, G.data_ptr(), ld))
+        return G
+
+    def gather_rows(self, pts, rows):
+        """``pts[rows]`` as a device tensor (a fresh one), gathered on the device: ``bcx_gather_rows``."""
+        Z = self._dev(pts)
+        r = self._rows_dev(rows, Z)
+        out = self._torch.empty((r.numel(), Z.shape[1]), dtype=self._torch.float64, device=self.device)
+        if r.numel():
+            self._check(self._lib.bcx_gather_rows(self._stream(), Z.data_ptr(), Z.stride(0), int(Z.shape[1]), r.data_ptr(), r.numel(),
+                                                  out.data_ptr(), out.stride(0)))
+        return out
+
+    def _colsum_rows_enqueue(self, Z, rows_ptr, n_rows, col):
+        """Column sums of the ``n_rows`` indexed rows of ``Z`` into the device vector ``col`` (index table at ``rows_ptr``)."""
+        S = self.theta.shape[0]
+        if n_rows == 0:
+            col.zero_()
+        elif self._rows_fused(Z):
+            self._check(self._lib.bcx_project_colsum_rows(*(self._common(Z) + [rows_ptr, n_rows, col.data_ptr(),
+                                                                                 self._workspace(S).data_ptr()])))
+        else:
+            G = self._gather(Z, rows_ptr, n_rows)
+            self._check(self._lib.bcx_project_colsum(*(self._common(G) + [col.data_ptr(), self._workspace(S).data_ptr()])))
+
     # -- fused consumers (SparseVI) -------------------------------------------------
     def _workspace(self, S):
         torch = self._torch
@@ -528,18 +612,25 @@ class DeviceProjector(Projector):
             self._sel_work = self._torch.empty((need + 7) // 8, dtype=self._torch.float64, device=self.device)
         return self._sel_work
 
-    def project_colsum(self, pts, persistent=True):
-        """sum_n vecs[n, :] as a length-S ndarray, without forming vecs.  ``persistent``: see ``_moments_for``."""
+    def project_colsum(self, pts, persistent=True, *, rows=None):
+        """sum_n vecs[n, :] as a length-S ndarray, without forming vecs.  ``persistent``: see ``_moments_for``.
+        ``rows`` (host int array or device int64 tensor of positions into ``pts``): ``pts`` is the standing data set and only
+        the indexed rows are summed -- always by projection, with the bits ``project_colsum(pts[rows])`` has for a device copy
+        of the same leading dimension."""
         Z = self._dev(pts)
+        if rows is not None:
+            return self._colsum_projected(Z, rows=self._rows_dev(rows, Z))
         if self._moments_for(pts, Z, persistent) is not None:
             return self._colsum_from_moments(Z)        # (row-sharded: the moments are already the global ones)
         return self._colsum_projected(Z)
 
-    def _colsum_projected(self, Z, out=None):
+    def _colsum_projected(self, Z, out=None, rows=None):
         torch = self._torch
         S = self.theta.shape[0]
         col = torch.empty(S, dtype=torch.float64, device=self.device) if out is None else out
-        if Z.shape[0]:
+        if rows is not None:
+            self._colsum_rows_enqueue(Z, rows.data_ptr(), rows.numel(), col)
+        elif Z.shape[0]:
             self._launch(self._lib.bcx_project_colsum, self._common(Z) + [col.data_ptr(), self._workspace(S).data_ptr()], Z)
         else:
             col.zero_()
@@ -549,20 +640,22 @@ class DeviceProjector(Projector):
             torch.distributed.all_reduce(col, op=torch.distributed.ReduceOp.SUM, group=self.group)
         return col.cpu().numpy() if out is None else None
 
-    def colsum_and_core(self, pts, core, persistent=True):
+    def colsum_and_core(self, pts, core, persistent=True, *, rows=None):
         """(project_colsum(pts), project(core) as an ndarray) with ONE device->host copy: what every ADAM step of SparseVI
         reads back (sparsevi.py:35-41, 70-74).  ``core`` is the k x (D+1) array of coreset points (ndarray or device tensor),
         k may be 0.  ``persistent``: ``pts`` is the caller's standing data set, not a per-call sub-sample (``_moments_for``)."""
-        buf, k = self.colsum_and_core_enqueue(pts, core, persistent)
+        buf, k = self.colsum_and_core_enqueue(pts, core, persistent, rows=rows)
         S = self.theta.shape[0]
         h = buf.cpu().numpy()
         return h[:S], h[S:].reshape(k, S)
 
-    def colsum_and_core_enqueue(self, pts, core, persistent=True):
+    def colsum_and_core_enqueue(self, pts, core, persistent=True, *, rows=None):
         """The same two projections left ON THE DEVICE, nothing read back: (buf, k) with buf[:S] the column sums and
-        buf[S:] the k x S projected coreset points (one buffer, reused by the next call; valid in stream order)."""
+        buf[S:] the k x S projected coreset points (one buffer, reused by the next call; valid in stream order).
+        ``rows``: as ``project_colsum``."""
         torch = self._torch
         Z = self._dev(pts)
+        rdev = None if rows is None else self._rows_dev(rows, Z)
         S = self.theta.shape[0]
         C = None if core is None or core.shape[0] == 0 else self._dev(core)
         k = 0 if C is None else C.shape[0]
@@ -570,7 +663,9 @@ class DeviceProjector(Projector):
             self._cc_buf = torch.empty(S * (max(k, 7) + 1), dtype=torch.float64, device=self.device)
         buf = self._cc_buf[:S * (k + 1)]
         col = buf[:S]
-        if self._moments_for(pts, Z, persistent) is not None:
+        if rdev is not None:
+            self._colsum_projected(Z, out=col, rows=rdev)      # (a sub-sample's moments are not the data's: always projected)
+        elif self._moments_for(pts, Z, persistent) is not None:
             self._colsum_from_moments(Z, out=col, tbar=getattr(self, "theta_mean", None))
         else:
             self._colsum_projected(Z, out=col)      # (a shard without rows: zeros, and still the all-reduce its peers join)
@@ -579,12 +674,14 @@ class DeviceProjector(Projector):
             self._launch(self._lib.bcx_project_write_points, self._common(C) + [buf[S:].data_ptr(), S, 1], C)
         return buf, k
 
-    def enqueue_step_plan(self, pts, core, persistent, draws, mean):
+    def enqueue_step_plan(self, pts, core, persistent, draws, mean, *, rows=None):
         """For a loop that repeats ``colsum_and_core_enqueue(pts, core)`` at draws that are rewritten IN PLACE between the
         repetitions (``SparseVICoreset``'s device-resident weight optimisation): installs ``draws`` / ``mean`` once and returns
         ``(run, buf, k)`` -- ``run()`` enqueues the column sums of ``pts`` into buf[:S] and the k x S projected coreset
         points into buf[S:], the latter as RAW log-likelihoods (uncentred: ``bcx_sparsevi_adam_step`` takes the row means),
-        from argument lists built once.  The decisions of ``_moments_for`` are taken at every repetition as before."""
+        from argument lists built once.  The decisions of ``_moments_for`` are taken at every repetition as before.
+        ``rows`` (T x n_sub index table, host or device): repetition ``i`` is ``run(i)`` and sums the rows ``pts[rows[i]]`` -- by
+        projection, never in closed form."""
         self.use_draws(draws, mean=mean)
         if self._draws.data_ptr() != draws.data_ptr():
             # (use_draws copies rows that do not start on 16-byte boundaries: the copy would go stale at the next repetition)
@@ -599,6 +696,19 @@ class DeviceProjector(Projector):
         col = buf[:S]
         core_args = self._common(C) + [buf[S:].data_ptr(), S, 0]
         state = {"mom": None, "both": None}
+        if rows is not None:
+            table = self._rows_dev(rows, Z, ndim=2)
+            n_sub, tbase = int(table.shape[1]), table.data_ptr()
+
+            def run_rows(i):
+                if not 0 <= i < table.shape[0]:
+                    raise IndexError("step %d of an index table of %d rows" % (i, table.shape[0]))
+                if self._gauss:
+                    self._gauss_refresh()          # (the draws were rewritten in place: the operand follows them)
+                self._colsum_rows_enqueue(Z, tbase + 8 * n_sub * i, n_sub, col)
+                self._check(lib.bcx_project_write_points(*core_args))
+            run_rows.table = table
+            return run_rows, buf, k
 
         def run_gauss():
             self._gauss_refresh()              # (the draws were rewritten in place: the operand follows them)
@@ -634,16 +744,31 @@ class DeviceProjector(Projector):
             self._check(lib.bcx_project_write_points(*core_args))
         return run, buf, k
 
-    def project_select(self, pts, resid, row_ids=None):
+    def project_select(self, pts, resid, row_ids=None, *, rows=None):
         """(max_n corr_n, arg-max row) with corr_n = vecs[n].resid / ||vecs[n]|| / S (first maximum).
         ``row_ids`` (ascending, one per local row): the identity under which a local row competes -- its global row
         number (default: ``row_offset`` + local row) or, for a random subsample, its position in the drawn index
-        array -- so that the first-maximum rule of ``corrs.argmax()`` (sparsevi.py:55) holds across shards."""
+        array -- so that the first-maximum rule of ``corrs.argmax()`` (sparsevi.py:55) holds across shards.
+        ``rows`` (as ``project_colsum``): the arg-max over the rows ``pts[rows]``; the second value is then the POSITION in
+        ``rows`` of the first maximum (``sub[position]`` is the data row, sparsevi.py:57)."""
         torch = self._torch
         Z = self._dev(pts)
         S = self.theta.shape[0]
         r = torch.from_numpy(np.ascontiguousarray(resid, dtype=np.float64)).to(self.device)
         res = torch.empty(2, dtype=torch.float64, device=self.device)
+        if rows is not None:
+            rdev = self._rows_dev(rows, Z)
+            n_rows = int(rdev.numel())
+            if n_rows == 0:
+                return -np.inf, -1
+            work = self._select_scratch(n_rows, S)
+            tail = [r.data_ptr(), float(np.sum(resid)), res.data_ptr(), work.data_ptr(), work.numel() * 8]
+            if self._rows_fused(Z):
+                self._check(self._lib.bcx_project_select_rows_ws(*(self._common(Z) + [rdev.data_ptr(), n_rows] + tail)))
+            else:
+                self._check(self._lib.bcx_project_select_ws(*(self._common(self._gather(Z, rdev.data_ptr(), n_rows)) + tail)))
+            h = res.cpu()
+            return float(h[0]), int(h[1:2].view(torch.int64)[0])
         if Z.shape[0]:
             work = self._select_scratch(Z.shape[0], S)
             self._launch(self._lib.bcx_project_select_ws, self._common(Z) + [r.data_ptr(), float(np.sum(resid)), res.data_ptr(),

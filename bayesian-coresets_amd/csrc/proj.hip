@@ -48,6 +48,7 @@ struct ProjArgs {
   double* best_val;     // SELECT: gridDim.x
   int64_t* best_idx;    // SELECT: gridDim.x
   const double* tab;    // the likelihood's tables (proj_math.h), PJT_DOUBLES doubles in device memory
+  const int64_t* rows;  // GATHER instantiations: row i of the virtual N-row matrix is row rows[i] of Z (N = number of indices)
 };
 
 // gammaln(y + 1) of the Poisson likelihood (model_poiss.py:37).  Only WRITE forms it: along a row it is a constant, which
@@ -236,8 +237,15 @@ struct PjPos {       // one stage of the workgroup's sequence: k stage s of colu
   int64_t br;
 };
 
-template <int FAM, int MODE, bool ALIGNED, int NCT>
+// GATHER (COLSUM / SELECT): the rows are INDEXED rows of a standing matrix -- row i of the tile sequence is Z[rows[i]], duplicates
+// and any order allowed, no index checked.  Only addresses change: a request still carries one 32-bit number, now counted from
+// p.Z itself (in 16-byte units on the ALIGNED path, rows being 16-byte aligned there; in elements otherwise -- the entry refuses
+// a matrix beyond that reach), taken from the index array where the contiguous form computes it from the block's base; the
+// response of a row is read through its index.  Stages, zero-fill, arithmetic and every order of summation are those of the
+// contiguous kernel on a copy of the rows, so the results are too, bit for bit.  GATHER = false is the kernel as it was.
+template <int FAM, int MODE, bool ALIGNED, int NCT, bool GATHER = false>
 __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
+  static_assert(!GATHER || MODE != PMODE_WRITE, "the gathered form exists for the fused consumers");
   constexpr int COLS = PJ_COLS(NCT), TBYTES = PJ_TBYTES(NCT), TBASE = PJ_TBASE(NCT), ZRING = PJ_ZRING(NCT);
   constexpr int TCH = NCT / 2;               // Theta chunks (8 columns each) per wave and stage
   // ONE LDS object: staging rings | COLSUM: 4 x S column sums | SELECT: the four waves' candidates (a second __shared__
@@ -315,8 +323,23 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
   int64_t zp_br = -1;
   int tp_cg = -1;
   const int kmax = ALIGNED ? ((D - 1) & ~1) : (D - 1);
+  // the address of request j's row: block base + signed element offset, or (GATHER) p.Z + the unsigned row offset
+  auto zrow = [&](int j) {
+    if constexpr (GATHER) return p.Z + (size_t)(unsigned)zpv[LEAN ? 0 : j] * (ALIGNED ? 2 : 1);
+    else return zbase + zp(j);
+  };
   auto set_z = [&](int64_t fbr) {
     zp_br = fbr;
+    if constexpr (GATHER) {
+      // rows 8 j + fr of this wave's 32: their indices (beyond the last one: the last one -- zero-filled after landing)
+      const int64_t r = fbr * PJ_ROWS + 32 * wave + fr, rlast = p.N - 1;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int64_t off = p.rows[min(r + 8 * j, rlast)] * p.ldz;
+        zpv[LEAN ? 0 : j] = (int)(unsigned)(ALIGNED ? off >> 1 : off);
+      }
+      return;
+    }
     zbase = p.Z + fbr * PJ_ROWS * p.ldz;
     zmax = (int)((p.N - 1 - fbr * PJ_ROWS) * p.ldz);      // (>= 0: the block's first row exists)
     const int z0 = (32 * wave + fr) * (int)p.ldz;
@@ -354,7 +377,7 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
     const int kc = min(a.s * PJ_KC + 2 * fq, kmax);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
-      pj_glds16(zbase + (zp(j) + kc), lds0 + (unsigned)(zslot * PJ_ZBYTES + (4 * wave + j) * 1024));
+      pj_glds16(GATHER ? zrow(j) + kc : zbase + (zp(j) + kc), lds0 + (unsigned)(zslot * PJ_ZBYTES + (4 * wave + j) * 1024));
   };
   auto issue_t = [&](const PjPos& a, int tslot) {
     if (a.cg != tp_cg) set_t(a.cg);
@@ -385,7 +408,7 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
     const int k0 = min(k, D - 1), k1 = min(k + 1, D - 1);
 #pragma unroll
     for (int j = 0; j < 4 + TCH; ++j) {
-      const double* src = j < 4 ? zbase + zp(j) : p.theta + tp(j < 4 ? 0 : j - 4);
+      const double* src = j < 4 ? zrow(j) : p.theta + tp(j < 4 ? 0 : j - 4);
       sreg[ALIGNED ? 0 : j].x = src[k0];
       sreg[ALIGNED ? 0 : j].y = src[k1];
     }
@@ -515,7 +538,7 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
             if ((NG >= 8 ? q : q * NG / 8) != g) continue;
             if (q < TCH) { if (more) pj_glds16(p.theta + (tp(q) + (LEAN ? min(kts + 2 * fq, kmax) : kct)), lds0 + (unsigned)(TBASE + ts1 * TBYTES + (TCH * wave + q) * 1024)); }
             else if (ZRING == 3 ? more2 : more)
-              pj_glds16(zbase + (zp(q - TCH) + (LEAN ? min(kzs + 2 * fq, kmax) : kcz)), lds0 + (unsigned)((ZRING == 3 ? zs2 : zs1) * PJ_ZBYTES + (4 * wave + q - TCH) * 1024));
+              pj_glds16(GATHER ? zrow(q - TCH) + kcz : zbase + (zp(q - TCH) + (LEAN ? min(kzs + 2 * fq, kmax) : kcz)), lds0 + (unsigned)((ZRING == 3 ? zs2 : zs1) * PJ_ZBYTES + (4 * wave + q - TCH) * 1024));
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -554,7 +577,7 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
             if ((NG >= 8 ? q : q * NG / 8) != g) continue;
             if (q < TCH) { if (more) pj_glds16(p.theta + (tp(q) + (LEAN ? min(kts + 2 * fq, kmax) : kct)), lds0 + (unsigned)(TBASE + ts1 * TBYTES + (TCH * wave + q) * 1024)); }
             else if (ZRING == 3 ? more2 : more)
-              pj_glds16(zbase + (zp(q - TCH) + (LEAN ? min(kzs + 2 * fq, kmax) : kcz)), lds0 + (unsigned)((ZRING == 3 ? zs2 : zs1) * PJ_ZBYTES + (4 * wave + q - TCH) * 1024));
+              pj_glds16(GATHER ? zrow(q - TCH) + kcz : zbase + (zp(q - TCH) + (LEAN ? min(kzs + 2 * fq, kmax) : kcz)), lds0 + (unsigned)((ZRING == 3 ? zs2 : zs1) * PJ_ZBYTES + (4 * wave + q - TCH) * 1024));
           }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -711,7 +734,8 @@ __global__ __launch_bounds__(256, 2) void proj_kernel(ProjArgs p) {
             // (the row test on 32-bit numbers -- rows left in the matrix from this wave's first one, a scalar -- so that no 64-bit
             // lane value has to live across the k loop)
             const int rl = 16 * tr + li;
-            const double y = (p.ycol >= 0 && rl < rows_left) ? p.Z[(r0 + rl) * p.ldz + p.ycol] : 0.0;
+            // (GATHER: the response sits in the indexed row)
+            const double y = (p.ycol >= 0 && rl < rows_left) ? p.Z[(GATHER ? p.rows[GATHER ? r0 + rl : 0] : r0 + rl) * p.ldz + p.ycol] : 0.0;
             yq[tr] = (FAM == FAM_LINREG) ? 2.0 * y : y;      // (loglik_shifted)
             cq[tr] = (FAM == FAM_POISSON) ? 0.0 : clin;   // (Poisson: gammaln(y + 1) is constant along the row and cancels in value - shift)
             rs[tr] = 0.0; rq[tr] = 0.0; rd[tr] = 0.0;
@@ -1252,7 +1276,7 @@ struct ProjProfile {
 thread_local ProjProfile g_prof;
 }  // namespace
 
-template <int FAM, int MODE, int NCT, bool ALIGNED_ONLY = false> static int launch_one(bool aligned, dim3 grid, size_t shmem, hipStream_t st, const ProjArgs& p) {
+template <int FAM, int MODE, int NCT, bool ALIGNED_ONLY = false, bool GATHER = false> static int launch_one(bool aligned, dim3 grid, size_t shmem, hipStream_t st, const ProjArgs& p) {
   const bool timed = g_prof.on;
   if (timed) {
     if (g_prof.used == g_prof.ev.size()) {
@@ -1264,11 +1288,11 @@ template <int FAM, int MODE, int NCT, bool ALIGNED_ONLY = false> static int laun
     PROJ_HIP(hipEventRecord(g_prof.ev[g_prof.used].first, st));
   }
 if (aligned) {
-    PROJ_HIP(hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, true, NCT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL((proj_kernel<FAM, MODE, true, NCT>), grid, dim3(256), shmem, st, p);
+    PROJ_HIP(hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, true, NCT, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL((proj_kernel<FAM, MODE, true, NCT, GATHER>), grid, dim3(256), shmem, st, p);
   } else if constexpr (!ALIGNED_ONLY) {
-    PROJ_HIP(hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, false, NCT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
-    hipLaunchKernelGGL((proj_kernel<FAM, MODE, false, NCT>), grid, dim3(256), shmem, st, p);
+    PROJ_HIP(hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, false, NCT, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    hipLaunchKernelGGL((proj_kernel<FAM, MODE, false, NCT, GATHER>), grid, dim3(256), shmem, st, p);
   }
   PROJ_HIP(hipGetLastError());
   if (timed) {
@@ -1368,7 +1392,7 @@ static bool proj_aligned(const ProjArgs& p) {
   // 16-byte requests need 16-byte aligned rows: even leading dimensions and aligned bases (else 8-byte loads)
   return ((uintptr_t)p.Z % 16 == 0) && ((uintptr_t)p.theta % 16 == 0) && p.ldz % 2 == 0 && p.ldt % 2 == 0;
 }
-template <int MODE> static int launch_family(int family, dim3 grid, size_t extra_lds, hipStream_t st, const ProjArgs& p_in) {
+template <int MODE, bool GATHER = false> static int launch_family(int family, dim3 grid, size_t extra_lds, hipStream_t st, const ProjArgs& p_in) {
   ProjArgs p = p_in;
   const int nct = proj_nct(MODE, family, p.S, proj_aligned(p), p.D);
   const size_t tab_bytes = family == FAM_POISSON ? PJT_BYTES(PJT_DOUBLES) : family == FAM_LOGISTIC ? PJT_BYTES(PJT_DOUBLES_LOGISTIC) : 0;
@@ -1377,7 +1401,7 @@ template <int MODE> static int launch_family(int family, dim3 grid, size_t extra
   if (shmem > 160 * 1024) { g_proj_err = "bcx_project: S too large for the column-sum accumulators (S <= 3072)"; return BCX_ERR_ARG; }
   const bool aligned = proj_aligned(p);
   if constexpr (MODE == PMODE_SELECT) {
-    if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8, true>(true, grid, shmem, st, p);
+    if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8, true, GATHER>(true, grid, shmem, st, p);
   }
   if constexpr (MODE == PMODE_WRITE) {
     if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8, true>(true, grid, shmem, st, p);
@@ -1386,16 +1410,16 @@ template <int MODE> static int launch_family(int family, dim3 grid, size_t extra
     if (nct == 8 && family == FAM_GAUSSIAN) return launch_one<FAM_GAUSSIAN, MODE, 8, true>(true, grid, shmem, st, p);
   }
   if constexpr (MODE == PMODE_COLSUM) {
-    if (nct == 8 && family == FAM_GAUSSIAN) return launch_one<FAM_GAUSSIAN, MODE, 8>(aligned, grid, shmem, st, p);
-    if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8>(aligned, grid, shmem, st, p);
-    if (nct == 8 && family == FAM_LOGISTIC) return launch_one<FAM_LOGISTIC, MODE, 8, true>(true, grid, shmem, st, p);
-    if (nct == 8 && family == FAM_POISSON) return launch_one<FAM_POISSON, MODE, 8, true>(true, grid, shmem, st, p);
+    if (nct == 8 && family == FAM_GAUSSIAN) return launch_one<FAM_GAUSSIAN, MODE, 8, false, GATHER>(aligned, grid, shmem, st, p);
+    if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8, false, GATHER>(aligned, grid, shmem, st, p);
+    if (nct == 8 && family == FAM_LOGISTIC) return launch_one<FAM_LOGISTIC, MODE, 8, true, GATHER>(true, grid, shmem, st, p);
+    if (nct == 8 && family == FAM_POISSON) return launch_one<FAM_POISSON, MODE, 8, true, GATHER>(true, grid, shmem, st, p);
   }
   switch (family) {
-    case FAM_LOGISTIC: return launch_one<FAM_LOGISTIC, MODE, 4>(aligned, grid, shmem, st, p);
-    case FAM_POISSON: return launch_one<FAM_POISSON, MODE, 4>(aligned, grid, shmem, st, p);
-    case FAM_LINREG: return launch_one<FAM_LINREG, MODE, 4>(aligned, grid, shmem, st, p);
-    case FAM_GAUSSIAN: return launch_one<FAM_GAUSSIAN, MODE, 4>(aligned, grid, shmem, st, p);
+    case FAM_LOGISTIC: return launch_one<FAM_LOGISTIC, MODE, 4, false, GATHER>(aligned, grid, shmem, st, p);
+    case FAM_POISSON: return launch_one<FAM_POISSON, MODE, 4, false, GATHER>(aligned, grid, shmem, st, p);
+    case FAM_LINREG: return launch_one<FAM_LINREG, MODE, 4, false, GATHER>(aligned, grid, shmem, st, p);
+    case FAM_GAUSSIAN: return launch_one<FAM_GAUSSIAN, MODE, 4, false, GATHER>(aligned, grid, shmem, st, p);
     default: g_proj_err = "unknown likelihood family"; return BCX_ERR_ARG;
   }
 }
@@ -1417,7 +1441,7 @@ static int fill(ProjArgs& p, int family, const void* Z, int64_t N, int64_t ldz, 
   p.Z = (const double*)Z; p.theta = (const double*)theta; p.N = N; p.ldz = ldz; p.ldt = ldt; p.D = D; p.S = S;
   p.ycol = has_y ? ycol : -1; p.param = param;
   p.out = nullptr; p.ldo = 0; p.rowsum = nullptr; p.colpart = nullptr; p.resid = nullptr; p.resid_sum = 0.0;
-  p.best_val = nullptr; p.best_idx = nullptr; p.team = 0; p.part = nullptr; p.tab = nullptr;
+  p.best_val = nullptr; p.best_idx = nullptr; p.team = 0; p.part = nullptr; p.tab = nullptr; p.rows = nullptr;
   return BCX_OK;
 }
 
@@ -1548,24 +1572,56 @@ extern "C" int bcx_project_points_colsum_moments(void* stream, const void* Zc_de
   return BCX_OK;
 }
 
-// colsum_dev[s] = sum_n vecs[n][s] without materialising vecs.  work_dev: 2048 * S doubles.
-extern "C" int bcx_project_colsum(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
-                                  int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
-                                  void* colsum_dev, void* work_dev) {
+// The gathered consumers (bcx_project_*_rows): n_rows indices into the N rows of Z.  A request of the kernel carries a 32-bit
+// offset from Z itself, in 16-byte units where the rows are 16-byte aligned and in elements otherwise: a matrix beyond that
+// reach (64 GiB / 32 GiB) is refused -- the caller gathers with bcx_gather_rows and takes the contiguous entry.
+static int rows_check(const ProjArgs& p, const void* rows_dev, int64_t n_rows, int64_t N, const char* who) {
+  if (N < 0 || (n_rows > 0 && (!rows_dev || N < 1))) { g_proj_err = std::string(who) + ": bad index table"; return BCX_ERR_ARG; }
+  const int64_t last = N > 0 ? (N - 1) * p.ldz : 0;
+  if ((proj_aligned(p) ? last >> 1 : last) > (int64_t)0xffffffffLL) {
+    g_proj_err = std::string(who) + ": the matrix is beyond the 32-bit reach of the gathered requests (bcx_gather_rows + the contiguous entry)";
+    return BCX_ERR_ARG;
+  }
+  return BCX_OK;
+}
+
+// rows_dev == nullptr: the N rows of Z themselves; otherwise N indices into the n_total rows of Z
+static int project_colsum(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
+                          int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
+                          void* colsum_dev, void* work_dev, const void* rows_dev, int64_t n_total, bool gather) {
   ProjArgs p;
   int rc = fill(p, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param);
   if (rc) return rc;
   if (!colsum_dev || !work_dev) { g_proj_err = "bcx_project_colsum: bad output"; return BCX_ERR_ARG; }
+  if (gather && (rc = rows_check(p, rows_dev, N, n_total, "bcx_project_colsum_rows"))) return rc;
+  p.rows = (const int64_t*)rows_dev;
   hipStream_t st = (hipStream_t)stream;
   int grid = 0;
   p.colpart = (double*)work_dev;
   proj_plan(PMODE_COLSUM, family, N, S, proj_aligned(p), D, &grid, &p.team);
   const size_t cacc = p.team ? (size_t)16 * proj_nct(PMODE_COLSUM, family, S, proj_aligned(p), D) : (size_t)S;   // accumulators per wave
-  if ((rc = launch_family<PMODE_COLSUM>(family, dim3(grid), 4 * cacc * sizeof(double), st, p))) return rc;
+  if (gather) rc = launch_family<PMODE_COLSUM, true>(family, dim3(grid), 4 * cacc * sizeof(double), st, p);
+  else rc = launch_family<PMODE_COLSUM>(family, dim3(grid), 4 * cacc * sizeof(double), st, p);
+  if (rc) return rc;
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3((S + 63) / 64), dim3(256), 0, st, p.colpart, grid, S, (double*)colsum_dev);
   hipLaunchKernelGGL(colsum_center_kernel, dim3(1), dim3(256), 0, st, S, (double*)colsum_dev);
   PROJ_HIP(hipGetLastError());
   return BCX_OK;
+}
+
+// colsum_dev[s] = sum_n vecs[n][s] without materialising vecs.  work_dev: 2048 * S doubles.
+extern "C" int bcx_project_colsum(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
+                                  int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
+                                  void* colsum_dev, void* work_dev) {
+  return project_colsum(stream, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param, colsum_dev, work_dev, nullptr, N, false);
+}
+// The same over the n_rows INDEXED rows Z[rows[i]] of the N-row matrix (int64 indices in device memory, each in [0, N): not
+// checked; duplicates and any order allowed): the bits of bcx_project_colsum on a contiguous copy of those rows with the same
+// leading dimension and alignment.
+extern "C" int bcx_project_colsum_rows(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
+                                       int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
+                                       const void* rows_dev, int64_t n_rows, void* colsum_dev, void* work_dev) {
+  return project_colsum(stream, family, Z_dev, n_rows, ldz, D, ycol, theta_dev, S, ldt, param, colsum_dev, work_dev, rows_dev, N, true);
 }
 
 // arg-max_n of vecs[n].resid / ||vecs[n]|| / S  (first maximum), result to result_dev = {double value, int64 row}.
@@ -1580,11 +1636,14 @@ extern "C" int64_t bcx_project_select_scratch_bytes(int32_t family, int64_t N, i
 
 static int project_select(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
                           int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
-                          const void* resid_dev, double resid_sum, void* result_dev, void* work_dev, void* part_dev) {
+                          const void* resid_dev, double resid_sum, void* result_dev, void* work_dev, void* part_dev,
+                          const void* rows_dev = nullptr, int64_t n_total = 0, bool gather = false) {
   ProjArgs p;
   int rc = fill(p, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param);
   if (rc) return rc;
   if (!resid_dev || !result_dev || !work_dev) { g_proj_err = "bcx_project_select: bad output"; return BCX_ERR_ARG; }
+  if (gather && (rc = rows_check(p, rows_dev, N, n_total, "bcx_project_select_rows_ws"))) return rc;
+  p.rows = (const int64_t*)rows_dev;
   hipStream_t st = (hipStream_t)stream;
   int grid = 0;
   proj_plan(PMODE_SELECT, family, N, S, proj_aligned(p), D, &grid, &p.team);
@@ -1607,7 +1666,10 @@ static int project_select(void* stream, int32_t family, const void* Z_dev, int64
     own = true;
   }
   p.part = (double*)part;
-  if (N > 0 && (rc = launch_family<PMODE_SELECT>(family, dim3(grid), 0, st, p))) { if (own) (void)hipFreeAsync(part, st); return rc; }
+  if (N > 0) {
+    rc = gather ? launch_family<PMODE_SELECT, true>(family, dim3(grid), 0, st, p) : launch_family<PMODE_SELECT>(family, dim3(grid), 0, st, p);
+    if (rc) { if (own) (void)hipFreeAsync(part, st); return rc; }
+  }
   const int nparts = (int)std::max<int64_t>(1, std::min<int64_t>((N + 255) / 256, 512));
   hipLaunchKernelGGL(select_combine_kernel, dim3(nparts), dim3(256), 0, st, (const double*)part, N, ngc, cols, S, p.resid, p.best_val,
                      p.best_idx);
@@ -1633,6 +1695,62 @@ extern "C" int bcx_project_select_ws(void* stream, int32_t family, const void* Z
   if (work_bytes < bcx_project_select_scratch_bytes(family, N, S)) { g_proj_err = "bcx_project_select_ws: scratch too small"; return BCX_ERR_ARG; }
   return project_select(stream, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param, resid_dev, resid_sum, result_dev, work_dev,
                         work_dev ? (char*)work_dev + 4096 * sizeof(double) : nullptr);
+}
+
+// The select step over the n_rows indexed rows Z[rows[i]] (as bcx_project_colsum_rows): result_dev = {value, POSITION i in rows}
+// (first maximum), the pair bcx_project_select_ws returns on a contiguous copy of those rows.  All scratch from the caller:
+// bcx_project_select_rows_scratch_bytes(family, n_rows, S) bytes.
+extern "C" int64_t bcx_project_select_rows_scratch_bytes(int32_t family, int64_t n_rows, int32_t S) {
+  return bcx_project_select_scratch_bytes(family, n_rows, S);
+}
+extern "C" int bcx_project_select_rows_ws(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
+                                          int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
+                                          const void* rows_dev, int64_t n_rows, const void* resid_dev, double resid_sum,
+                                          void* result_dev, void* work_dev, int64_t work_bytes) {
+  if (n_rows < 0 || work_bytes < bcx_project_select_rows_scratch_bytes(family, n_rows, S)) {
+    g_proj_err = "bcx_project_select_rows_ws: scratch too small";
+    return BCX_ERR_ARG;
+  }
+  return project_select(stream, family, Z_dev, n_rows, ldz, D, ycol, theta_dev, S, ldt, param, resid_dev, resid_sum, result_dev, work_dev,
+                        work_dev ? (char*)work_dev + 4096 * sizeof(double) : nullptr, rows_dev, N, true);
+}
+
+// out[i][0 .. C) = Z[rows[i]][0 .. C): a memory-bound copy of indexed rows into a contiguous buffer, 16-byte pieces where both
+// sides allow them (aligned bases, even leading dimensions), one piece per thread.
+template <bool VEC>
+__global__ __launch_bounds__(256) void gather_rows_kernel(const double* Z, int64_t ldz, int C, const int64_t* rows, int64_t n_rows,
+                                                          double* out, int64_t ldo) {
+  const int ppr = VEC ? (C + 1) / 2 : C;                                // pieces per row
+  const int64_t total = n_rows * ppr;
+  for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (int64_t)gridDim.x * 256) {
+    const int64_t i = t / ppr;
+    const int q = (int)(t - i * ppr);
+    const double* src = Z + rows[i] * ldz;
+    double* dst = out + i * ldo;
+    if (VEC) {
+      if (2 * q + 1 < C) *(pv2d*)(dst + 2 * q) = *(const pv2d*)(src + 2 * q);
+      else dst[2 * q] = src[2 * q];
+    } else {
+      dst[q] = src[q];
+    }
+  }
+}
+extern "C" int bcx_gather_rows(void* stream, const void* Z_dev, int64_t ldz, int32_t C, const void* rows_dev, int64_t n_rows,
+                               void* out_dev, int64_t ldo) {
+  if (n_rows < 0 || C < 1 || ldz < C || ldo < C || (n_rows > 0 && (!Z_dev || !rows_dev || !out_dev))) {
+    g_proj_err = "bcx_gather_rows: bad arguments";
+    return BCX_ERR_ARG;
+  }
+  if (n_rows == 0) return BCX_OK;
+  const bool vec = (uintptr_t)Z_dev % 16 == 0 && (uintptr_t)out_dev % 16 == 0 && ldz % 2 == 0 && ldo % 2 == 0;
+  const int64_t total = n_rows * (vec ? (C + 1) / 2 : C);
+  const int g = (int)std::max<int64_t>(1, std::min<int64_t>((total + 255) / 256, 8192));
+  if (vec) hipLaunchKernelGGL(gather_rows_kernel<true>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const double*)Z_dev, ldz, (int)C,
+                              (const int64_t*)rows_dev, n_rows, (double*)out_dev, ldo);
+  else hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const double*)Z_dev, ldz, (int)C,
+                          (const int64_t*)rows_dev, n_rows, (double*)out_dev, ldo);
+  PROJ_HIP(hipGetLastError());
+  return BCX_OK;
 }
 
 // rows_dev (N x ld doubles, S used per row) -= its row means, in place: projector.py:21 for rows that were written raw

@@ -78,15 +78,18 @@ def run(a):
         bb = lambda sampler: bc.DeviceProjector("gaussian", sampler, a.proj_dim, Siginv=Siginv)
         sampler_w = bc.GaussianPosteriorSampler(mu0, Sig0inv, Siginv, seed=a.trial)
     sched = eval(a.step_sched)
+    sub_mode = "device" if device else "host"       # (sub-sampled steps project the drawn rows where the data is resident)
     build = {
-        "SVI": lambda: bc.SparseVICoreset(x, bb(sampler_w), opt_itrs=a.opt_itrs, step_sched=sched),
+        "SVI": lambda: bc.SparseVICoreset(x, bb(sampler_w), n_subsample_select=a.subsample_select, n_subsample_opt=a.subsample_opt,
+                                          opt_itrs=a.opt_itrs, step_sched=sched, subsample=sub_mode),
         "SVI-EXACT": lambda: bc.SparseVICoreset(x, exact(), opt_itrs=a.opt_itrs, step_sched=sched),
         "GIGA-OPT": lambda: bc.HilbertCoreset(x, bb(fixed(mup, Up))),
         "GIGA-OPT-EXACT": lambda: bc.HilbertCoreset(x, exact(x)),
         "GIGA-REAL": lambda: bc.HilbertCoreset(x, bb(fixed(muh, Uh))),
         "GIGA-REAL-EXACT": lambda: bc.HilbertCoreset(x, exact(xhat)),
         "US": lambda: bc.UniformSamplingCoreset(x),
-        "PSVI": lambda: bc.BatchPSVICoreset(x, bb(sampler_w), opt_itrs=a.opt_itrs, step_sched=sched),
+        "PSVI": lambda: bc.BatchPSVICoreset(x, bb(sampler_w), opt_itrs=a.opt_itrs, n_subsample_opt=a.subsample_opt, step_sched=sched,
+                                            subsample=sub_mode),
     }
     alg = build[a.alg]()
     n = Ms.shape[0]
@@ -133,6 +136,8 @@ def parser():
     ap.add_argument("--coreset_size_spacing", type=str, choices=["log", "linear"], default="log")
     ap.add_argument("--opt_itrs", type=int, default=100)
     ap.add_argument("--step_sched", type=str, default="lambda i : 1./(1+i)")
+    ap.add_argument("--subsample_select", type=int, default=None, help="SVI: rows drawn for every selection step (default: all)")
+    ap.add_argument("--subsample_opt", type=int, default=None, help="SVI / PSVI: rows drawn for every ADAM step (default: all)")
     ap.add_argument("--trial", type=int, default=1)
     ap.add_argument("--results_folder", type=str, default="results/")
     ap.add_argument("--verbosity", type=str, default="error", choices=["error", "warning", "critical", "info", "debug"])

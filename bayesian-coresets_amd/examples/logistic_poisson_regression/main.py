@@ -97,7 +97,9 @@ def run(a):
             sampler_w = sampler_host
     dev = lambda sampler: bc.DeviceProjector(family, sampler, a.proj_dim)
     build = {
-        "SVI": lambda: bc.SparseVICoreset(Z, dev(sampler_w), opt_itrs=a.opt_itrs, step_sched=eval(a.step_sched)),
+        # (--subsample_select / --subsample_opt: the drawn rows are projected where the data is resident, never gathered on the host)
+        "SVI": lambda: bc.SparseVICoreset(Z, dev(sampler_w), n_subsample_select=a.subsample_select, n_subsample_opt=a.subsample_opt,
+                                          opt_itrs=a.opt_itrs, step_sched=eval(a.step_sched), subsample="device"),
         "GIGA-OPT": lambda: bc.HilbertCoreset(Z, dev(gauss(mup, Sigp))),
         "GIGA-REAL": lambda: bc.HilbertCoreset(Z, dev(gauss(muh, Sigh))),
         "US": lambda: bc.UniformSamplingCoreset(Z),
@@ -145,6 +147,8 @@ def parser():
     ap.add_argument("--coreset_size_spacing", type=str, choices=["log", "linear"], default="log")
     ap.add_argument("--opt_itrs", type=int, default=100)
     ap.add_argument("--step_sched", type=str, default="lambda i : 1./(1+i)")
+    ap.add_argument("--subsample_select", type=int, default=None, help="SVI: rows drawn for every selection step (default: all)")
+    ap.add_argument("--subsample_opt", type=int, default=None, help="SVI: rows drawn for every ADAM step (default: all)")
     ap.add_argument("--trial", type=int, default=1)
     ap.add_argument("--results_folder", type=str, default="results/")
     ap.add_argument("--verbosity", type=str, default="error", choices=["error", "warning", "critical", "info", "debug"])

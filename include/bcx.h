@@ -253,6 +253,27 @@ int64_t bcx_project_select_scratch_bytes(int32_t family, int64_t N, int32_t S);
 int bcx_project_select_ws(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
                           int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
                           const void* resid_dev, double resid_sum, void* result_dev, void* work_dev, int64_t work_bytes);
+/* The two fused consumers on INDEXED rows of a standing matrix: row i of the virtual n_rows-row matrix is Z[rows[i]], rows_dev =
+ * n_rows int64 indices in device memory, duplicates and any order allowed (a `randint` draw).  Every index must lie in [0, N):
+ * the kernel does not check -- the caller validates the table before it uploads it.  Same kernel, launch plan and order of
+ * every sum as the contiguous entries take for N = n_rows: the results are those of bcx_project_colsum / bcx_project_select_ws on
+ * a contiguous copy of the indexed rows (same leading dimension and 16-byte alignment class), bit for bit; the select's
+ * result_dev names the POSITION i in rows (first maximum).  n_rows = 0: zeros / (-inf, -1).  The row requests carry 32-bit
+ * offsets from Z_dev (16-byte units for 16-byte aligned rows, elements otherwise): a matrix of more than 64 GiB / 32 GiB is
+ * refused with BCX_ERR_ARG -- gather with bcx_gather_rows and call the contiguous entry instead.
+ * Scratch as the contiguous entries: work_dev = 2048*S doubles (colsum), bcx_project_select_rows_scratch_bytes (select). */
+int bcx_project_colsum_rows(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
+                            int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
+                            const void* rows_dev, int64_t n_rows, void* colsum_dev, void* work_dev);
+int64_t bcx_project_select_rows_scratch_bytes(int32_t family, int64_t n_rows, int32_t S);
+int bcx_project_select_rows_ws(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
+                               int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
+                               const void* rows_dev, int64_t n_rows, const void* resid_dev, double resid_sum,
+                               void* result_dev, void* work_dev, int64_t work_bytes);
+/* out_dev[i][0 .. C) = Z_dev[rows[i]][0 .. C) for i < n_rows (out_dev: n_rows x ldo doubles, caller-owned): a plain copy of the
+ * indexed rows, 16-byte pieces where bases and leading dimensions allow them.  Indices are not checked. */
+int bcx_gather_rows(void* stream, const void* Z_dev, int64_t ldz, int32_t C, const void* rows_dev, int64_t n_rows,
+                    void* out_dev, int64_t ldo);
 /* Closed-form column sums of the linear-regression family (family 2) from the one-time second moments of the data:
  *   sum_n (y_n - x_n.theta)^2 = yy - 2 theta^T X^T y + theta^T X^T X theta
  * so the 1 + opt_itrs full-data column sums of a SparseVI step (sparsevi.py:23-42, 69-76; model_linreg.py:4-10) cost
