@@ -916,20 +916,32 @@ extern "C" int bcx_argmax_correlation(bcx_solver* s, const double* query_host, i
   int rc = read_state(s, &h);
   if (rc != BCX_OK) return rc;
   std::vector<double> q64((size_t)s->ld64, 0.0);
+  // |q| without leaving fp64's range at any scale of q: the squares are taken of q * 2^-E0, E0 the exponent of the largest
+  // element; the fp32 query then holds q * 2^-E with E the exponent of |q| (apply_common.h store_query: same rule)
+  double qmax = 0.0;
+  for (int j = 0; j < d; ++j) { q64[j] = query_host[j]; qmax = std::fmax(qmax, std::fabs(query_host[j])); }
+  const bool scalable = qmax > 0.0 && qmax < INFINITY;     // (a zero, infinite or NaN query is scanned as it is)
+  const int E0 = scalable ? std::ilogb(qmax) : 0;
   double qn = 0.0;
-  for (int j = 0; j < d; ++j) { q64[j] = query_host[j]; qn += query_host[j] * query_host[j]; }
+  for (int j = 0; j < d; ++j) { const double t = std::ldexp(query_host[j], -E0); qn += t * t; }
+  qn = std::sqrt(qn);                                      // |q| * 2^-E0, in [1, 2 sqrt(d))
+  int E = 0;
   BCX_HIP(hipMemcpy(s->q64, q64.data(), (size_t)s->ld64 * 8, hipMemcpyHostToDevice));
   if (s->cfg.store_dtype == BCX_F64) {
     std::vector<double> qs((size_t)s->ld, 0.0);
     for (int j = 0; j < d; ++j) qs[j] = query_host[j];
     BCX_HIP(hipMemcpy(s->qst, qs.data(), (size_t)s->ld * 8, hipMemcpyHostToDevice));
+    qn = std::ldexp(qn, E0);                               // (not read: the fp64 scan's error term is zero)
   } else {
+    const int E1 = (scalable && qn > 0.0 && qn < INFINITY) ? std::ilogb(qn) : 0;   // (a NaN element: no second step)
+    E = E0 + E1;
     std::vector<float> qs((size_t)s->ld, 0.f);
-    for (int j = 0; j < d; ++j) qs[j] = (float)query_host[j];
+    for (int j = 0; j < d; ++j) qs[j] = (float)std::ldexp(query_host[j], -E);
     BCX_HIP(hipMemcpy(s->qst, qs.data(), (size_t)s->ld * 4, hipMemcpyHostToDevice));
+    qn = std::ldexp(qn, -E1);
   }
   DevState forced = h;
-  forced.active = 1; forced.exact_mode = 0; forced.qscale = sqrt(qn);
+  forced.active = 1; forced.exact_mode = 0; forced.qscale = qn; forced.qexp = E;
   double rec[BCX_REC_HDR];
   for (int attempt = 0; attempt < 2; ++attempt) {
     forced.exact_mode = attempt;

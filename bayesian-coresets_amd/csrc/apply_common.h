@@ -28,10 +28,24 @@ struct ApplyArgs {
   int32_t* tr_status;
 };
 
-static __device__ __forceinline__ void store_query(const ApplyArgs& a, int which, int j, double v) {
+// The scan reads a fp32 query (fp32 / fp16 storage).  A residual query is stored there as q * 2^-E, E the exponent of its
+// norm: the stored norm lies in [1, 2) whatever the scale of the data, so neither the query nor the scan's error term
+// err_coef * qscale can leave fp32's range.  The scaling is exact (a power of two) and E is computed from replicated state,
+// so every shard derives the same one; q64 -- what the fp64 re-score reads -- stays as it is.  fp64 storage: E = 0.
+static __device__ __forceinline__ int query_exponent(const ApplyArgs& a, double qnorm) {
+  return (a.store_f64 || !(qnorm > 0.0) || !(qnorm < INFINITY)) ? 0 : ilogb(qnorm);
+}
+
+static __device__ __forceinline__ void store_query(const ApplyArgs& a, int which, int j, double v, int E = 0) {
   a.q64[(size_t)which * a.ld64 + j] = v;
   if (a.store_f64) ((double*)a.qst)[(size_t)which * a.ld + j] = v;
-  else ((float*)a.qst)[(size_t)which * a.ld + j] = (float)v;
+  else ((float*)a.qst)[(size_t)which * a.ld + j] = (float)(E ? ldexp(v, -E) : v);
+}
+
+// norm of the stored query and its exponent (one thread)
+static __device__ __forceinline__ void set_query_scale(DevState* st, double qnorm, int E) {
+  st->qscale = E ? ldexp(qnorm, -E) : qnorm;
+  st->qexp = E;
 }
 
 // Query for the next select.  Returns false when the reference's _select would raise
@@ -41,8 +55,10 @@ static __device__ bool prepare_query(const ApplyArgs& a, double* scratch) {
   const int d = a.d;
   if (a.alg != BCX_ALG_GIGA) {
     // residual = b - A w    frankwolfe.py:16 / orthopursuit.py:18
-    for (int j = threadIdx.x; j < d; j += blockDim.x) store_query(a, 0, j, a.b[j] - a.xw[j]);
-    if (threadIdx.x == 0) st->qscale = st->err;
+    const double qn = st->err;
+    const int E = query_exponent(a, qn);
+    for (int j = threadIdx.x; j < d; j += blockDim.x) store_query(a, 0, j, a.b[j] - a.xw[j], E);
+    if (threadIdx.x == 0) set_query_scale(st, qn, E);
     return true;
   }
   const double nw = st->nw;
@@ -64,7 +80,7 @@ static __device__ bool prepare_query(const ApplyArgs& a, double* scratch) {
     store_query(a, 0, j, a.tmp[j] / cn);
     store_query(a, 1, j, a.xw[j] / nw);
   }
-  if (threadIdx.x == 0) st->qscale = 1.0;
+  if (threadIdx.x == 0) set_query_scale(st, 1.0, 0);
   return true;
 }
 

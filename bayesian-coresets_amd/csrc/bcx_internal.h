@@ -101,7 +101,9 @@ struct DevState {
   int64_t n_cand;      // diagnostics: candidate rows re-scored in fp64, summed over iterations
   int64_t n_resolved;  // diagnostics: resolve passes
   int64_t n_omp[4];    // diagnostics (omp_lh.hip): OMP steps, columns that left, from-scratch re-solves, extra columns entered
-  double qscale;       // norm of the query vector (error bound of the fp32 scan scales with it)
+  double qscale;       // norm of the query vector AS STORED for the scan (error bound of the fp32 scan scales with it)
+  int32_t qexp;        // the fp32 query holds q * 2^-qexp (apply_common.h store_query); a low-precision score that leaves
+  int32_t qexp_pad;    // the scan unre-scored is multiplied back by 2^qexp (resolve_core.h)
   long long dbg_t[32]; // phase time stamps of the last tail (dev builds with -DBCX_TIMING, tools/tail_timing.py)
 };
 

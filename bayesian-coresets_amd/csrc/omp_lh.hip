@@ -737,6 +737,7 @@ __global__ __launch_bounds__(THREADS) void omp_lh_kernel(NnlsArgs n, GridSync gs
   // query b - xw' (prepare_query, orthopursuit.py:18) in the pass that commits xw', from the copies in LDS: prepare_next
   // would read the counters, b and xw' back from memory (three dependent round trips, ~2 us of every step).
   const bool fast_next = status == BCX_IT_OK && it0 + 1 < itrs0 && !(a.refresh_every > 0 && since0 + 1 >= a.refresh_every);
+  const int qE = query_exponent(a, new_err);      // (the next query's norm is the new error)
   if (status == BCX_IT_OK) {
     for (int q = tid; q < p; q += blockDim.x) n.plist[q] = L.cs[q];
     for (int j = tid; j < k1; j += blockDim.x) {
@@ -747,7 +748,7 @@ __global__ __launch_bounds__(THREADS) void omp_lh_kernel(NnlsArgs n, GridSync gs
     }
     for (int j = tid; j < d; j += blockDim.x) {
       a.xw[j] = L.qs[j];
-      if (fast_next) store_query(a, 0, j, L.bs[j] - L.qs[j]);
+      if (fast_next) store_query(a, 0, j, L.bs[j] - L.qs[j], qE);
     }
     if (tid == 0) {
       st->k = k1;
@@ -759,7 +760,7 @@ __global__ __launch_bounds__(THREADS) void omp_lh_kernel(NnlsArgs n, GridSync gs
       st->nw = nwn == 0.0 ? 1.0 : nwn;
       st->since_refresh = since0 + 1;
       if (checked && !no_mono0) st->retried = 0;
-      if (fast_next) st->qscale = new_err;
+      if (fast_next) set_query_scale(st, new_err, qE);
     }
   } else if (tid == 0) {
     st->hvalid = 0;        // weights were not touched; H and the lists changed: rebuilt from the weights next time

@@ -133,7 +133,10 @@ static __device__ __forceinline__ void resolve_core(const ResolveArgs& a, Winner
   // one shard than on four (found by the 4-rank exact-fallback test on rows duplicated up to scaling) -- or (b) a
   // single candidate on a single shard, whose score nobody reads (the usual case: 1.00-1.01 candidates per iteration).
   const bool unscored = exact || (!a.need_score && nc == 1);
-  if (unscored && tid < nc) cscore[tid] = exact ? Lstar : 0.0;
+  // (an "exact" scan over the stored low-precision rows -- no resident fp64 rows -- scored the scaled query q * 2^-qexp:
+  //  its score goes back to the caller's scale here)
+  const bool lowp_final = exact && !a.store_f64 && !a.A64;
+  if (unscored && tid < nc) cscore[tid] = exact ? (lowp_final ? ldexp(Lstar, a.st->qexp) : Lstar) : 0.0;
   // A single candidate that has to be scored (the OMP step compares its score with the negative direction, a row shard
   // sends it to its peers): the wave that scores it leaves the raw row in LDS / in the record as it reads it, and the
   // winner's row is not fetched a second time -- one dependent round trip less (the usual case: 1.00-1.01 candidates).

@@ -208,8 +208,9 @@ static __device__ void apply_core(const ApplyArgs& a, const StateVecs& v, int64_
                     !(a.refresh_every > 0 && since + 1 >= a.refresh_every);
   if (fast) {
     if (ALG != BCX_ALG_GIGA) {
-      for (int j = tid; j < d; j += blockDim.x) store_query(a, 0, j, v.b[j] - v.xw[j]);   // frankwolfe.py:16
-      if (tid == 0) st->qscale = new_err;
+      const int E = query_exponent(a, new_err);
+      for (int j = tid; j < d; j += blockDim.x) store_query(a, 0, j, v.b[j] - v.xw[j], E);   // frankwolfe.py:16
+      if (tid == 0) set_query_scale(st, new_err, E);
       BCX_STAMP(st, 9);
       return;
     }
@@ -228,7 +229,7 @@ static __device__ void apply_core(const ApplyArgs& a, const StateVecs& v, int64_
         store_query(a, 0, j, v.tx[j] / cn);
         store_query(a, 1, j, v.xw[j] / new_nw);
       }
-      if (tid == 0) st->qscale = 1.0;
+      if (tid == 0) set_query_scale(st, 1.0, 0);
       BCX_STAMP(st, 9);
       return;
     }
