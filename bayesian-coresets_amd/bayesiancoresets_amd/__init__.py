@@ -12,6 +12,7 @@ from .projector import BlackBoxProjector, Projector, DeviceProjector
 from .linreg_sampler import LinregPosteriorSampler
 from .laplace_sampler import LaplacePosteriorSampler
 from .gaussian_sampler import GaussianPosteriorSampler
+from .mcmc import DeviceHMC, log_joint_grad
 from . import snnls
 from . import util
 

@@ -46,6 +46,8 @@ SYMBOLS = (
     "bcx_gaussian_posterior_draw", "bcx_project_grad_points_gaussian", "bcx_psvi_gradient_gaussian",
     "bcx_psvi_adam_step",
     "bcx_project_colsum_rows", "bcx_project_select_rows_ws", "bcx_project_select_rows_scratch_bytes", "bcx_gather_rows",
+    "bcx_log_joint_grad", "bcx_log_joint_grad_scratch_bytes", "bcx_hmc_coreset", "bcx_hmc_coreset_ok", "bcx_hmc_coreset_lds_bytes",
+    "bcx_hmc_stream", "bcx_hmc_stream_scratch_bytes",
 )
 
 
@@ -198,6 +200,17 @@ def load():
     sigs["bcx_project_grad_points_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp]
     sigs["bcx_psvi_gradient_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp, i64, vp, dbl, vp, vp]
     sigs["bcx_psvi_adam_step"] = [vp, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i32, dbl, dbl, dbl, vp, i64, vp, vp]
+    sigs["bcx_log_joint_grad"] = [vp, i32, vp, i64, i64, i32, vp, vp, i32, i32, vp, vp, vp]
+    lib.bcx_log_joint_grad_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_log_joint_grad_scratch_bytes.argtypes = [i64, i32, i32]
+    hmc_common = [vp, vp, i64, i32, i32, i32, i32, dbl, dbl, vp, i32, vp, vp, vp, vp, vp, vp, vp]
+    sigs["bcx_hmc_coreset"] = [vp, i32, i32, i32, vp, vp, i64] + hmc_common
+    sigs["bcx_hmc_stream"] = [vp, i32, i64, i32, vp, vp, i64] + hmc_common + [vp, i64]
+    sigs["bcx_hmc_coreset_ok"] = [i32, i32]
+    lib.bcx_hmc_coreset_lds_bytes.restype = ctypes.c_int64
+    lib.bcx_hmc_coreset_lds_bytes.argtypes = [i32, i32]
+    lib.bcx_hmc_stream_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_hmc_stream_scratch_bytes.argtypes = [i64, i32, i32]
     lib.bcx_psvi_gradient_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_psvi_gradient_scratch_bytes.argtypes = [i32, i32]
     sigs["bcx_linreg_posterior_draw_factored"] = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp]

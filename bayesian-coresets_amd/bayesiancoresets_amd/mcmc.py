@@ -1,0 +1,226 @@
+"""MCMC on the weighted points: what a Bayesian coreset is built for.  The reference's logistic / Poisson regression
+experiment scores every coreset by running Stan on it with ``'w': wts`` (examples/logistic_poisson_regression/main.py:107-127,
+205-232; examples/common/mcmc.py:60-70); here the sampler is Hamiltonian Monte Carlo on the device (csrc/hmc.hip):
+
+* ``DeviceHMC(family, D, chains, leapfrog, seed).sample(pts, wts, n_samples, ...)``: ``chains`` chains in the whitened variable
+  xi (theta = center + transform^T xi, by default the Laplace mode and covariance factor of the same weighted posterior), a fixed
+  number of leapfrog steps, the step adapted per chain by dual averaging during the warm-up.  k points that fit the LDS of one
+  workgroup run as ONE launch with a workgroup per chain; more (the resident full data set) run as one log-joint pass over the
+  rows per leapfrog step for all chains, enqueued without host synchronisation.  The normal numbers come from the library's
+  counter-based generator (``_DeviceNormals``): a seed fixes the run.
+* ``log_joint_grad(family, pts, wts, thetas)``: the weighted log joint and its gradient for many parameter vectors at once
+  (model_lr.py:34-39, 59-64; model_poiss.py:40-46, 69-74) -- what the experiment's ``Fs`` metric is made of.
+
+This is fixed-length HMC, not NUTS, with a unit mass matrix in xi; logistic and Poisson only (the linreg / Gaussian posteriors
+are closed-form and sampled exactly by their own samplers), D <= 32.  There is no CPU fallback."""
+import importlib.util
+import os
+import time
+
+import numpy as np
+
+from .laplace_sampler import FAMILIES, LaplacePosteriorSampler
+from .linreg_sampler import _DeviceNormals
+
+DMAX = 32
+STREAM_CHAINS_MAX = 256
+DIAG = 6
+
+
+def _example_model(family):
+    path = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples", "common",
+                        "model_lr.py" if family == "logistic" else "model_poiss.py")
+    if not os.path.exists(path):
+        raise ValueError("DeviceHMC: no default center / transform for this many points without the example models (%s); pass "
+                         "center= and transform=" % path)
+    spec = importlib.util.spec_from_file_location("_bcx_hmc_" + os.path.basename(path)[:-3], path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def split_rhat(x):
+    """Split-R-hat per coordinate of x (chains x draws x D): every chain cut into halves (Gelman et al., BDA3 section 11.4)."""
+    x = np.asarray(x, dtype=np.float64)
+    C, T, D = x.shape
+    h = T // 2
+    if h < 2:
+        return np.full(D, np.nan)
+    y = np.concatenate((x[:, :h], x[:, T - h:]), axis=0)
+    W = y.var(axis=1, ddof=1).mean(axis=0)
+    B = h * y.mean(axis=1).var(axis=0, ddof=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.sqrt(((h - 1.0) / h * W + B / h) / W)
+
+
+class HMCResult(object):
+    """``samples`` (chains, n_samples, D); ``accept_rate`` / ``step_size`` (chains); ``delta_h`` / ``accepted`` (chains,
+    n_samples); ``rhat`` (D); ``seconds_per_iteration`` (wall time of the run over warm-up + sampling transitions); ``streamed``
+    (the path taken); ``center`` / ``transform``; ``trace`` (``keep_trace=True``: every transition, warm-up included)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _device_rows(torch, device, pts, cols, what):
+    if isinstance(pts, torch.Tensor):
+        t = pts.to(device=device, dtype=torch.float64)
+        if t.dim() != 2 or t.stride(1) != 1:
+            t = t.reshape(t.shape[0], -1).contiguous()
+    else:
+        t = torch.from_numpy(np.ascontiguousarray(np.atleast_2d(np.asarray(pts, dtype=np.float64)))).to(device)
+    if t.shape[1] != cols:
+        raise ValueError("%s have %d columns, the model takes %d" % (what, t.shape[1], cols))
+    return t
+
+
+def log_joint_grad(family, pts, wts, thetas, device="cuda"):
+    """(values (C), gradients (C x D)) of the weighted log joint at the rows of ``thetas`` -- ndarrays, or device tensors when
+    ``thetas`` is one.  ``pts``: rows y x (logistic) or [x, y] (Poisson), host array or device tensor; ``wts=None``: ones."""
+    import torch
+    from . import _native
+    if family not in FAMILIES:
+        raise ValueError("family must be 'logistic' or 'poisson'")
+    if not torch.cuda.is_available():
+        raise RuntimeError("log_joint_grad needs a GPU (there is no CPU fallback)")
+    lib = _native.load()
+    as_tensor = isinstance(thetas, torch.Tensor)
+    if isinstance(pts, torch.Tensor) and pts.is_cuda:
+        device = pts.device
+    device = torch.device(device)
+    th = thetas.to(device=device, dtype=torch.float64) if as_tensor else \
+        torch.from_numpy(np.ascontiguousarray(np.atleast_2d(np.asarray(thetas, dtype=np.float64)))).to(device)
+    th = th.reshape(-1, th.shape[-1]).contiguous()
+    C, D = th.shape
+    if D < 1 or D > DMAX:
+        raise ValueError("log_joint_grad: D = %d parameters (1 <= D <= %d)" % (D, DMAX))
+    cols = D + (1 if family == "poisson" else 0)
+    N = 0 if pts is None else len(pts)
+    Z = _device_rows(torch, device, pts, cols, "points") if N else None
+    w = None
+    if wts is not None and N:
+        w = wts.to(device=device, dtype=torch.float64).contiguous() if isinstance(wts, torch.Tensor) else \
+            torch.from_numpy(np.ascontiguousarray(wts, dtype=np.float64)).to(device)
+        if w.shape != (N,):
+            raise ValueError("log_joint_grad: %d weights for %d points" % (w.numel(), N))
+    value = torch.empty(C, dtype=torch.float64, device=device)
+    grad = torch.empty(C, D, dtype=torch.float64, device=device)
+    work = torch.empty(max(int(lib.bcx_log_joint_grad_scratch_bytes(N, D, C)), 8) // 8, dtype=torch.float64, device=device)
+    with torch.cuda.device(device):
+        rc = lib.bcx_log_joint_grad(int(torch.cuda.current_stream(device).cuda_stream), FAMILIES[family], Z.data_ptr() if N else None, N,
+                                    Z.stride(0) if N else cols, D, w.data_ptr() if w is not None else None, th.data_ptr(), C, D,
+                                    value.data_ptr(), grad.data_ptr(), work.data_ptr())
+    if rc != 0:
+        raise _native.EngineError(rc, lib.bcx_project_last_error().decode())
+    if as_tensor:
+        return value, grad
+    return value.cpu().numpy(), grad.cpu().numpy()
+
+
+class DeviceHMC(_DeviceNormals):
+    STEP0 = 0.5        # the step the dual averaging starts from (the whitened target is near N(0, I))
+
+    def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda"):
+        import torch
+        from . import _native
+        if family not in FAMILIES:
+            raise ValueError("family must be 'logistic' or 'poisson'")
+        if not 1 <= int(D) <= DMAX:
+            raise ValueError("DeviceHMC: D = %d parameters (1 <= D <= %d)" % (D, DMAX))
+        if int(chains) < 1 or int(leapfrog) < 1:
+            raise ValueError("DeviceHMC: at least one chain and one leapfrog step")
+        self._torch, self._nat = torch, _native
+        self._lib = _native.load()
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeviceHMC needs a GPU (there is no CPU fallback)")
+        self.family, self._fam = family, FAMILIES[family]
+        self.device = torch.device(device)
+        self.D, self.chains, self.leapfrog = int(D), int(chains), int(leapfrog)
+        self.ld = self.D + (self.D % 2)
+        self.cols = self.D + (1 if family == "poisson" else 0)
+        self._seed, self._offset = (0 if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF, 0
+        self._seed_arg = seed
+        self._status = torch.zeros(2, dtype=torch.int32, device=self.device)
+
+    def coreset_path(self, k):
+        """Whether k points run on the LDS-resident path (one launch, a workgroup per chain)."""
+        return bool(self._lib.bcx_hmc_coreset_ok(int(k), self.D))
+
+    def _default_frame(self, k, pts, wts):
+        if k == 0:
+            return np.zeros(self.D), None
+        lap = LaplacePosteriorSampler(self.family, self.D, device=self.device, seed=self._seed_arg)
+        host_pts = pts.cpu().numpy() if isinstance(pts, self._torch.Tensor) else np.asarray(pts, dtype=np.float64)
+        host_w = None if wts is None else (wts.cpu().numpy() if isinstance(wts, self._torch.Tensor) else np.asarray(wts, dtype=np.float64))
+        if lap.supports(self.D + 1, k):
+            return lap.posterior(np.ones(k) if host_w is None else host_w, host_pts)
+        mod = _example_model(self.family)
+        mu, cov = mod.laplace_fit(host_pts, host_w)
+        return mu, np.linalg.cholesky(cov).T
+
+    def sample(self, pts, wts, n_samples, n_warmup=None, center=None, transform=None, keep_trace=False, _dev_step_size=None,
+               _dev_force_stream=False):
+        """``pts``: k rows (host array or device tensor; None / empty: the prior); ``wts``: k weights or None (ones);
+        ``n_warmup`` defaults to ``n_samples`` (examples/common/mcmc.py:65).  ``center`` (D) / ``transform`` (D x D, Sigma ~
+        transform^T transform) default to the Laplace fit of the same weighted posterior; ``transform=np.eye(D)``: plain HMC."""
+        torch, lib, D, C, ld = self._torch, self._lib, self.D, self.chains, self.ld
+        n_samples = int(n_samples)
+        n_warmup = n_samples if n_warmup is None else int(n_warmup)
+        if n_samples < 0 or n_warmup < 0 or n_samples + n_warmup < 1:
+            raise ValueError("DeviceHMC.sample: at least one transition")
+        T = n_samples + n_warmup
+        k = 0 if pts is None else len(pts)
+        Z = _device_rows(torch, self.device, pts, self.cols, "points") if k else None
+        w = None
+        if wts is not None and k:
+            w = wts.to(device=self.device, dtype=torch.float64).contiguous() if isinstance(wts, torch.Tensor) else \
+                torch.from_numpy(np.ascontiguousarray(wts, dtype=np.float64)).to(self.device)
+            if w.shape != (k,):
+                raise ValueError("DeviceHMC.sample: %d weights for %d points" % (w.numel(), k))
+        if center is None and transform is None:
+            center, transform = self._default_frame(k, pts, wts)
+        mu = np.zeros(D) if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(D)
+        Wm = None if transform is None else np.ascontiguousarray(transform, dtype=np.float64).reshape(D, D)
+        mu_dev = torch.from_numpy(mu).to(self.device)
+        W_dev = None if Wm is None else torch.from_numpy(Wm).to(self.device)
+        streamed = bool(_dev_force_stream) or not self.coreset_path(k)
+        if streamed and C > STREAM_CHAINS_MAX:
+            raise ValueError("DeviceHMC: the streamed path takes at most %d chains" % STREAM_CHAINS_MAX)
+        noise = self._normal(C, T, D + 3)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        samples = torch.empty(C, T, ld, **f64)
+        xis = torch.empty(C, T, ld, **f64) if keep_trace else None
+        props = torch.empty(C, T, ld, **f64) if keep_trace else None
+        diag = torch.empty(C, T, DIAG, **f64)
+        acc, eps = torch.empty(C, **f64), torch.empty(C, **f64)
+        ptr = lambda t: None if t is None else t.data_ptr()
+        common = [ptr(mu_dev), ptr(W_dev), D, C, n_warmup, n_samples, self.leapfrog, self.STEP0,
+                  0.0 if _dev_step_size is None else float(_dev_step_size), noise.data_ptr(), ld, samples.data_ptr(), ptr(xis), ptr(props),
+                  diag.data_ptr(), acc.data_ptr(), eps.data_ptr(), self._status.data_ptr()]
+        with torch.cuda.device(self.device):
+            stream = int(torch.cuda.current_stream(self.device).cuda_stream)
+            torch.cuda.synchronize(self.device)
+            t0 = time.perf_counter()
+            if streamed:
+                nbytes = int(lib.bcx_hmc_stream_scratch_bytes(k, D, C))
+                work = torch.empty(nbytes // 8 + 1, **f64)
+                rc = lib.bcx_hmc_stream(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, *(common + [work.data_ptr(), nbytes]))
+            else:
+                rc = lib.bcx_hmc_coreset(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, *common)
+            if rc != 0:
+                raise self._nat.EngineError(rc, lib.bcx_project_last_error().decode())
+            torch.cuda.synchronize(self.device)
+            seconds = time.perf_counter() - t0
+        st = self._status.cpu().numpy()
+        if st[0] == 2:
+            raise self._nat.EngineError(self._nat.ERR_STATE, "HMC on the device: the log joint at the start is not finite (NaN weights or points)")
+        out = samples[:, n_warmup:, :D].cpu().numpy()
+        dg = diag.cpu().numpy()
+        res = HMCResult(samples=out, accept_rate=acc.cpu().numpy(), step_size=eps.cpu().numpy(), delta_h=dg[:, n_warmup:, 0],
+                        accepted=dg[:, n_warmup:, 1] > 0.5, rhat=split_rhat(out) if n_samples >= 4 else np.full(D, np.nan),
+                        seconds_per_iteration=seconds / T, streamed=streamed, nonfinite_rejected=bool(st[0] == 1),
+                        center=mu, transform=np.eye(D) if Wm is None else Wm, n_warmup=n_warmup, trace=None)
+        if keep_trace:
+            res.trace = dict(noise=noise.cpu().numpy(), theta=samples[:, :, :D].cpu().numpy(), xi=xis[:, :, :D].cpu().numpy(),
+                             proposal=props[:, :, :D].cpu().numpy(), diag=dg, step0=self.STEP0)
+        return res

@@ -1,0 +1,24 @@
+"""MCMC for the experiments' evaluation: the role of the reference's examples/common/mcmc.py:60-70 (`run`: Stan on the data
+with per-point weights, as many warm-up as sampling iterations), on ``bc.DeviceHMC`` -- Hamiltonian Monte Carlo on the GPU,
+whitened by the Laplace approximation of the same weighted posterior."""
+import numpy as np
+
+FAMILY = {"lr": "logistic", "poiss": "poisson"}
+MIN_WARMUP = 200
+
+
+def run(Z, wts, n_samples, model_name, seed, chains=64, leapfrog=8, device="cuda"):
+    """(samples (n_samples x D), seconds): ``n_samples`` draws from the posterior of the rows ``Z`` (host array or device
+    tensor, the model's layout; None / empty: the prior) with weights ``wts`` (None: ones), pooled over ``chains`` chains
+    that each warm up for as long as they sample (at least MIN_WARMUP transitions)."""
+    import bayesiancoresets_amd as bc
+    family = FAMILY[model_name]
+    k = 0 if Z is None else len(Z)
+    if k == 0:
+        raise ValueError("mcmc.run: no rows (the prior needs no sampler)")
+    D = Z.shape[1] - (1 if family == "poisson" else 0)
+    per_chain = -(-int(n_samples) // chains)
+    hmc = bc.DeviceHMC(family, D, chains=chains, leapfrog=leapfrog, seed=seed, device=device)
+    res = hmc.sample(Z, wts, per_chain, max(per_chain, MIN_WARMUP))
+    samples = res.samples.transpose(1, 0, 2).reshape(-1, D)[:int(n_samples)]
+    return samples, res.seconds_per_iteration * (per_chain + res.n_warmup)

@@ -21,6 +21,23 @@ def log_likelihood(z, th):
     return out
 
 
+def log_joint(z, th, wts):
+    """sum_j w_j log p(z_j | theta) + log p(theta) for every row of ``th`` (model_lr.py:34-39): the host statement of
+    ``bc.log_joint_grad``'s values."""
+    th = np.atleast_2d(th)
+    prior = -0.5 * th.shape[1] * np.log(2.0 * np.pi) - 0.5 * (th ** 2).sum(axis=1)
+    return (np.asarray(wts)[:, None] * log_likelihood(z, th)).sum(axis=0) + prior
+
+
+def grad_th_log_joint(z, th, wts):
+    """Its gradient in theta, C x D (model_lr.py:41-48, 59-64): sum_j w_j sigmoid(-z_j.theta) z_j - theta."""
+    z, th = np.atleast_2d(z), np.atleast_2d(th)
+    arg = -z.dot(th.T)
+    e = np.exp(np.minimum(arg, 100.0))
+    s = np.where(arg < 100, e / (1.0 + e), 1.0)
+    return (np.asarray(wts)[:, None] * s).T.dot(z) - th
+
+
 def _matvec(xp, Z, th):
     # row-wise dot products as an elementwise product + sum: D is ~10, and this keeps the device path free of any
     # BLAS call (a 1M x 10 GEMV / GEMM through a vendor library costs more in set-up than the arithmetic is worth)

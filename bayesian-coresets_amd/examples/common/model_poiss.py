@@ -45,6 +45,22 @@ def _derivs(s, y):
     return g, h
 
 
+def log_joint(z, th, wts):
+    """sum_j w_j log p(z_j | theta) + log p(theta) for every row of ``th`` (model_poiss.py:40-46; -log y! kept): the host
+    statement of ``bc.log_joint_grad``'s values."""
+    th = np.atleast_2d(th)
+    prior = -0.5 * th.shape[1] * np.log(2.0 * np.pi) - 0.5 * (th ** 2).sum(axis=1)
+    return (np.asarray(wts)[:, None] * log_likelihood(z, th)).sum(axis=0) + prior
+
+
+def grad_th_log_joint(z, th, wts):
+    """Its gradient in theta, C x D (model_poiss.py:47-56, 69-74): sum_j w_j (y_j rate'/rate - rate') x_j - theta."""
+    z, th = np.atleast_2d(z), np.atleast_2d(th)
+    x = z[:, :-1]
+    g, _ = _derivs(x.dot(th.T), z[:, -1][:, None])
+    return (np.asarray(wts)[:, None] * g).T.dot(x) - th
+
+
 def laplace_fit(Z, wts=None, mu0=None, tol=1e-10, max_iter=200):
     """(mu, cov) of the Laplace approximation to the (weighted) posterior."""
     Z = np.atleast_2d(np.asarray(Z, dtype=np.float64))

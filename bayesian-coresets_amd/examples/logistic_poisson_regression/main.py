@@ -12,9 +12,13 @@ incremental build over the size schedule, and `US` as the uniform baseline.  The
 (bc.DeviceProjector "logistic" / "poisson"), the greedy construction on the device engine.
 `--dataset synth_lr | synth_poiss` generates the data (`--data_num` rows, `--data_dim` columns); a path to an .npz with
 arrays X, y (the reference's data/*.npz layout, last column of X the intercept) is standardised as load_data does.
-The reference evaluates a coreset by Stan MCMC on it (pystan: not available here, and not on the path this repository
-is about); this harness reports the same metric columns -- reverse / forward KL to the full-data posterior, relative errors
-of mean and covariance -- between the LAPLACE approximations of the coreset posterior and of the full-data posterior."""
+The reference evaluates a coreset by Stan MCMC on it (main.py:107-127, 205-232).  `--eval laplace` (the default) reports the
+metric columns -- reverse / forward KL to the full-data posterior, relative errors of mean and covariance -- between the
+LAPLACE approximations of the coreset posterior and of the full-data posterior.  `--eval mcmc` samples both posteriors with
+bc.DeviceHMC (examples/common/mcmc.py; `--mcmc_samples_full` / `--mcmc_samples_coreset` draws, the full-data draws cached under
+<results_folder>/mcmc_cache), takes the Gaussian moments of the draws for the same columns and adds the reference's others: `Fs`
+(the mean squared difference of the coreset's and the full data's log-joint gradients over the full-data draws, two
+bc.log_joint_grad calls), `full_mcmc_time_per_itr`, `mcmc_time_per_itr`."""
 import argparse
 import os
 import sys
@@ -26,6 +30,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, os.path.join(HERE, "..", ".."))
 sys.path.insert(1, os.path.join(HERE, "..", "common"))
 import results  # noqa: E402
+import mcmc  # noqa: E402
 import model_lr  # noqa: E402
 import model_poiss  # noqa: E402
 
@@ -50,7 +55,25 @@ def load(a, rs):
     return model_poiss.synthetic_rows(a.data_num, a.data_dim, rs)
 
 
+def full_data_samples(a, Z):
+    """The full-data draws and the sampler's time per iteration, cached per model / data set / trial (main.py:107-127)."""
+    folder = os.path.join(a.results_folder, "mcmc_cache")
+    name = "full_samples_%s_%s_%d_%d_%d_%d.npz" % (a.model, os.path.basename(a.dataset), a.data_num, a.data_dim, a.trial, a.mcmc_samples_full)
+    path = os.path.join(folder, name)
+    if os.path.exists(path):
+        d = np.load(path)
+        return d["samples"], float(d["t"])
+    samples, t = mcmc.run(Z, None, a.mcmc_samples_full, a.model, a.trial)
+    t_per_itr = t / (a.mcmc_samples_full * 2)                                  # (main.py:123-124: warm-up = sampling)
+    os.makedirs(folder, exist_ok=True)
+    np.savez(path, samples=samples, t=t_per_itr)
+    return samples, t_per_itr
+
+
 def run(a):
+    use_mcmc = getattr(a, "eval", "laplace") == "mcmc"
+    if not use_mcmc and hasattr(a, "eval"):
+        delattr(a, "eval")              # (the default evaluation's result files keep the argument set they always had)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
         print("Quitting.")
@@ -106,6 +129,13 @@ def run(a):
     }
     alg = build[a.alg]()
     n = Ms.shape[0]
+    extra = {}
+    if use_mcmc:
+        full_samples, full_t = full_data_samples(a, Z)
+        mup, Sigp = full_samples.mean(axis=0), np.cov(full_samples, rowvar=False)     # main.py:137-138
+        SigpInv = np.linalg.inv(Sigp)
+        _, gfs = bc.log_joint_grad(family, Z, None, full_samples)
+        extra = dict(Fs=np.zeros(n), full_mcmc_time_per_itr=np.full(n, full_t), mcmc_time_per_itr=np.zeros(n))
     cputs, walls, csizes = np.zeros(n), np.zeros(n), np.zeros(n)
     rklw, fklw, mu_errs, Sig_errs = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
     for m in range(n):
@@ -116,7 +146,16 @@ def run(a):
         walls[m] = time.perf_counter() - t0 + (walls[m - 1] if m else 0.0)
         wts, pts, idcs = alg.get()
         csizes[m] = (wts > 0).sum()
-        if csizes[m] > 0:
+        if use_mcmc:
+            if csizes[m] > 0:
+                cst, t_cst = mcmc.run(pts[wts > 0], wts[wts > 0], a.mcmc_samples_coreset, a.model, a.trial)
+            else:
+                cst, t_cst = np.random.RandomState(a.trial).randn(a.mcmc_samples_coreset, D), 0.0      # the prior
+            muw, Sigw = cst.mean(axis=0), np.cov(cst, rowvar=False)
+            _, gcs = bc.log_joint_grad(family, pts[wts > 0], wts[wts > 0], full_samples)
+            extra["Fs"][m] = ((gcs - gfs) ** 2).sum(axis=1).mean()              # main.py:226-228
+            extra["mcmc_time_per_itr"][m] = t_cst / (a.mcmc_samples_coreset * 2)
+        elif csizes[m] > 0:
             muw, Sigw = laplace(pts[wts > 0], wts[wts > 0])
         else:
             muw, Sigw = np.zeros(D), np.eye(D)
@@ -126,7 +165,7 @@ def run(a):
         Sig_errs[m] = np.sqrt(((Sigp - Sigw) ** 2).sum()) / np.sqrt((Sigp ** 2).sum())
     print("final: csize %d, reverse KL %.6g, forward KL %.6g, %.2f s wall" % (csizes[-1], rklw[-1], fklw[-1], walls[-1]))
     results.save(a, a.results_folder, csizes=csizes, Ms=Ms, cputs=cputs, walls=walls, rklw=rklw, fklw=fklw, mu_errs=mu_errs,
-                 Sig_errs=Sig_errs)
+                 Sig_errs=Sig_errs, **extra)
 
 
 def parser():
@@ -139,8 +178,10 @@ def parser():
     ap.add_argument("--data_num", type=int, default=10000)
     ap.add_argument("--data_dim", type=int, default=3)
     ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "GIGA-OPT", "GIGA-REAL", "US"])
-    ap.add_argument("--mcmc_samples_full", type=int, default=10000, help="accepted for command-line compatibility; unused (no MCMC evaluation)")
-    ap.add_argument("--mcmc_samples_coreset", type=int, default=10000, help="accepted for command-line compatibility; unused")
+    ap.add_argument("--mcmc_samples_full", type=int, default=10000, help="--eval mcmc: draws from the full-data posterior")
+    ap.add_argument("--mcmc_samples_coreset", type=int, default=10000, help="--eval mcmc: draws from every coreset's posterior")
+    ap.add_argument("--eval", type=str, choices=["laplace", "mcmc"], default="laplace",
+                    help="score a coreset by the Laplace approximation of its posterior, or by HMC on it (bc.DeviceHMC)")
     ap.add_argument("--proj_dim", type=int, default=500)
     ap.add_argument("--coreset_size_max", type=int, default=1000)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)

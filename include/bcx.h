@@ -515,6 +515,46 @@ int bcx_psvi_gradient_gaussian(void* stream, const void* operand_dev, int32_t S,
 int bcx_psvi_adam_step(void* stream, int32_t k, int32_t d, const void* grad_dev, int32_t S, void* w_dev, void* P_dev, int64_t ldp,
                        void* mom1_dev, void* mom2_dev, const void* sched_dev, int32_t step, double b1, double b2, double eps,
                        void* XT_dev, int64_t ldk, void* y_dev, void* trace_dev);
+/* The weighted log joint of the logistic / Poisson regression models and its gradient for C parameter vectors at once
+ * (examples/common/model_lr.py:34-39, 59-64; model_poiss.py:40-46, 69-74, prior constant and the Poisson -log y! included):
+ *     value_dev[c] = sum_j w_j log p(z_j | theta_c) - |theta_c|^2 / 2 - D/2 log 2 pi,   grad_dev[c] (row stride ldt) its gradient.
+ * Z_dev: N x ldz rows as bcx_laplace_sampler reads them (logistic y x, Poisson [x, y]); w_dev: N weights or NULL (ones);
+ * Theta_dev: C x ldt.  Any N >= 0 and C >= 1, D <= 32.  work_dev: bcx_log_joint_grad_scratch_bytes(N, D, C) bytes (-1: out of
+ * range).  Per-workgroup partial sums in a fixed order and a fixed-order second level (csrc/hmc.hip), no floating-point
+ * atomics: the same inputs give the same bits.  Asynchronous on `stream`. */
+int64_t bcx_log_joint_grad_scratch_bytes(int64_t N, int32_t D, int32_t C);
+int bcx_log_joint_grad(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D, const void* w_dev,
+                       const void* Theta_dev, int32_t C, int32_t ldt, void* value_dev, void* grad_dev, void* work_dev);
+/* Hamiltonian Monte Carlo on the weighted posterior of k points -- the evaluation of the reference's logistic / Poisson
+ * experiment (examples/logistic_poisson_regression/main.py:107-127, 205-232 and examples/common/mcmc.py:60-70 run Stan with
+ * 'w': wts; this is HMC with a fixed number of leapfrog steps, not NUTS).  `chains` chains move in xi with theta = mu + W^T xi
+ * (mu_dev: D or NULL = 0; W_dev: D x D, row stride ldw, or NULL = identity), unit mass matrix, from xi = 0, for n_warmup +
+ * n_samples = T transitions.  Transition t of chain c reads the D + 3 standard normals noise_dev[(c T + t)(D + 3) ..]: D momenta,
+ * two for the accept threshold e = (z1^2 + z2^2) / 2 (accept iff dH <= e), one for the step jitter eps_t = eps exp(0.1 z).  The
+ * warm-up adapts eps per chain from eps0 by dual averaging (Hoffman & Gelman 2014, Alg. 5: delta 0.8, gamma 0.05, t0 10,
+ * kappa 0.75); sampling uses the averaged step.  fixed_eps > 0 (a development argument): that base step throughout, no adaptation.
+ * Outputs: samples_dev (chains x T x ld, theta after every transition, warm-up included); xi_dev / prop_dev (the same shape, or
+ * NULL: the states and the proposals in xi); diag_dev (chains x T x 6: dH, accepted, eps_t, the next transition's base step,
+ * the dual-averaging Hbar and log eps-bar); accept_dev (chains: the accept rate of the sampling transitions); eps_dev (chains:
+ * their base step); status_dev (2 int32): [0] of this call 0 ok / 1 a non-finite dH was rejected / 2 the log joint at the start
+ * is not finite (NaN weights or points: nothing is scrubbed), [1] the worst [0] since the caller zeroed it.
+ * bcx_hmc_coreset: ONE launch, a workgroup per chain, the points in LDS -- the (k, D) for which bcx_hmc_coreset_ok is non-zero
+ * (D <= 32, bcx_hmc_coreset_lds_bytes within the LDS the device gives a workgroup less the kernel's own).
+ * bcx_hmc_stream: any N (the full data set), at most 256 chains: every leapfrog step is one bcx_log_joint_grad-shaped pass over
+ * the rows for all chains and a small kernel per chain; enqueued on `stream` without host synchronisation; work_dev:
+ * bcx_hmc_stream_scratch_bytes(N, D, chains) bytes.  The two run the same transition text and agree to rounding. */
+int bcx_hmc_coreset_ok(int32_t k, int32_t D);
+int64_t bcx_hmc_coreset_lds_bytes(int32_t k, int32_t D);
+int bcx_hmc_coreset(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                    const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                    int32_t leapfrog, double eps0, double fixed_eps, const void* noise_dev, int32_t ld, void* samples_dev,
+                    void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev);
+int64_t bcx_hmc_stream_scratch_bytes(int64_t N, int32_t D, int32_t chains);
+int bcx_hmc_stream(void* stream, int32_t family, int64_t N, int32_t D, const void* w_dev, const void* Z_dev, int64_t ldz,
+                   const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                   int32_t leapfrog, double eps0, double fixed_eps, const void* noise_dev, int32_t ld, void* samples_dev,
+                   void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev, void* work_dev,
+                   int64_t work_bytes);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 

@@ -1,0 +1,110 @@
+"""Dev tool: time of the device HMC (bc.DeviceHMC, csrc/hmc.hip) per leapfrog step and per transition, and effective samples
+per second -- coreset path at k in {30, 300, 1000}, D = 10, 64 and 256 chains; streamed path at N = 1M, D = 10, 64 chains -- next
+to the NumPy restatement's time per transition on the host (tests/hmc_restatement.py) and the log-joint pass against its
+fp64-VALU model.  One JSON line per case.
+
+    python tools/hmc_bench.py [--quick]
+"""
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "bayesian-coresets_amd"), os.path.join(ROOT, "bayesian-coresets_amd", "examples", "common"),
+          os.path.join(ROOT, "tests")):
+    sys.path.insert(0, p)
+
+import hmc_restatement as hr  # noqa: E402
+import model_lr  # noqa: E402
+
+L = 8
+
+
+def ess_per_chain(x):
+    """Effective sample size of one coordinate of one chain by the initial positive sequence of its autocorrelations."""
+    x = x - x.mean()
+    n = x.shape[0]
+    f = np.fft.rfft(x, 2 * n)
+    ac = np.fft.irfft(f * np.conj(f))[:n]
+    ac /= ac[0]
+    s = 0.0
+    for t in range(1, n - 1, 2):
+        pair = ac[t] + ac[t + 1]
+        if pair < 0:
+            break
+        s += pair
+    return n / (1.0 + 2.0 * s)
+
+
+def data(n, d, rs):
+    X = np.hstack((rs.randn(n, d - 1), np.ones((n, 1))))
+    y = np.where(rs.rand(n) < 1 / (1 + np.exp(-X.dot(np.ones(d) / np.sqrt(d)))), 1.0, -1.0)
+    return y[:, None] * X
+
+
+def case(bc, torch, name, pts, wts, chains, n, center=None, transform=None):
+    D = pts.shape[1]
+    hmc = bc.DeviceHMC("logistic", D, chains=chains, leapfrog=L, seed=1)
+    hmc.sample(pts, wts, 10, 10, center=center, transform=transform)               # (first-use costs)
+    res = hmc.sample(pts, wts, n, n, center=center, transform=transform)
+    per_tr = res.seconds_per_iteration
+    ess = np.mean([ess_per_chain(res.samples[c, :, j]) for c in range(min(chains, 16)) for j in range(D)]) * chains
+    out = dict(case=name, path="streamed" if res.streamed else "coreset", k=int(pts.shape[0]), D=D, chains=chains,
+               us_per_transition=per_tr * 1e6, us_per_leapfrog=per_tr * 1e6 / L, us_per_transition_per_chain=per_tr * 1e6 / chains,
+               accept=float(res.accept_rate.mean()), step=float(res.step_size.mean()), rhat_max=float(np.nanmax(res.rhat)),
+               ess_per_second=float(ess / (per_tr * 2 * n)))
+    print(json.dumps(out), flush=True)
+    return res
+
+
+def host_baseline(pts, wts, center, transform, n=30):
+    D = pts.shape[1]
+    host = pts.cpu().numpy() if hasattr(pts, "cpu") else pts
+    tgt = hr.Target("logistic", host, wts, D, center, transform)
+    z = np.random.RandomState(0).randn(n, D + 3)
+    t0 = time.perf_counter()
+    hr.run_chain(tgt, z, n, L, 0.5)
+    return (time.perf_counter() - t0) / n
+
+
+def main():
+    import torch
+    import bayesiancoresets_amd as bc
+    quick = "--quick" in sys.argv
+    rs = np.random.RandomState(0)
+    D = 10
+    for k in (30, 300, 1000):
+        pts, wts = data(k, D, rs), rs.uniform(1.0, 50.0, k)
+        mu, cov = model_lr.laplace_fit(pts, wts)
+        W = np.linalg.cholesky(cov).T
+        host = host_baseline(pts, wts, mu, W)
+        for chains in (64, 256):
+            case(bc, torch, "coreset k=%d" % k, pts, wts, chains, 100 if quick else 500, mu, W)
+        print(json.dumps(dict(case="host restatement k=%d" % k, us_per_transition_per_chain=host * 1e6)), flush=True)
+    N = 100000 if quick else 1000000
+    Z = torch.from_numpy(data(N, D, rs)).cuda()
+    mu, cov = model_lr.laplace_fit(Z)
+    W = np.linalg.cholesky(cov).T
+    case(bc, torch, "streamed N=%d" % N, Z, None, 64, 20 if quick else 100, mu, W)
+    print(json.dumps(dict(case="host restatement N=%d" % N, us_per_transition_per_chain=host_baseline(Z, None, mu, W, 3) * 1e6)), flush=True)
+    # the log-joint pass alone against its model: C x N evaluations of ~100 fp64 VALU operations (exp, log1p, two
+    # divisions) plus 2 D multiply-adds each, on 256 CUs x 4 SIMDs x 16 fp64 lanes per clock at 2.4 GHz
+    th = torch.from_numpy(mu + 0.1 * rs.randn(64, D)).cuda()
+    bc.log_joint_grad("logistic", Z, None, th)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    reps = 5
+    for _ in range(reps):
+        bc.log_joint_grad("logistic", Z, None, th)
+    torch.cuda.synchronize()
+    dt = (time.perf_counter() - t0) / reps
+    ops = 64.0 * N * (100 + 2 * D)
+    bound = ops / (256 * 4 * 16 * 2.4e9)
+    print(json.dumps(dict(case="log_joint_grad N=%d C=64" % N, us=dt * 1e6, valu_model_us=bound * 1e6, fraction_of_model=bound / dt)), flush=True)
+
+
+if __name__ == "__main__":
+    main()
