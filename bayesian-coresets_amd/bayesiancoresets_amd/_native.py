@@ -48,6 +48,7 @@ SYMBOLS = (
     "bcx_project_colsum_rows", "bcx_project_select_rows_ws", "bcx_project_select_rows_scratch_bytes", "bcx_gather_rows",
     "bcx_log_joint_grad", "bcx_log_joint_grad_scratch_bytes", "bcx_hmc_coreset", "bcx_hmc_coreset_ok", "bcx_hmc_coreset_lds_bytes",
     "bcx_hmc_stream", "bcx_hmc_stream_scratch_bytes",
+    "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
 )
 
 
@@ -188,6 +189,9 @@ def load():
     sigs["bcx_laplace_sampler_ok"] = [i32, i32]
     lib.bcx_laplace_sampler_lds_bytes.restype = ctypes.c_int64
     lib.bcx_laplace_sampler_lds_bytes.argtypes = [i32, i32]
+    sigs["bcx_laplace_sampler_stream"] = sigs["bcx_laplace_sampler"] + [vp, i64]
+    lib.bcx_laplace_stream_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_laplace_stream_scratch_bytes.argtypes = [i32, i32]
     sigs["bcx_row_sumsq"] = [vp, vp, i64, i32, i64, vp]
     sigs["bcx_project_grad_points"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp]
     sigs["bcx_psvi_gradient"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp, i64, vp, dbl, vp, vp]

@@ -14,7 +14,13 @@ in-register Cholesky, then the draws mu + R L^-1); the normal numbers come from 
 reference finds the mode with SciPy's BFGS to gtol 1e-5; this is Newton to |step| < 1e-10 on the same objective (the
 iteration of examples/common/model_lr.py / model_poiss.py ``laplace_fit``, which the tests pin to the reference's outputs).
 Limits: D <= 32 parameters, the points within 96 KiB of LDS (``supports``); beyond them ``enqueue_plan`` declines (the host
-loop then runs) and the call form raises.  There is no CPU fallback."""
+loop then runs) and the call form raises.  There is no CPU fallback.
+
+``stream=True`` lifts the limit on the points: beyond it the fit is one persistent launch of up to a workgroup per CU that
+streams the points from device memory (csrc/laplace_stream.hip: per pass one record of partial sums per workgroup, added in
+workgroup order behind a grid barrier; the same iteration, status word and outputs), any k.  ``posterior`` and the call form
+then also take the points as a DEVICE tensor (``wts=None``: ones) and read them where they are -- the resident full data set
+is fitted without a copy."""
 import numpy as np
 
 from .linreg_sampler import _DeviceNormals, _MovingPoints
@@ -26,7 +32,9 @@ class LaplacePosteriorSampler(_DeviceNormals):
     SMAX = 4096        # draws per call (DeviceProjector's own limit on the projection dimension)
     NOISE_BUDGET = 2 << 30
 
-    def __init__(self, family, D, device="cuda", seed=None, tol=1e-10, max_iter=100):
+    KMAX_STREAM = (1 << 31) - 1     # rows the streamed form takes (a 32-bit count in the ABI)
+
+    def __init__(self, family, D, device="cuda", seed=None, tol=1e-10, max_iter=100, *, stream=False):
         import torch
         from . import _native
         if family not in FAMILIES:
@@ -48,9 +56,25 @@ class LaplacePosteriorSampler(_DeviceNormals):
         self._none = torch.zeros(2, dtype=torch.float64, device=self.device)
         self._theta = {}
         self._pts_key, self._pts_dev = None, None
+        self.stream = bool(stream)
+        self._dev_force_stream = False                      # tests: the streamed form where the LDS form applies too
+        self._work = None
 
     def supports(self, n, k):
+        if self.stream:
+            return 1 <= n <= self.SMAX and 0 <= int(k) <= self.KMAX_STREAM and 1 <= self.D <= 32
         return 1 <= n <= self.SMAX and bool(self._lib.bcx_laplace_sampler_ok(int(k), self.D))
+
+    def _streams(self, k):
+        """Whether k points go through csrc/laplace_stream.hip (only a ``stream=True`` sampler ever does)."""
+        return self.stream and (bool(self._dev_force_stream) or not self._lib.bcx_laplace_sampler_ok(int(k), self.D))
+
+    def _stream_work(self, k):
+        """A scratch buffer of the streamed form for k points (partial records + the barrier's counter)."""
+        need = int(self._lib.bcx_laplace_stream_scratch_bytes(int(k), self.D))
+        if need < 0:
+            raise ValueError("LaplacePosteriorSampler: no streamed fit for %d points of %d parameters" % (k, self.D))
+        return self._torch.zeros((need + 7) // 8, dtype=self._torch.float64, device=self.device)
 
     def _theta_buf(self, n):
         t = self._theta.get(n)
@@ -67,11 +91,31 @@ class LaplacePosteriorSampler(_DeviceNormals):
             self._pts_dev = self._torch.from_numpy(np.ascontiguousarray(pts)).to(self.device)
         return self._pts_dev
 
-    def _args(self, k, w_dev, pts_dev, warm, R, rbar, theta):
+    def _device_points(self, pts):
+        """A device tensor of points as the kernels read it: fp64 rows of ``cols`` values with unit column stride, used in place
+        (its row stride may exceed ``cols``: a view of wider rows)."""
+        torch = self._torch
+        if pts.dim() != 2 or pts.shape[1] != self.cols:
+            raise ValueError("points are %s, the %s model takes rows of %d columns" % (tuple(pts.shape), self.family, self.cols))
+        if pts.dtype != torch.float64 or pts.device != self._mu.device or (pts.shape[0] > 1 and pts.stride(0) < self.cols) or \
+                (pts.shape[1] > 1 and pts.stride(1) != 1):
+            pts = pts.to(device=self.device, dtype=torch.float64).contiguous()
+        return pts
+
+    def _args(self, k, w_dev, pts_dev, warm, R, rbar, theta, work=None):
+        """Argument list of bcx_laplace_sampler, or -- with a scratch buffer -- of bcx_laplace_sampler_stream (``_fn``)."""
         stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-        return [stream, self._fam, k, self.D, w_dev.data_ptr() if k else None, pts_dev.data_ptr() if k else None, self.cols,
-                self._mu.data_ptr(), int(warm), self.tol, self.max_iter, R.data_ptr(), rbar.data_ptr(), theta.shape[0], self.ld,
-                theta.data_ptr(), self._tbar.data_ptr(), self._status.data_ptr()]
+        a = [stream, self._fam, k, self.D, w_dev.data_ptr() if k else None, pts_dev.data_ptr() if k else None, self.cols,
+             self._mu.data_ptr(), int(warm), self.tol, self.max_iter, R.data_ptr(), rbar.data_ptr(), theta.shape[0], self.ld,
+             theta.data_ptr(), self._tbar.data_ptr(), self._status.data_ptr()]
+        if k:
+            a[6] = max(a[6], pts_dev.stride(0))             # (the row stride: the points may be a view of padded rows)
+        if work is not None:
+            a += [work.data_ptr(), work.numel() * 8]
+        return a
+
+    def _fn(self, work):
+        return self._lib.bcx_laplace_sampler if work is None else self._lib.bcx_laplace_sampler_stream
 
     def check(self, worst=False):
         """Synchronises; raises if the last fit (``worst``: any fit since the word was zeroed -- a plan zeroes it when it starts)
@@ -80,6 +124,9 @@ class LaplacePosteriorSampler(_DeviceNormals):
         st = self._status.cpu().numpy()
         v = st[2] if worst else st[0]
         if v != 0:
+            if v == 3:
+                raise self._nat.EngineError(self._nat.ERR_TIMEOUT, "Laplace fit on the device: a wait between the workgroups of the "
+                                            "streamed fit expired%s" % (" at a step of the loop" if worst else ""))
             raise self._nat.EngineError(self._nat.ERR_STATE, "Laplace fit on the device: %s%s"
                                         % ("iteration limit" if v == 1 else "no positive definite Newton matrix",
                                            " at a step of the loop" if worst else " after %d Newton steps" % int(st[1])))
@@ -88,19 +135,35 @@ class LaplacePosteriorSampler(_DeviceNormals):
     # -- the reference's sampler signature --------------------------------------------------------------------------------------
     def __call__(self, n, wts, pts):
         torch = self._torch
-        k = 0 if wts is None or pts is None else len(wts)
-        if k and np.asarray(pts).size == 0:
-            k = 0
+        on_device = isinstance(pts, torch.Tensor)           # the points where they are (wts None: ones); never brought to the host
+        if on_device:
+            k = int(pts.shape[0]) if pts.dim() == 2 and pts.numel() else 0
+        else:
+            k = 0 if wts is None or pts is None else len(wts)
+            if k and np.asarray(pts).size == 0:
+                k = 0
         if not self.supports(n, k):
             raise ValueError("LaplacePosteriorSampler: %d draws for %d weighted points of %d parameters (D <= 32, the points within "
-                             "96 KiB of LDS, at most %d draws)" % (n, k, self.D, self.SMAX))
+                             "96 KiB of LDS unless stream=True, at most %d draws)" % (n, k, self.D, self.SMAX))
         pts_dev, w_dev = None, self._none
         if k:
-            pts_dev = self._points(pts)
-            w_dev = torch.from_numpy(np.ascontiguousarray(wts, dtype=np.float64)).to(self.device)
+            pts_dev = self._device_points(pts) if on_device else self._points(pts)
+            if wts is None:
+                w_dev = torch.ones(k, dtype=torch.float64, device=self.device)
+            elif isinstance(wts, torch.Tensor):
+                w_dev = wts.to(device=self.device, dtype=torch.float64).contiguous()
+            else:
+                w_dev = torch.from_numpy(np.ascontiguousarray(wts, dtype=np.float64)).to(self.device)
+            if w_dev.shape != (k,):
+                raise ValueError("LaplacePosteriorSampler: %d weights for %d points" % (w_dev.numel(), k))
         theta = self._theta_buf(n)
         R = self._noise(n)
-        rc = self._lib.bcx_laplace_sampler(*self._args(k, w_dev, pts_dev, False, R, self._column_means(R), theta))
+        work = None
+        if self._streams(k):
+            if self._work is None or self._work.numel() * 8 < int(self._lib.bcx_laplace_stream_scratch_bytes(k, self.D)):
+                self._work = self._stream_work(k)
+            work = self._work
+        rc = self._fn(work)(*self._args(k, w_dev, pts_dev, False, R, self._column_means(R), theta, work))
         if rc != 0:
             raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
         self.newton_steps = self.check()
@@ -108,7 +171,8 @@ class LaplacePosteriorSampler(_DeviceNormals):
         return theta[:, :self.D]
 
     def posterior(self, wts, pts):
-        """(mode, covariance factor W with Sigma = W^T W) as ndarrays: the rows of W come out as the draws of unit noise."""
+        """(mode, covariance factor W with Sigma = W^T W) as ndarrays: the rows of W come out as the draws of unit noise.
+        ``pts``: an array, or a device tensor that is read in place (then ``wts`` None: ones, or a tensor / array of k weights)."""
         torch = self._torch
         keep = self._noise
         try:
@@ -144,6 +208,8 @@ class _LaplacePlan(object):
     def __init__(self, sampler, n, pts_dev, noise):
         self.s, self.n, self.pts_dev = sampler, n, pts_dev
         self.theta = sampler._theta_buf(n)
+        # (the streamed form's scratch is the plan's own: its steps are enqueued behind one another on one stream)
+        self.work = sampler._stream_work(pts_dev.shape[0]) if sampler._streams(pts_dev.shape[0]) else None
         sampler._status[2].zero_()                          # (check() then covers every fit of this plan)
         self.set_noise(noise)
 
@@ -158,14 +224,13 @@ class _LaplacePlan(object):
         s = self.s
         a = self._a
         if a is None or self._w_ptr != w_dev.data_ptr():
-            a = self._a = s._args(self.pts_dev.shape[0], w_dev, self.pts_dev, False, self.noise, self.rbar, self.theta)
-            a[6] = max(a[6], self.pts_dev.stride(0))        # (the row stride: the points may be a view of padded rows)
+            a = self._a = s._args(self.pts_dev.shape[0], w_dev, self.pts_dev, False, self.noise, self.rbar, self.theta, self.work)
             self._w_ptr = w_dev.data_ptr()
             self._r0, self._rstep = self.noise.data_ptr(), self.noise.stride(0) * 8
             self._b0, self._bstep = self.rbar.data_ptr(), self.rbar.stride(0) * 8
         a[8] = 1 if i > 0 else 0                            # (warm: the mode of the previous ADAM step)
         a[11], a[12] = self._r0 + i * self._rstep, self._b0 + i * self._bstep
-        rc = s._lib.bcx_laplace_sampler(*a)
+        rc = s._fn(self.work)(*a)
         if rc != 0:
             raise s._nat.EngineError(rc, s._lib.bcx_project_last_error().decode())
         return self.buffers()

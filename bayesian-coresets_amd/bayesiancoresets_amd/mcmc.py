@@ -120,7 +120,7 @@ def log_joint_grad(family, pts, wts, thetas, device="cuda"):
 class DeviceHMC(_DeviceNormals):
     STEP0 = 0.5        # the step the dual averaging starts from (the whitened target is near N(0, I))
 
-    def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda"):
+    def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda", *, device_frame=False):
         import torch
         from . import _native
         if family not in FAMILIES:
@@ -140,15 +140,20 @@ class DeviceHMC(_DeviceNormals):
         self.cols = self.D + (1 if family == "poisson" else 0)
         self._seed, self._offset = (0 if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF, 0
         self._seed_arg = seed
+        self.device_frame = bool(device_frame)              # the default frame by a streamed Laplace fit of the points in place
         self._status = torch.zeros(2, dtype=torch.int32, device=self.device)
 
     def coreset_path(self, k):
         """Whether k points run on the LDS-resident path (one launch, a workgroup per chain)."""
         return bool(self._lib.bcx_hmc_coreset_ok(int(k), self.D))
 
-    def _default_frame(self, k, pts, wts):
+    def _default_frame(self, k, pts, wts, Z=None, w=None):
         if k == 0:
             return np.zeros(self.D), None
+        if self.device_frame and Z is not None:
+            # csrc/laplace_stream.hip on the device rows (any k): no download of the points, no host Newton iteration
+            lap = LaplacePosteriorSampler(self.family, self.D, device=self.device, seed=self._seed_arg, stream=True)
+            return lap.posterior(w, Z)
         lap = LaplacePosteriorSampler(self.family, self.D, device=self.device, seed=self._seed_arg)
         host_pts = pts.cpu().numpy() if isinstance(pts, self._torch.Tensor) else np.asarray(pts, dtype=np.float64)
         host_w = None if wts is None else (wts.cpu().numpy() if isinstance(wts, self._torch.Tensor) else np.asarray(wts, dtype=np.float64))
@@ -178,7 +183,7 @@ class DeviceHMC(_DeviceNormals):
             if w.shape != (k,):
                 raise ValueError("DeviceHMC.sample: %d weights for %d points" % (w.numel(), k))
         if center is None and transform is None:
-            center, transform = self._default_frame(k, pts, wts)
+            center, transform = self._default_frame(k, pts, wts, Z, w)
         mu = np.zeros(D) if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(D)
         Wm = None if transform is None else np.ascontiguousarray(transform, dtype=np.float64).reshape(D, D)
         mu_dev = torch.from_numpy(mu).to(self.device)

@@ -74,6 +74,7 @@ def run(a):
     use_mcmc = getattr(a, "eval", "laplace") == "mcmc"
     if not use_mcmc and hasattr(a, "eval"):
         delattr(a, "eval")              # (the default evaluation's result files keep the argument set they always had)
+    stream = bool(getattr(a, "laplace_stream", False))     # (absent unless given: the parser suppresses its default)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
         print("Quitting.")
@@ -95,10 +96,23 @@ def run(a):
             return model_lr.laplace_fit(pts, wts)
         return model_poiss.laplace_fit(pts, wts)
 
-    mup, Sigp = laplace(Z, None)                                               # main.py:145 (tangent space of GIGA-OPT)
+    # --laplace_stream: the SVI sampler streams the points beyond one workgroup's LDS (csrc/laplace_stream.hip), and the
+    # full-data and sub-sample fits run on the rows where they are resident, through the same sampler
+    fitter, Z_dev = None, None
+    if stream and D <= 32 and not getattr(a, "host_sampler", False):
+        import torch
+        fitter = bc.LaplacePosteriorSampler(family, D, seed=a.trial, stream=True)
+        Z_dev = torch.from_numpy(np.ascontiguousarray(Z, dtype=np.float64)).to(fitter.device)
+
+    def laplace_resident(rows):
+        mu, W = fitter.posterior(None, rows)
+        return mu, W.T.dot(W)
+
+    mup, Sigp = laplace(Z, None) if fitter is None else laplace_resident(Z_dev)   # main.py:145 (tangent space of GIGA-OPT)
     SigpInv = np.linalg.inv(Sigp)
-    Zhat = Z[np.random.randint(0, Z.shape[0], int(np.sqrt(Z.shape[0])))]      # main.py:150-152
-    muh, Sigh = laplace(Zhat, None)
+    hat = np.random.randint(0, Z.shape[0], int(np.sqrt(Z.shape[0])))
+    Zhat = Z[hat]                                                              # main.py:150-152
+    muh, Sigh = laplace(Zhat, None) if fitter is None else laplace_resident(Z_dev[torch.from_numpy(hat).to(Z_dev.device)])
     gauss = lambda mu, Sig: (lambda n, w, p: np.atleast_2d(np.random.multivariate_normal(mu, Sig, n)))
 
     def sampler_w(n, wts, pts):                                                # main.py:155-162
@@ -115,7 +129,7 @@ def run(a):
     sampler_host = sampler_w
     if D <= 32 and not getattr(a, "host_sampler", False):
         try:
-            sampler_w = bc.LaplacePosteriorSampler(family, D, seed=a.trial)
+            sampler_w = bc.LaplacePosteriorSampler(family, D, seed=a.trial, stream=stream)
         except RuntimeError:
             sampler_w = sampler_host
     dev = lambda sampler: bc.DeviceProjector(family, sampler, a.proj_dim)
@@ -193,6 +207,9 @@ def parser():
     ap.add_argument("--trial", type=int, default=1)
     ap.add_argument("--results_folder", type=str, default="results/")
     ap.add_argument("--verbosity", type=str, default="error", choices=["error", "warning", "critical", "info", "debug"])
+    ap.add_argument("--laplace_stream", action="store_true", default=argparse.SUPPRESS,     # (result files keep their argument set)
+                    help="SVI: bc.LaplacePosteriorSampler(stream=True) -- any coreset size on the device; the full-data and sub-sample "
+                         "Laplace fits on the resident rows through the same kernel")
     ap.add_argument("--host_sampler", action="store_true", help="SVI: the Laplace fit of every sampler call on the host (NumPy) instead of csrc/laplace.hip")
     return ap
 

@@ -407,6 +407,19 @@ int64_t bcx_laplace_sampler_lds_bytes(int32_t k, int32_t D);
 int bcx_laplace_sampler(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
                         void* mu_dev, int32_t warm, double tol, int32_t max_iter, const void* R_dev, const void* Rbar_dev,
                         int32_t S, int32_t ld, void* theta_dev, void* tbar_dev, void* status_dev);
+/* The same fit and draws for ANY k (the points beyond bcx_laplace_sampler_ok, the resident full data set): the points stay in
+ * device memory and are streamed by up to one workgroup per CU in ONE persistent launch (csrc/laplace_stream.hip); per pass
+ * every workgroup writes one record of partial sums, the records are added in workgroup order after a grid barrier (no
+ * floating-point atomics: a fit is bit-reproducible for a given (k, D) on a given device) and every workgroup takes the
+ * Newton step of bcx_laplace_sampler itself.  Same arguments, outputs and status word; status [0] / [2] = 3: a wait between
+ * the workgroups expired (GPU shared / preempted), the outputs are not valid.  work_dev: bcx_laplace_stream_scratch_bytes(k, D)
+ * bytes (-1: bad k / D), owned by the call until it has completed.  BCX_ERR_STATE when the device cannot hold the launch's
+ * workgroups together.  Asynchronous on `stream`. */
+int64_t bcx_laplace_stream_scratch_bytes(int32_t k, int32_t D);
+int bcx_laplace_sampler_stream(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                               void* mu_dev, int32_t warm, double tol, int32_t max_iter, const void* R_dev, const void* Rbar_dev,
+                               int32_t S, int32_t ld, void* theta_dev, void* tbar_dev, void* status_dev, void* work_dev,
+                               int64_t work_bytes);
 /* The dense re-weight's Gram matrix as an operator of its own (optimize() forms it over the active rows, snnls.py:82-97:
  * `nnls(A[:, active], b)` solves the normal equations of that k-column block): G_dev (k x ldg doubles, both triangles) =
  * V V^T for the k rows of d doubles at rows_dev (row stride ld >= d), on the fp64 matrix cores; the d products of an entry
