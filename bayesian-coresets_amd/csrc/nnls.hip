@@ -656,77 +656,7 @@ int bcx_launch_omp_fused(bcx_solver* s, int exact) {
   return rc;
 }
 
-// ---- optimize(): Gram matrix on the fp64 matrix cores + cold-start NNLS ---------------------------
-typedef double v4d __attribute__((ext_vector_type(4)));
-
-// G[i][j] = row_i . row_j for i, j < k on v_mfma_f64_16x16x4_f64.  A wave owns a 32 x 32 block of G (2 x 2 MFMA tiles)
-// and only blocks on or above the diagonal are computed, the mirror image is stored with them.  The four k-slots of an
-// MFMA step are fed in a permuted k order -- lane group lk supplies k = 8t + 2 lk (+1) to steps 2t (2t+1) -- so one
-// 16-byte load per operand tile feeds two steps: 4 loads per 8 MFMAs (round 1: one wave per 16 x 16 tile, 2 scalar
-// loads per MFMA, 7.8 TFLOP/s).  Rows are d doubles apart; 8-byte loads when d is odd.
-struct __attribute__((aligned(8))) gpd2 { double x, y; };
-__global__ __launch_bounds__(256) void gram_mfma_kernel(const double* __restrict__ rows, int k, int d,
-                                                        double* __restrict__ G, int64_t ldg, int nblk) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int li = lane & 15, lk = lane >> 4;
-  // upper-triangular block index -> (I, J), I <= J < nblk
-  int t = blockIdx.x * 4 + wave;
-  if (t >= nblk * (nblk + 1) / 2) return;
-  int I = 0;
-  while (t >= nblk - I) { t -= nblk - I; ++I; }
-  const int J = I + t;
-  const double* pa[2];
-  const double* pb[2];
-  bool va[2], vb[2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u) {
-    const int ri = I * 32 + 16 * u + li, rj = J * 32 + 16 * u + li;
-    va[u] = ri < k; vb[u] = rj < k;
-    pa[u] = rows + (size_t)(va[u] ? ri : 0) * d;
-    pb[u] = rows + (size_t)(vb[u] ? rj : 0) * d;
-  }
-  v4d acc[2][2];
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < 2; ++v) acc[u][v] = (v4d){0.0, 0.0, 0.0, 0.0};
-  const bool even = (d & 1) == 0;
-  for (int k0 = 0; k0 < d; k0 += 8) {
-    const int c = k0 + 2 * lk;
-    gpd2 av[2], bv[2];
-#pragma unroll
-    for (int u = 0; u < 2; ++u) {
-      if (even && c + 1 < d) { av[u] = *(const gpd2*)(pa[u] + c); bv[u] = *(const gpd2*)(pb[u] + c); }
-      else {
-        av[u].x = c < d ? pa[u][c] : 0.0; av[u].y = c + 1 < d ? pa[u][c + 1] : 0.0;
-        bv[u].x = c < d ? pb[u][c] : 0.0; bv[u].y = c + 1 < d ? pb[u][c + 1] : 0.0;
-      }
-      if (!va[u]) { av[u].x = 0.0; av[u].y = 0.0; }
-      if (!vb[u]) { bv[u].x = 0.0; bv[u].y = 0.0; }
-    }
-#pragma unroll
-    for (int u = 0; u < 2; ++u)
-#pragma unroll
-      for (int v = 0; v < 2; ++v) {
-        acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u].x, bv[v].x, acc[u][v], 0, 0, 0);
-        acc[u][v] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u].y, bv[v].y, acc[u][v], 0, 0, 0);
-      }
-  }
-  // f64 C/D layout: col = lane & 15, row = (lane >> 4) + 4 * reg
-#pragma unroll
-  for (int u = 0; u < 2; ++u)
-#pragma unroll
-    for (int v = 0; v < 2; ++v)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int row = I * 32 + 16 * u + lk + 4 * r, col = J * 32 + 16 * v + li;
-        if (row < k && col < k) {
-          G[(size_t)row * ldg + col] = acc[u][v][r];
-          if (I != J) G[(size_t)col * ldg + row] = acc[u][v][r];
-        }
-      }
-}
-
+// ---- optimize(): cold-start NNLS (the Gram matrix comes from moments.hip / gram.hip) ------------
 __global__ __launch_bounds__(NN_THREADS) void optimize_kernel(NnlsArgs n, double tol) {
   const ApplyArgs& a = n.a;
   DevState* st = a.st;
@@ -786,25 +716,16 @@ int bcx_launch_optimize(bcx_solver* s, double tol) {
     return BCX_OK;
   };
   if (k > 0) {
-    static const bool old_gram = bcx_dev_env("BCX_GRAM_DIRECT") != nullptr;     // dev: round 2's kernel (operands straight from L2)
     const int kp64 = (k + 63) / 64 * 64;       // (the warm start forms the inverse of a kp64 x kp64 block with the same kernel)
     const size_t need = std::max((size_t)bcx_gram_rows_scratch_bytes(k, s->cfg.d), (size_t)bcx_gram_rows_scratch_bytes(kp64, kp64));
-    if (!old_gram && s->gram_work_bytes < need) {
+    if (s->gram_work_bytes < need) {
       if (s->gram_work) BCX_HIP(hipFree(s->gram_work));
       s->gram_work = nullptr; s->gram_work_bytes = 0;
       BCX_HIP(hipMalloc((void**)&s->gram_work, need));
       s->gram_work_bytes = need;
     }
-    if (old_gram) {
-      const int nblk = (k + 31) / 32;
-      const int nwave = nblk * (nblk + 1) / 2;
-      hipLaunchKernelGGL(gram_mfma_kernel, dim3((nwave + 3) / 4), dim3(256), 0, s->stream, s->act_rows, k,
-                         s->cfg.d, s->gram, (int64_t)s->gram_cap, nblk);
-      BCX_HIP(hipGetLastError());
-    } else {
-      const int rc = bcx_gram_rows(s->stream, s->act_rows, k, s->cfg.d, (int64_t)s->cfg.d, s->gram, (int64_t)s->gram_cap, s->gram_work);
-      if (rc != BCX_OK) { s->err = "optimize: Gram kernel launch failed"; return rc; }
-    }
+    const int rc = bcx_gram_rows(s->stream, s->act_rows, k, s->cfg.d, (int64_t)s->cfg.d, s->gram, (int64_t)s->gram_cap, s->gram_work);
+    if (rc != BCX_OK) { s->err = "optimize: Gram kernel launch failed"; return rc; }
   }
   if (k > 0) {
     // incremental Lawson-Hanson on the double-double inverse (omp_lh.hip), started WARM from the largest independent part of

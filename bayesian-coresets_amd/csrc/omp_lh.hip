@@ -1130,8 +1130,8 @@ int bcx_launch_optimize_lh(bcx_solver* s, double tol, int k, const int32_t* warm
   gs.timeout_ticks = 1000000000LL;     // 10 s
   // The barriers of this kernel carry NO release / acquire fences (dev: BCX_GRID_FENCE=1 puts them back).  Everything that
   // crosses workgroups here is an exchange vector written write-through (sc1 stores, drained by every wave before its
-  // workgroup arrives: grid_publish) and read with sc1 loads after the wait -- the hand-off form csrc/lrpost.hip and
-  // csrc/persist.hip use -- and H is touched by its rows' owner waves only, so the fences order nothing that is read.  What
+  // workgroup arrives: grid_publish) and read with sc1 loads after the wait -- the hand-off form csrc/lrpost.hip
+  // uses -- and H is touched by its rows' owner waves only, so the fences order nothing that is read.  What
   // they cost is H: the release writes the XCD's dirty rows back (16 MB per pass over the inverse at k = 1024), the acquire
   // drops them from the L2 before the owner reads them again.  Measured (k = 1497, d = 1024, tools/optimize_ab.sh):
   // 64 workgroups x 1024 threads 36.3 ms with, 34.5 without; 128 x 512 26.7 with, 22.4 without (the phase clock: the barrier

@@ -389,7 +389,7 @@ static int launch_t(bcx_solver* s, const ScanArgs& a, int G, int CH, int UR, int
 }
 
 // Everything a scan launch is decided by (arguments, kernel variant, launch width): bcx_launch_scan below and the
-// several-iterations-per-launch form of persist.hip take the same plan.
+// 8-bit tier (screen8.hip, which takes the storage scan's error term from it) read the same plan.
 int bcx_scan_plan(bcx_solver* s, int exact, ScanArgs* ap, ScanPlan* pl) {
   ScanArgs& a = *ap;
   // storage fp64            : fp64 kernel over the normalised rows

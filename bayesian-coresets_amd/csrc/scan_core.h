@@ -1,6 +1,5 @@
-// scan_core.h -- the pieces of the correlation scan shared by scan.hip (one launch per greedy iteration) and persist.hip
-// (several iterations per launch): storage types, streaming loads, the cross-lane sums, the interval arithmetic, the
-// per-lane top-2 tracker and scan_body, one pass of a workgroup over its rows.
+// scan_core.h -- the pieces of the correlation scan shared by scan.hip and screen8.hip: storage types, streaming loads,
+// the cross-lane sums, the interval arithmetic and the per-lane top-2 tracker.
 #pragma once
 #include <stdlib.h>
 #include <math.h>
@@ -288,210 +287,4 @@ template <typename T> __device__ __forceinline__ void track_update(Track<T>& tr,
   tr.i1 = g1 ? ri : tr.i1;
   tr.U1 = g1 ? U : tr.U1;
   tr.L = L > tr.L ? L : tr.L;
-}
-
-// One pass of a workgroup over its rows (row block blk of nblk, grid stride) for persist.hip: scan_kernel's arithmetic, row
-// mapping and partials (scan.hip keeps its own text: the headline kernel's code does not change with this file), but the loads
-// of the first trip are issued before gate() -- which waits for this iteration's query and returns false when the state machine
-// has stopped -- and the query is fetched after it (sc1 loads; the partials leave as sc1 stores: no fences on this side).
-// Returns false when the gate or the state machine said stop (no partials written).
-template <typename ST, bool DUAL, int G, int CH, int UR, typename Gate>
-__device__ __forceinline__ bool scan_body(const ScanArgs& a, const unsigned blk, const unsigned nblk, Gate gate) {
-  typedef typename Stor<ST>::V V;
-  typedef typename Stor<ST>::Q Q;
-  typedef typename Stor<ST>::T T;
-  constexpr int RPW = 64 / G;                       // rows per wave per step
-  constexpr int WAVES = BCX_SCAN_THREADS / 64;
-  constexpr int RPB = WAVES * RPW * UR;             // rows per workgroup per trip
-  constexpr bool PACK4 = G >= 4 && (UR % 4 == 0);
-  constexpr int GSZ = PACK4 ? G / 4 : G;          // lanes that end up tracking the same row
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int sub = lane % G, rsub = lane / G;
-  int myu = 0, myrs = 0;                            // PACK4: the (row step, row-in-load) pair this lane tracks
-  if constexpr (PACK4) pack_map<G>(lane, myu, myrs);
-
-  // query pieces for this lane's columns -> registers
-  Q q0[CH], q1[CH];
-  int voff[CH];
-#pragma unroll
-  for (int c = 0; c < CH; ++c) { const int v = c * G + sub; voff[c] = v < a.nvec ? v : 0; }   // clamp: the load stays inside the row, the zero query kills the product
-  T e = 0;
-
-  Track<T> tr;
-  tr.U1 = tr.U2 = tr.U3 = tr.L = -INFINITY;
-  tr.i1 = tr.i2 = 0x7fffffff;
-
-  const V* base = (const V*)a.An;
-  const int64_t n = a.n;
-  auto row_of = [&](int64_t r0, int u) { return r0 + (int64_t)(u * WAVES + wave) * RPW + rsub; };
-  auto load_trip = [&](V (&x)[UR][CH], int64_t r0) {
-#pragma unroll
-    for (int u = 0; u < UR; ++u) {
-      const int64_t rw = row_of(r0, u);
-      const int64_t rc = rw < n ? rw : n - 1;
-      const V* p = base + rc * a.ldv;
-#pragma unroll
-      for (int c = 0; c < CH; ++c) x[u][c] = stream_load(p + voff[c]);
-    }
-  };
-  auto compute_trip = [&](V (&x)[UR][CH], int64_t r0) {
-    int64_t row[UR];
-#pragma unroll
-    for (int u = 0; u < UR; ++u) {
-      row[u] = row_of(r0, u);
-      if constexpr (sizeof(T) == 8) {
-        if (a.norms) {   // raw fp64 rows: An = A / Anorms element by element (giga.py:13)
-          const double nr = a.norms[row[u] < n ? row[u] : n - 1];
-#pragma unroll
-          for (int c = 0; c < CH; ++c) { x[u][c].x /= nr; x[u][c].y /= nr; }
-        }
-      }
-    }
-    if constexpr (PACK4) {
-      // four row steps at a time: transposed reduction, then every group of G/4 lanes tracks one row
-#pragma unroll
-      for (int g4 = 0; g4 < UR / 4; ++g4) {
-        T a0[4], a1[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-          T t0 = 0, t1 = 0;
-#pragma unroll
-          for (int c = 0; c < CH; ++c) {
-            t0 = vdot(x[g4 * 4 + u][c], q0[c], t0);
-            if (DUAL) t1 = vdot(x[g4 * 4 + u][c], q1[c], t1);
-          }
-          a0[u] = t0; a1[u] = t1;
-        }
-        const T s0 = reduce4_pack<G, T>(a0[0], a0[1], a0[2], a0[3]);
-        const T s1 = DUAL ? reduce4_pack<G, T>(a1[0], a1[1], a1[2], a1[3]) : (T)0;
-        const int64_t myrow = r0 + (int64_t)((g4 * 4 + myu) * WAVES + wave) * RPW + myrs;
-        T U, L;
-        if constexpr (sizeof(T) == 4) {
-          float Uf, Lf;
-          if (DUAL) giga_interval((float)s0, (float)s1, (float)e, Uf, Lf);
-          else { const float ee = (float)e + fabsf((float)s0) * 2e-7f; Uf = (float)s0 + ee; Lf = (float)s0 - ee; }
-          U = Uf; L = Lf;
-        } else {
-          U = L = DUAL ? (T)giga_score((double)s0, (double)s1) : s0;   // exact mode: the score itself
-        }
-        if (!(myrow < n)) { U = -INFINITY; L = -INFINITY; }
-        track_update<T>(tr, U, L, (int)myrow);
-      }
-    } else {
-#pragma unroll
-      for (int u = 0; u < UR; ++u) {
-        T s0 = 0, s1 = 0;
-#pragma unroll
-        for (int c = 0; c < CH; ++c) {
-          s0 = vdot(x[u][c], q0[c], s0);
-          if (DUAL) s1 = vdot(x[u][c], q1[c], s1);
-        }
-        s0 = group_allsum<T, G>(s0);
-        if (DUAL) s1 = group_allsum<T, G>(s1);
-        T U, L;
-        if (sizeof(T) == 4) {
-          if (DUAL) {
-            float Uf, Lf;
-            giga_interval((float)s0, (float)s1, (float)e, Uf, Lf);
-            U = Uf; L = Lf;
-          } else {
-            const T ee = e + fabsf((float)s0) * 2e-7f;
-            U = s0 + ee; L = s0 - ee;
-          }
-        } else {
-          U = L = DUAL ? (T)giga_score((double)s0, (double)s1) : s0;
-        }
-        if (!(row[u] < n)) { U = -INFINITY; L = -INFINITY; }
-        track_update<T>(tr, U, L, (int)row[u]);
-      }
-    }
-  };
-  const int64_t stride = (int64_t)nblk * RPB;
-  // (Two trips in flight per wave -- the loads of trip t+1 issued before trip t is reduced -- measured 3-5 points
-  //  slower at every row length: this stream wants ~32 KiB in flight per CU, not more.)
-  {
-    // The rows do not depend on the query: the first trip's loads are issued, THEN the workgroup waits for the query of
-    // this iteration (gate: the tail workgroup of the same launch publishes it, persist.hip) and fetches it.
-    int64_t r0 = (int64_t)blk * RPB;
-    V x[UR][CH];
-    if (r0 < n) load_trip(x, r0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (!gate()) return false;
-    // The query, its scale and the state machine's switch were written by another workgroup, possibly on another XCD, while
-    // this one was running: sc1 loads (served by the memory side, whatever this XCD's L2 holds from the last iteration) -- an
-    // acquire fence here instead costs ~19 ns PER WAVE of the whole launch, one after the other (measured: 2048 waves, +39 us
-    // per iteration).  The compiler does not count these loads: one wait for all of them (and for the trip above, which
-    // is needed next anyway), then the values are tied to the wait before anything reads them.
-    static_assert(sizeof(Q) == 16, "16-byte query pieces (fp32 / fp64 storage)");
-    nt_u4 rq0[CH], rq1[CH];
-    unsigned ract;
-    v2u rqs;
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const Q* p0 = (const Q*)a.q + voff[c];
-      asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(rq0[c]) : "v"(p0) : "memory");
-      if (DUAL) {
-        const Q* p1 = p0 + a.qstride;
-        asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=v"(rq1[c]) : "v"(p1) : "memory");
-      }
-    }
-    {
-      const int* pa = &a.st->active;
-      const double* ps = &a.st->qscale;
-      asm volatile("global_load_dword %0, %1, off sc1" : "=v"(ract) : "v"(pa) : "memory");
-      asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(rqs) : "v"(ps) : "memory");
-    }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      asm volatile("" : "+v"(rq0[c]));
-      if (DUAL) asm volatile("" : "+v"(rq1[c]));
-    }
-    asm volatile("" : "+v"(ract));
-    asm volatile("" : "+v"(rqs));
-    if (!ract) return false;          // the state machine stopped (uniform: one word)
-#pragma unroll
-    for (int c = 0; c < CH; ++c) {
-      const bool ok = c * G + sub < a.nvec;
-      __builtin_memcpy(&q0[c], &rq0[c], 16);
-      if (!ok) memset(&q0[c], 0, sizeof(Q));
-      if (DUAL) {
-        __builtin_memcpy(&q1[c], &rq1[c], 16);
-        if (!ok) memset(&q1[c], 0, sizeof(Q));
-      }
-    }
-    {
-      const unsigned long long qb = ((unsigned long long)rqs.y << 32) | rqs.x;
-      e = (T)(a.err_coef * (float)__longlong_as_double((long long)qb));
-    }
-    if (r0 < n) {
-      __builtin_amdgcn_sched_barrier(0);
-      compute_trip(x, r0);
-      for (r0 += stride; r0 < n; r0 += stride) {
-        load_trip(x, r0);
-        __builtin_amdgcn_sched_barrier(0);
-        compute_trip(x, r0);
-      }
-    }
-  }
-  // combine the row groups of a wave (lanes with equal `sub` hold distinct row groups)
-#pragma unroll
-  for (int off = GSZ; off < 64; off <<= 1) tr = merge<T>(tr, shfl_track<T>(tr, off));
-  __shared__ Track<T> wtr[WAVES];
-  if (lane == 0) wtr[wave] = tr;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    Track<T> r = wtr[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) r = merge<T>(r, wtr[w]);
-    const int b = (int)blk;
-    // write-through (sc1) stores: the tail's workgroup reads them from the memory side; the caller waits for them before its stamp
-    auto st64 = [](double* p, double v) {
-      __hip_atomic_store((unsigned long long*)p, (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    };
-    st64(a.out.U1 + b, (double)r.U1); st64(a.out.U2 + b, (double)r.U2); st64(a.out.U3 + b, (double)r.U3); st64(a.out.L + b, (double)r.L);
-    __hip_atomic_store(a.out.i1 + b, r.i1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(a.out.i2 + b, r.i2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  return true;
 }

@@ -1,6 +1,5 @@
 // tail_core.h -- the replicated O(d) state machine of a GIGA / Frank-Wolfe iteration after the winner is known (apply_core) and
-// what its kernels fetch before the scan's partials arrive: shared by resolve.hip (one launch per iteration) and persist.hip
-// (the tail workgroup of a launch that covers several iterations).
+// what its kernels fetch before the scan's partials arrive: the device code of resolve.hip's tail kernels.
 #pragma once
 #include "bcx_internal.h"
 #include "dev_util.h"

@@ -1,7 +1,7 @@
 """dev: the Gram operator of the dense re-weight (bcx_gram: csrc/gram.hip gram_sk_kernel; BCX_GRAM_NCT=-1: csrc/moments.hip
 gram_tile_kernel + moments_reduce_kernel; BCX_GRAM_NCT=4 / 8 forces the tile width) --
 kernel time by hipEvents over `reps` back-to-back calls, upper-triangle flops k (k + 1) d over that time against the fp64 MFMA
-peak; beside it round 2's direct kernel through optimize() is selected with BCX_GRAM_DIRECT=1 (tools/optimize_bench.py).
+peak.
     python tools/gram_bench.py [k,d ...]"""
 import os, sys
 os.environ.setdefault("BCX_DEV", "1")   # dev switches are read only under this gate (csrc/dev_util.h)
