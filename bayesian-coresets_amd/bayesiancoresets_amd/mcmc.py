@@ -1,6 +1,6 @@
 """MCMC on the weighted points: what a Bayesian coreset is built for.  The reference's logistic / Poisson regression
 experiment scores every coreset by running Stan on it with ``'w': wts`` (examples/logistic_poisson_regression/main.py:107-127,
-205-232; examples/common/mcmc.py:60-70); here the sampler is Hamiltonian Monte Carlo on the device (csrc/hmc.hip):
+205-232; examples/common/mcmc.py:60-70); here the sampler is Hamiltonian Monte Carlo on the device (csrc/hmc.hip, csrc/nuts.hip):
 
 * ``DeviceHMC(family, D, chains, leapfrog, seed).sample(pts, wts, n_samples, ...)``: ``chains`` chains in the whitened variable
   xi (theta = center + transform^T xi, by default the Laplace mode and covariance factor of the same weighted posterior), a fixed
@@ -8,11 +8,17 @@ experiment scores every coreset by running Stan on it with ``'w': wts`` (example
   workgroup run as ONE launch with a workgroup per chain; more (the resident full data set) run as one log-joint pass over the
   rows per leapfrog step for all chains, enqueued without host synchronisation.  The normal numbers come from the library's
   counter-based generator (``_DeviceNormals``): a seed fixes the run.
+* ``DeviceHMC(..., kernel="nuts", max_depth=8)``: the same chains with the No-U-Turn transition (csrc/nuts.hip) in
+  place of the fixed leapfrog count -- trees of up to ``max_depth`` doublings, no step jitter, dual averaging on the tree's mean
+  accept statistic -- for points that fit the LDS of one workgroup, as ONE launch.
 * ``log_joint_grad(family, pts, wts, thetas)``: the weighted log joint and its gradient for many parameter vectors at once
   (model_lr.py:34-39, 59-64; model_poiss.py:40-46, 69-74) -- what the experiment's ``Fs`` metric is made of.
 
-This is fixed-length HMC, not NUTS, with a unit mass matrix in xi; logistic and Poisson only (the linreg / Gaussian posteriors
-are closed-form and sampled exactly by their own samplers), D <= 32.  There is no CPU fallback."""
+Fixed-length HMC is the default; NUTS runs only on the LDS-resident path (there is no streamed NUTS: more points than one
+workgroup holds raise, use ``kernel="hmc"``), with up to 10 doublings and a noise tensor of chains x transitions x
+(D + 3 max_depth + 2 (2^max_depth - 1)) doubles of at most 2 GiB.  Both use a unit mass matrix in xi (no learned mass matrix);
+logistic and Poisson only (the linreg / Gaussian posteriors are closed-form and sampled exactly by their own samplers), D <= 32,
+one device.  There is no CPU fallback."""
 import importlib.util
 import os
 import time
@@ -25,6 +31,9 @@ from .linreg_sampler import _DeviceNormals
 DMAX = 32
 STREAM_CHAINS_MAX = 256
 DIAG = 6
+NUTS_DIAG = 8
+NUTS_DEPTH_MAX = 10
+NUTS_NOISE_BYTES_MAX = 2 << 30
 
 
 def _example_model(family):
@@ -56,7 +65,11 @@ def split_rhat(x):
 class HMCResult(object):
     """``samples`` (chains, n_samples, D); ``accept_rate`` / ``step_size`` (chains); ``delta_h`` / ``accepted`` (chains,
     n_samples); ``rhat`` (D); ``seconds_per_iteration`` (wall time of the run over warm-up + sampling transitions); ``streamed``
-    (the path taken); ``center`` / ``transform``; ``trace`` (``keep_trace=True``: every transition, warm-up included)."""
+    (the path taken); ``center`` / ``transform``; ``trace`` (``keep_trace=True``: every transition, warm-up included).
+    ``kernel="nuts"`` adds ``tree_depth`` / ``n_leapfrog`` / ``divergent`` / ``accept_stat`` (chains, n_samples) and
+    ``leapfrog_total`` (chains: the leapfrog steps of all transitions, warm-up included); there
+    ``accept_rate`` is the per-chain mean of the accept statistic, ``delta_h`` the selected state's energy minus the start's and
+    ``accepted`` whether the state moved."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -120,15 +133,19 @@ def log_joint_grad(family, pts, wts, thetas, device="cuda"):
 class DeviceHMC(_DeviceNormals):
     STEP0 = 0.5        # the step the dual averaging starts from (the whitened target is near N(0, I))
 
-    def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda", *, device_frame=False):
-        import torch
-        from . import _native
+    def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda", *, device_frame=False, kernel="hmc", max_depth=8):
         if family not in FAMILIES:
             raise ValueError("family must be 'logistic' or 'poisson'")
         if not 1 <= int(D) <= DMAX:
             raise ValueError("DeviceHMC: D = %d parameters (1 <= D <= %d)" % (D, DMAX))
         if int(chains) < 1 or int(leapfrog) < 1:
             raise ValueError("DeviceHMC: at least one chain and one leapfrog step")
+        if kernel not in ("hmc", "nuts"):
+            raise ValueError("DeviceHMC: kernel must be 'hmc' or 'nuts', not %r" % (kernel,))
+        if not 1 <= int(max_depth) <= NUTS_DEPTH_MAX:
+            raise ValueError("DeviceHMC: max_depth = %d (1 <= max_depth <= %d)" % (max_depth, NUTS_DEPTH_MAX))
+        import torch
+        from . import _native
         self._torch, self._nat = torch, _native
         self._lib = _native.load()
         if not torch.cuda.is_available():
@@ -136,6 +153,7 @@ class DeviceHMC(_DeviceNormals):
         self.family, self._fam = family, FAMILIES[family]
         self.device = torch.device(device)
         self.D, self.chains, self.leapfrog = int(D), int(chains), int(leapfrog)
+        self.kernel, self.max_depth = kernel, int(max_depth)
         self.ld = self.D + (self.D % 2)
         self.cols = self.D + (1 if family == "poisson" else 0)
         self._seed, self._offset = (0 if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF, 0
@@ -146,6 +164,10 @@ class DeviceHMC(_DeviceNormals):
     def coreset_path(self, k):
         """Whether k points run on the LDS-resident path (one launch, a workgroup per chain)."""
         return bool(self._lib.bcx_hmc_coreset_ok(int(k), self.D))
+
+    def nuts_path(self, k):
+        """Whether k points fit the NUTS kernel (``kernel="nuts"``: the only path it has)."""
+        return bool(self._lib.bcx_nuts_coreset_ok(int(k), self.D))
 
     def _default_frame(self, k, pts, wts, Z=None, w=None):
         if k == 0:
@@ -175,6 +197,15 @@ class DeviceHMC(_DeviceNormals):
             raise ValueError("DeviceHMC.sample: at least one transition")
         T = n_samples + n_warmup
         k = 0 if pts is None else len(pts)
+        nuts = self.kernel == "nuts"
+        R = D + 3 * self.max_depth + 2 * ((1 << self.max_depth) - 1) if nuts else D + 3
+        if nuts:
+            if _dev_force_stream or not self.nuts_path(k):
+                raise ValueError("DeviceHMC: there is no streamed NUTS -- %d points of %d parameters do not fit the LDS of one workgroup "
+                                 "(or the streamed path was forced); use kernel=\"hmc\"" % (k, D))
+            if 8 * C * T * R > NUTS_NOISE_BYTES_MAX:
+                raise ValueError("DeviceHMC: the NUTS noise (chains x transitions x %d doubles = %d bytes) exceeds 2 GiB; lower max_depth "
+                                 "(%d), chains (%d) or the number of transitions (%d)" % (R, 8 * C * T * R, self.max_depth, C, T))
         Z = _device_rows(torch, self.device, pts, self.cols, "points") if k else None
         w = None
         if wts is not None and k:
@@ -188,15 +219,15 @@ class DeviceHMC(_DeviceNormals):
         Wm = None if transform is None else np.ascontiguousarray(transform, dtype=np.float64).reshape(D, D)
         mu_dev = torch.from_numpy(mu).to(self.device)
         W_dev = None if Wm is None else torch.from_numpy(Wm).to(self.device)
-        streamed = bool(_dev_force_stream) or not self.coreset_path(k)
+        streamed = not nuts and (bool(_dev_force_stream) or not self.coreset_path(k))
         if streamed and C > STREAM_CHAINS_MAX:
             raise ValueError("DeviceHMC: the streamed path takes at most %d chains" % STREAM_CHAINS_MAX)
-        noise = self._normal(C, T, D + 3)
+        noise = self._normal(C, T, R)
         f64 = dict(dtype=torch.float64, device=self.device)
         samples = torch.empty(C, T, ld, **f64)
         xis = torch.empty(C, T, ld, **f64) if keep_trace else None
         props = torch.empty(C, T, ld, **f64) if keep_trace else None
-        diag = torch.empty(C, T, DIAG, **f64)
+        diag = torch.empty(C, T, NUTS_DIAG if nuts else DIAG, **f64)
         acc, eps = torch.empty(C, **f64), torch.empty(C, **f64)
         ptr = lambda t: None if t is None else t.data_ptr()
         common = [ptr(mu_dev), ptr(W_dev), D, C, n_warmup, n_samples, self.leapfrog, self.STEP0,
@@ -206,7 +237,13 @@ class DeviceHMC(_DeviceNormals):
             stream = int(torch.cuda.current_stream(self.device).cuda_stream)
             torch.cuda.synchronize(self.device)
             t0 = time.perf_counter()
-            if streamed:
+            if nuts:
+                fixed = 0.0 if _dev_step_size is None else float(_dev_step_size)
+                rc = lib.bcx_nuts_coreset(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, ptr(mu_dev), ptr(W_dev), D,
+                                          C, n_warmup, n_samples, self.max_depth, self.STEP0, fixed, noise.data_ptr(), R, ld,
+                                          samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(), eps.data_ptr(),
+                                          self._status.data_ptr())
+            elif streamed:
                 nbytes = int(lib.bcx_hmc_stream_scratch_bytes(k, D, C))
                 work = torch.empty(nbytes // 8 + 1, **f64)
                 rc = lib.bcx_hmc_stream(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, *(common + [work.data_ptr(), nbytes]))
@@ -221,10 +258,18 @@ class DeviceHMC(_DeviceNormals):
             raise self._nat.EngineError(self._nat.ERR_STATE, "HMC on the device: the log joint at the start is not finite (NaN weights or points)")
         out = samples[:, n_warmup:, :D].cpu().numpy()
         dg = diag.cpu().numpy()
-        res = HMCResult(samples=out, accept_rate=acc.cpu().numpy(), step_size=eps.cpu().numpy(), delta_h=dg[:, n_warmup:, 0],
-                        accepted=dg[:, n_warmup:, 1] > 0.5, rhat=split_rhat(out) if n_samples >= 4 else np.full(D, np.nan),
+        if nuts:
+            th = samples[:, :, :D].cpu().numpy()
+            before = np.concatenate((np.broadcast_to(mu, (C, 1, D)), th[:, :-1]), axis=1)      # (every chain starts at xi = 0: theta = center)
+            extra = dict(delta_h=dg[:, n_warmup:, 7], accepted=(th != before).any(axis=2)[:, n_warmup:], accept_stat=dg[:, n_warmup:, 0],
+                         tree_depth=dg[:, n_warmup:, 1].astype(np.int64), n_leapfrog=dg[:, n_warmup:, 2].astype(np.int64),
+                         divergent=dg[:, n_warmup:, 6] > 0.5, leapfrog_total=dg[:, :, 2].sum(axis=1).astype(np.int64), kernel="nuts",
+                         max_depth=self.max_depth)
+        else:
+            extra = dict(delta_h=dg[:, n_warmup:, 0], accepted=dg[:, n_warmup:, 1] > 0.5, kernel="hmc")
+        res = HMCResult(samples=out, accept_rate=acc.cpu().numpy(), step_size=eps.cpu().numpy(), rhat=split_rhat(out) if n_samples >= 4 else np.full(D, np.nan),
                         seconds_per_iteration=seconds / T, streamed=streamed, nonfinite_rejected=bool(st[0] == 1),
-                        center=mu, transform=np.eye(D) if Wm is None else Wm, n_warmup=n_warmup, trace=None)
+                        center=mu, transform=np.eye(D) if Wm is None else Wm, n_warmup=n_warmup, trace=None, **extra)
         if keep_trace:
             res.trace = dict(noise=noise.cpu().numpy(), theta=samples[:, :, :D].cpu().numpy(), xi=xis[:, :, :D].cpu().numpy(),
                              proposal=props[:, :, :D].cpu().numpy(), diag=dg, step0=self.STEP0)

@@ -23,13 +23,9 @@
 #include <math.h>
 #include <string>
 #include "bcx_internal.h"
-#include "dev_util.h"
-#include "lik_point.h"
+#include "hmc_core.h"
 
-#define HMC_DMAX 32
-#define HMC_THREADS 256
 #define HMC_STEP_THREADS 64
-#define HMC_LDW 33
 #define HMC_DIAG 6
 #define LJ_ROWS 128          // rows of a tile
 #define LJ_CT 8              // theta columns of a workgroup
@@ -171,52 +167,7 @@ extern "C" int bcx_log_joint_grad(void* stream, int32_t family, const void* Z_de
 }
 
 // ------------------------------------------------------------------------------------------------------------ the transition
-struct HmcPar {
-  const double* mu;       // D or NULL (zero)
-  const double* W;        // D x D, row stride ldw, or NULL (identity): theta = mu + W^T xi
-  const double* noise;    // C x T x (D + 3) standard normals
-  double* samples;        // C x T x ld: theta after every transition (warm-up included)
-  double* xis;            // C x T x ld or NULL: the same states in xi
-  double* props;          // C x T x ld or NULL: every transition's proposal in xi
-  double* diag;           // C x T x 6: dH, accepted, eps_t, the base step of the next transition, Hbar, log eps-bar
-  double* accept_rate;    // C: over the sampling transitions (all of them when there are none)
-  double* eps_final;      // C: the step the sampling transitions use
-  int* status;            // [0] this launch: 0 ok / 1 a non-finite dH was rejected / 2 non-finite log joint at the start; [1] worst since zeroed
-  double eps0, fixed_eps;
-  int64_t ldw;
-  int D, ld, L, T, nwarm, C;
-};
-enum { SC_LOGP = 0, SC_BASE, SC_HBAR, SC_LEBAR, SC_EPS_T, SC_H0, SC_E, SC_NACC, SC_COUNT = 16 };
-struct HmcChain {         // one chain's state (LDS; the streamed path keeps a copy in global memory between its kernels)
-  double xi[32], xp[32], p[32], gcur[32], thcur[32], th[32], sc[SC_COUNT];
-};
-struct HmcLds {
-  HmcChain s;
-  double W[32 * HMC_LDW], mu[32], gth[32];
-};
-
-static __device__ __forceinline__ double hmc_half_sq(const double* v, int D) {
-  double q = 0.0;
-  for (int c = 0; c < D; ++c) q = fma(v[c], v[c], q);
-  return 0.5 * q;
-}
-static __device__ __forceinline__ void hmc_load_frame(HmcLds& S, const HmcPar& a) {
-  const int D = a.D;
-  for (int e = threadIdx.x; e < 32 * 32; e += blockDim.x) {
-    const int i = e >> 5, c = e & 31;
-    S.W[i * HMC_LDW + c] = (i < D && c < D) ? (a.W ? a.W[(size_t)i * a.ldw + c] : (i == c ? 1.0 : 0.0)) : 0.0;
-  }
-  if (threadIdx.x < 32) S.mu[threadIdx.x] = (threadIdx.x < D && a.mu) ? a.mu[threadIdx.x] : 0.0;
-}
-// th = mu + W^T xp   (callers synchronise around it)
-static __device__ __forceinline__ void hmc_theta(HmcLds& S, int D) {
-  const int tid = threadIdx.x;
-  if (tid < D) {
-    double v = S.mu[tid];
-    for (int i = 0; i < D; ++i) v = fma(S.W[i * HMC_LDW + tid], S.s.xp[i], v);
-    S.s.th[tid] = v;
-  }
-}
+// (HmcPar, HmcChain, HmcLds, the frame, hmc_theta, hmc_reset, the dual averaging: csrc/hmc_core.h)
 // start transition t: momentum, threshold, jittered step, the first half kick and drift; leaves th = theta(xp)
 static __device__ void hmc_begin(HmcLds& S, const HmcPar& a, int chain, int t) {
   const int tid = threadIdx.x, D = a.D;
@@ -280,15 +231,8 @@ static __device__ void hmc_consume(HmcLds& S, const HmcPar& a, int chain, int ph
     if (a.xis) a.xis[o * a.ld + tid] = tid < D ? S.s.xi[tid] : 0.0;
   }
   if (!(a.fixed_eps > 0.0) && t < a.nwarm) {
-    // dual averaging, iteration m = t + 1 (Hoffman & Gelman 2014, Alg. 5; mu = log(10 eps0))
-    const double m = (double)(t + 1);
     const double alpha = fin ? fmin(1.0, exp(-dH)) : 0.0;
-    const double eta = 1.0 / (m + 10.0);
-    hbar = (1.0 - eta) * hbar + eta * (0.8 - alpha);
-    const double loge = log(10.0 * a.eps0) - (sqrt(m) / 0.05) * hbar;
-    const double mk = pow(m, -0.75);
-    lebar = mk * loge + (1.0 - mk) * lebar;
-    base = (t + 1 == a.nwarm) ? exp(lebar) : exp(loge);
+    base = hmc_dual_average(t, a.nwarm, a.eps0, alpha, hbar, lebar);
   }
   if (t >= a.nwarm || a.nwarm >= a.T) nacc += acc ? 1.0 : 0.0;
   if (tid == 0) {
@@ -306,11 +250,6 @@ static __device__ void hmc_consume(HmcLds& S, const HmcPar& a, int chain, int ph
   __syncthreads();
   if (t + 1 < a.T) hmc_begin(S, a, chain, t + 1);
 }
-static __device__ __forceinline__ void hmc_reset(HmcLds& S, const HmcPar& a) {
-  const int tid = threadIdx.x;
-  if (tid < 32) { S.s.xi[tid] = 0.0; S.s.xp[tid] = 0.0; S.s.p[tid] = 0.0; S.s.gcur[tid] = 0.0; S.s.thcur[tid] = 0.0; S.s.th[tid] = 0.0; S.gth[tid] = 0.0; }
-  if (tid < SC_COUNT) S.s.sc[tid] = tid == SC_BASE ? (a.fixed_eps > 0.0 ? a.fixed_eps : a.eps0) : 0.0;
-}
 
 // ------------------------------------------------------------------------------------------- coreset path: the points in LDS
 struct HmcCoresetArgs {
@@ -326,50 +265,15 @@ __global__ __launch_bounds__(HMC_THREADS) void hmc_coreset_kernel(HmcCoresetArgs
   __shared__ HmcLds S;
   __shared__ double s_part[8 * 32];
   __shared__ double scratch[BCX_SCRATCH];
-  const int tid = threadIdx.x, chain = blockIdx.x;
-  const int k = a.k, D = a.par.D, Dp = D + 1;         // (rows of D + 1 doubles: consecutive points on different banks)
-  double* sX = hmc_dyn;                                // k x Dp features
-  double* sw = sX + (size_t)k * Dp;                    // k weights
-  double* sy = sw + k;                                 // k responses (Poisson)
-  double* sg = sy + k;                                 // k: w_j g_j
-  for (int e = tid; e < k * D; e += HMC_THREADS) { const int j = e / D, c = e - j * D; sX[j * Dp + c] = a.pts[(size_t)j * a.ldp + c]; }
-  for (int j = tid; j < k; j += HMC_THREADS) {
-    sw[j] = a.w ? a.w[j] : 1.0;
-    sy[j] = a.family == LAP_POISSON ? a.pts[(size_t)j * a.ldp + D] : 0.0;
-  }
+  const int chain = blockIdx.x, D = a.par.D;
+  const HmcPoints P = hmc_load_points(hmc_dyn, a.family, a.k, D, a.w, a.pts, a.ldp);
   hmc_load_frame(S, a.par);
   hmc_reset(S, a.par);
   __syncthreads();
   hmc_theta(S, D);
   __syncthreads();
 
-  // the target at S.s.th: returns sum_j w_j log p_j - |theta|^2 / 2 and leaves its theta-gradient in S.gth
-  auto eval = [&]() -> double {
-    double part[1] = {0.0};
-    for (int j = tid; j < k; j += HMC_THREADS) {
-      double s = 0.0;
-      for (int c = 0; c < D; ++c) s = fma(sX[j * Dp + c], S.s.th[c], s);
-      double ll, g, h;
-      lap_point(a.family, s, sy[j], ll, g, h);
-      part[0] += sw[j] * ll;
-      sg[j] = sw[j] * g;
-    }
-    block_allsum<1>(part, scratch);
-    {
-      const int c = tid & 31, q = tid >> 5;             // eight interleaved slices of the points per coordinate
-      double t = 0.0;
-      if (c < D) for (int j = q; j < k; j += 8) t = fma(sg[j], sX[j * Dp + c], t);
-      s_part[q * 32 + c] = t;
-    }
-    __syncthreads();
-    if (tid < D) {
-      double t = s_part[tid];
-      for (int q = 1; q < 8; ++q) t += s_part[q * 32 + tid];
-      S.gth[tid] = t - S.s.th[tid];
-    }
-    __syncthreads();
-    return part[0] - hmc_half_sq(S.s.th, D);
-  };
+  auto eval = [&]() -> double { return hmc_eval_points(S, P, D, s_part, scratch); };      // (the target at S.s.th: csrc/hmc_core.h)
 
   hmc_consume(S, a.par, chain, 0, 0, eval());
   for (int t = 0; t < a.par.T; ++t)
@@ -395,7 +299,7 @@ static HmcPar hmc_par(int32_t D, const void* mu, const void* W, int64_t ldw, int
 
 extern "C" int64_t bcx_hmc_coreset_lds_bytes(int32_t k, int32_t D) {
   if (k < 0 || D < 1 || D > HMC_DMAX) return -1;
-  return ((int64_t)k * (D + 1) + 3 * (int64_t)k) * (int64_t)sizeof(double);
+  return hmc_points_lds_bytes(k, D);
 }
 // dynamic LDS one workgroup of the coreset kernel may have: the device's limit minus the kernel's static use (-1: no device)
 static int64_t hmc_coreset_lds_room() {

@@ -1,0 +1,272 @@
+// nuts.hip -- the No-U-Turn sampler (Hoffman & Gelman 2014) on the weighted points, for the case csrc/hmc.hip runs as one
+// launch: one workgroup per chain, the k points resident in LDS for all warm-up and sampling transitions.  The reference's
+// logistic / Poisson experiment scores a coreset with Stan, whose sampler is NUTS; the fixed leapfrog count of bcx_hmc_coreset is
+// the one knob this removes.
+//
+// The chain moves in xi, theta = mu + W^T xi, unit mass matrix, the target, frame and dual averaging of csrc/hmc_core.h.  With
+// J = max_depth, transition t of a chain reads R = D + 3 J + 2 (2^J - 1) standard normals: D momenta; per doubling j the
+// direction (z >= 0: forward) and two for the threshold e_j = (a^2 + b^2) / 2 ~ Exp(1); per leaf slot 2^j - 1 + i two for
+// e_leaf.  Doubling j integrates 2^j leapfrog steps of v eps from the right (v = +1) or left endpoint, one target evaluation per
+// leaf.  Leaf i: delta = H0 - H_leaf; the accept statistic gains min(1, exp delta); not (finite and delta > -1000) is a
+// divergence; logS = logaddexp(logS, delta) and the leaf becomes the doubling's proposal iff logS - delta <= e_leaf; every balanced
+// span of leaves that closes at i (one per trailing one bit of i) is tested for a U-turn against the endpoint of its first leaf,
+// which even leaf a left at checkpoint slot popcount(a) -- at most J slots.  A divergence or a turn discards the doubling and
+// stops the tree.  A completed doubling replaces the tree's proposal iff logW - logS <= e_j (biased progressive sampling), then
+// the tree stops if its own endpoints turn.  The selected state carries its log target, gradient and theta.
+//
+// Every branch is taken by the whole workgroup: each thread computes the decision from the same LDS values (or from scalars
+// every thread derived identically from them), and all loops are bounded by integers -- at most 2^J - 1 leaves per transition.
+#include <atomic>
+#include <string>
+#include "bcx_internal.h"
+#include "hmc_core.h"
+
+#define NUTS_JMAX 10
+#define NUTS_DIAG 8
+#define NUTS_DIVERGENT -1000.0
+
+void bcx_project_set_error(const std::string& msg);   // proj.hip
+
+struct NutsArgs {
+  HmcPar par;           // (noise: C x T rows of stride noise_ld; L unused; diag: C x T x 8)
+  const double* w;      // k weights or NULL (ones)
+  const double* pts;    // k x ldp
+  int64_t ldp, noise_ld;
+  int family, k, J;
+};
+struct NutsTree {
+  double xl[32], pl[32], gl[32], xr[32], pr[32], gr[32];     // the tree's endpoints: xi, momentum, xi-gradient
+  double gm[32];                                             // the xi-gradient at the moving end (its xi and momentum: S.s.xp, S.s.p)
+  double xs[32], gs[32], ths[32];                            // the doubling's proposal: xi, xi-gradient, theta
+  double ckx[NUTS_JMAX][32], ckp[NUTS_JMAX][32];             // checkpoints: xi and momentum of even leaves, slot popcount(leaf)
+};
+
+static __device__ __forceinline__ double nuts_logaddexp(double a, double b) { return fmax(a, b) + log1p(exp(-fabs(a - b))); }
+static __device__ __forceinline__ double nuts_threshold(const double* z) { return 0.5 * (z[0] * z[0] + z[1] * z[1]); }
+
+__global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(NutsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double nuts_dyn[];
+  __shared__ HmcLds S;
+  __shared__ NutsTree Tr;
+  __shared__ double s_part[8 * 32];
+  __shared__ double scratch[BCX_SCRATCH];
+  const int tid = threadIdx.x, chain = blockIdx.x;
+  const int D = a.par.D, J = a.J, T = a.par.T, nwarm = a.par.nwarm, ld = a.par.ld;
+  const HmcPoints P = hmc_load_points(nuts_dyn, a.family, a.k, D, a.w, a.pts, a.ldp);
+  hmc_load_frame(S, a.par);
+  hmc_reset(S, a.par);
+  __syncthreads();
+  hmc_theta(S, D);
+  __syncthreads();
+
+  // the start state xi = 0: its log target, xi-gradient and theta
+  double logp_cur = hmc_eval_points(S, P, D, s_part, scratch);
+  if (tid < D) {
+    double gx = 0.0;
+    for (int c = 0; c < D; ++c) gx = fma(S.W[tid * HMC_LDW + c], S.gth[c], gx);
+    S.s.gcur[tid] = gx;
+    S.s.thcur[tid] = S.s.th[tid];
+  }
+  if (tid == 0 && !isfinite(logp_cur)) { atomicMax(&a.par.status[0], 2); atomicMax(&a.par.status[1], 2); }
+  __syncthreads();
+
+  const bool adapt = !(a.par.fixed_eps > 0.0);
+  double base = adapt ? a.par.eps0 : a.par.fixed_eps, hbar = 0.0, lebar = 0.0, acc_sum = 0.0;
+  for (int t = 0; t < T; ++t) {
+    const double* z = a.par.noise + ((size_t)chain * T + t) * a.noise_ld;
+    const double eps = base;
+    const double H0 = hmc_half_sq(z, D) - logp_cur;
+    if (tid < D) {
+      const double p0 = z[tid], x0 = S.s.xi[tid], g0 = S.s.gcur[tid];
+      Tr.xl[tid] = x0; Tr.pl[tid] = p0; Tr.gl[tid] = g0;
+      Tr.xr[tid] = x0; Tr.pr[tid] = p0; Tr.gr[tid] = g0;
+    }
+    double logW = 0.0, asum = 0.0, dsel = 0.0;
+    int nleaf = 0, depth = 0;
+    bool divergent = false;
+    __syncthreads();
+    for (int j = 0; j < J; ++j) {
+      const bool fwd = z[D + 3 * j] >= 0.0;
+      const double v = fwd ? 1.0 : -1.0;
+      const double ej = nuts_threshold(z + D + 3 * j + 1);
+      if (tid < D) {
+        S.s.xp[tid] = fwd ? Tr.xr[tid] : Tr.xl[tid];
+        S.s.p[tid] = fwd ? Tr.pr[tid] : Tr.pl[tid];
+        Tr.gm[tid] = fwd ? Tr.gr[tid] : Tr.gl[tid];
+      }
+      __syncthreads();
+      const double he = v * (0.5 * eps), ve = v * eps;
+      const double* zl = z + D + 3 * J + 2 * ((1 << j) - 1);
+      double logS = 0.0, logp_s = 0.0, h_s = 0.0;
+      bool ok = true;
+      for (int i = 0; i < (1 << j); ++i) {
+        // one leapfrog step of v eps from the moving end
+        if (tid < D) {
+          const double ph = S.s.p[tid] + he * Tr.gm[tid];
+          S.s.p[tid] = ph;
+          S.s.xp[tid] = S.s.xp[tid] + ve * ph;
+        }
+        __syncthreads();
+        hmc_theta(S, D);
+        __syncthreads();
+        const double logp = hmc_eval_points(S, P, D, s_part, scratch);
+        if (tid < D) {
+          double gx = 0.0;
+          for (int c = 0; c < D; ++c) gx = fma(S.W[tid * HMC_LDW + c], S.gth[c], gx);
+          Tr.gm[tid] = gx;
+          S.s.p[tid] = S.s.p[tid] + he * gx;
+        }
+        __syncthreads();
+        const double Hl = hmc_half_sq(S.s.p, D) - logp;
+        const double delta = H0 - Hl;
+        const bool fin = isfinite(delta);
+        asum += fin ? fmin(1.0, exp(delta)) : 0.0;
+        ++nleaf;
+        if (!fin && tid == 0) { atomicMax(&a.par.status[0], 1); atomicMax(&a.par.status[1], 1); }
+        if (!(fin && delta > NUTS_DIVERGENT)) { divergent = true; ok = false; break; }
+        bool take = true;
+        if (i == 0) {
+          logS = delta;
+        } else {
+          logS = nuts_logaddexp(logS, delta);
+          take = logS - delta <= nuts_threshold(zl + 2 * i);
+        }
+        if (take) {
+          if (tid < D) { Tr.xs[tid] = S.s.xp[tid]; Tr.gs[tid] = Tr.gm[tid]; Tr.ths[tid] = S.s.th[tid]; }
+          logp_s = logp; h_s = Hl;
+        }
+        if (i & 1) {
+          // the balanced spans that close here: leaves i - 2^m + 1 .. i for every trailing one bit of i
+          for (int m = 1; m <= j && ((i >> (m - 1)) & 1); ++m) {
+            const int slot = __popc((unsigned)(i - (1 << m) + 1));
+            double da = 0.0, db = 0.0;
+            for (int c = 0; c < D; ++c) {
+              const double d = v * (S.s.xp[c] - Tr.ckx[slot][c]);
+              da = fma(d, Tr.ckp[slot][c], da);
+              db = fma(d, S.s.p[c], db);
+            }
+            if (da < 0.0 || db < 0.0) { ok = false; break; }
+          }
+        } else if (tid < D) {
+          const int slot = __popc((unsigned)i);
+          Tr.ckx[slot][tid] = S.s.xp[tid];
+          Tr.ckp[slot][tid] = S.s.p[tid];
+        }
+        __syncthreads();
+        if (!ok) break;
+      }
+      if (!ok) break;                       // a divergence or a turn inside the doubling: it is discarded, the tree stops
+      if (logW - logS <= ej) {
+        if (tid < D) { S.s.xi[tid] = Tr.xs[tid]; S.s.gcur[tid] = Tr.gs[tid]; S.s.thcur[tid] = Tr.ths[tid]; }
+        logp_cur = logp_s;
+        dsel = h_s - H0;
+      }
+      logW = nuts_logaddexp(logW, logS);
+      if (tid < D) {
+        if (fwd) { Tr.xr[tid] = S.s.xp[tid]; Tr.pr[tid] = S.s.p[tid]; Tr.gr[tid] = Tr.gm[tid]; }
+        else { Tr.xl[tid] = S.s.xp[tid]; Tr.pl[tid] = S.s.p[tid]; Tr.gl[tid] = Tr.gm[tid]; }
+      }
+      depth = j + 1;
+      __syncthreads();
+      double da = 0.0, db = 0.0;
+      for (int c = 0; c < D; ++c) {
+        const double d = Tr.xr[c] - Tr.xl[c];
+        da = fma(d, Tr.pl[c], da);
+        db = fma(d, Tr.pr[c], db);
+      }
+      if (da < 0.0 || db < 0.0) break;
+    }
+    __syncthreads();
+    // the new state is the selected one; outputs, adaptation
+    const size_t o = (size_t)chain * T + t;
+    if (tid < ld) {
+      a.par.samples[o * ld + tid] = tid < D ? S.s.thcur[tid] : 0.0;
+      if (a.par.xis) a.par.xis[o * ld + tid] = tid < D ? S.s.xi[tid] : 0.0;
+      if (a.par.props) a.par.props[o * ld + tid] = tid < D ? S.s.xi[tid] : 0.0;
+    }
+    const double alpha = asum / (double)nleaf;
+    if (adapt && t < nwarm) base = hmc_dual_average(t, nwarm, a.par.eps0, alpha, hbar, lebar);
+    if (t >= nwarm || nwarm >= T) acc_sum += alpha;
+    if (tid == 0) {
+      double* dg = a.par.diag + o * NUTS_DIAG;
+      dg[0] = alpha; dg[1] = (double)depth; dg[2] = (double)nleaf; dg[3] = base; dg[4] = hbar; dg[5] = lebar;
+      dg[6] = divergent ? 1.0 : 0.0; dg[7] = dsel;
+      if (t + 1 == T) {
+        const int cnt = nwarm >= T ? T : T - nwarm;
+        a.par.accept_rate[chain] = acc_sum / (double)cnt;
+        a.par.eps_final[chain] = base;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+extern "C" int64_t bcx_nuts_coreset_lds_bytes(int32_t k, int32_t D) {
+  if (k < 0 || D < 1 || D > HMC_DMAX) return -1;
+  return hmc_points_lds_bytes(k, D);
+}
+// dynamic LDS one workgroup of the NUTS kernel may have: the device's limit minus this kernel's static use (-1: no device)
+static int64_t nuts_coreset_lds_room() {
+  static std::atomic<int64_t> room[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
+  int64_t r = room[dev].load(std::memory_order_acquire);
+  if (r != 0) return r;
+  int maxb = 0;
+  hipFuncAttributes fa;
+  if (hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
+      hipFuncGetAttributes(&fa, (const void*)nuts_coreset_kernel) != hipSuccess) {
+    (void)hipGetLastError();
+    return -1;
+  }
+  r = (int64_t)maxb - (int64_t)fa.sharedSizeBytes;
+  if (r <= 0) r = -1;
+  room[dev].store(r, std::memory_order_release);
+  return r;
+}
+extern "C" int bcx_nuts_coreset_ok(int32_t k, int32_t D) {
+  const int64_t b = bcx_nuts_coreset_lds_bytes(k, D);
+  return b >= 0 && b <= nuts_coreset_lds_room();
+}
+extern "C" int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                                const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                                int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
+                                void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
+                                void* status_dev) {
+  const bool shape_ok = (family == LAP_LOGISTIC || family == LAP_POISSON) && D >= 1 && D <= HMC_DMAX && chains >= 1 && n_warmup >= 0 &&
+                        n_samples >= 0 && (int64_t)n_warmup + n_samples >= 1 && (int64_t)n_warmup + n_samples <= INT32_MAX &&
+                        max_depth >= 1 && max_depth <= NUTS_JMAX && eps0 > 0.0 && ld >= D && ld <= 32 && noise_dev && samples_dev &&
+                        diag_dev && accept_dev && eps_dev && status_dev;
+  if (!shape_ok || noise_ld < (int64_t)D + 3 * (int64_t)max_depth + 2 * (((int64_t)1 << max_depth) - 1) || !bcx_nuts_coreset_ok(k, D) ||
+      (W_dev && ldw < D) || (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0)))) {
+    bcx_project_set_error("bcx_nuts_coreset: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, the points within "
+                          "bcx_nuts_coreset_ok, at least one transition, max_depth 1 .. 10, noise_ld >= D + 3 max_depth + "
+                          "2 (2^max_depth - 1), eps0 > 0)");
+    return BCX_ERR_ARG;
+  }
+  NutsArgs a;
+  HmcPar& p = a.par;
+  p.mu = (const double*)mu_dev; p.W = (const double*)W_dev; p.noise = (const double*)noise_dev; p.samples = (double*)samples_dev;
+  p.xis = (double*)xi_dev; p.props = (double*)prop_dev; p.diag = (double*)diag_dev; p.accept_rate = (double*)accept_dev;
+  p.eps_final = (double*)eps_dev; p.status = (int*)status_dev; p.eps0 = eps0; p.fixed_eps = fixed_eps; p.ldw = ldw; p.D = D; p.ld = ld;
+  p.L = 0; p.T = n_warmup + n_samples; p.nwarm = n_warmup; p.C = chains;
+  a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.ldp = ldp; a.noise_ld = noise_ld; a.family = family; a.k = k; a.J = max_depth;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)bcx_nuts_coreset_lds_bytes(k, D);
+  if (lds > 16 * 1024) {
+    static std::atomic<size_t> lds_max[64];
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (lds > lds_max[dev].load(std::memory_order_acquire)) {
+      if (hipFuncSetAttribute((const void*)nuts_coreset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
+        bcx_project_set_error("bcx_nuts_coreset: hipFuncSetAttribute failed");
+        return BCX_ERR_HIP;
+      }
+      lds_max[dev].store(lds, std::memory_order_release);
+    }
+  }
+  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_nuts_coreset: memset failed"); return BCX_ERR_HIP; }
+  hipLaunchKernelGGL(nuts_coreset_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);
+  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_coreset: launch failed"); return BCX_ERR_HIP; }
+  return BCX_OK;
+}

@@ -18,7 +18,9 @@ LAPLACE approximations of the coreset posterior and of the full-data posterior. 
 bc.DeviceHMC (examples/common/mcmc.py; `--mcmc_samples_full` / `--mcmc_samples_coreset` draws, the full-data draws cached under
 <results_folder>/mcmc_cache), takes the Gaussian moments of the draws for the same columns and adds the reference's others: `Fs`
 (the mean squared difference of the coreset's and the full data's log-joint gradients over the full-data draws, two
-bc.log_joint_grad calls), `full_mcmc_time_per_itr`, `mcmc_time_per_itr`."""
+bc.log_joint_grad calls), `full_mcmc_time_per_itr`, `mcmc_time_per_itr`.  `--mcmc_kernel nuts` samples every coreset's posterior
+with the No-U-Turn transition (bc.DeviceHMC(kernel="nuts"): Stan's sampler; a coreset past one workgroup's LDS falls back to HMC);
+the full-data chain stays HMC."""
 import argparse
 import os
 import sys
@@ -63,7 +65,7 @@ def full_data_samples(a, Z):
     if os.path.exists(path):
         d = np.load(path)
         return d["samples"], float(d["t"])
-    samples, t = mcmc.run(Z, None, a.mcmc_samples_full, a.model, a.trial)
+    samples, t, _ = mcmc.run(Z, None, a.mcmc_samples_full, a.model, a.trial)
     t_per_itr = t / (a.mcmc_samples_full * 2)                                  # (main.py:123-124: warm-up = sampling)
     os.makedirs(folder, exist_ok=True)
     np.savez(path, samples=samples, t=t_per_itr)
@@ -74,6 +76,9 @@ def run(a):
     use_mcmc = getattr(a, "eval", "laplace") == "mcmc"
     if not use_mcmc and hasattr(a, "eval"):
         delattr(a, "eval")              # (the default evaluation's result files keep the argument set they always had)
+    mcmc_kernel = getattr(a, "mcmc_kernel", "hmc")
+    if mcmc_kernel == "hmc" and hasattr(a, "mcmc_kernel"):
+        delattr(a, "mcmc_kernel")       # (likewise, given explicitly: the default sampler's result files keep their names)
     stream = bool(getattr(a, "laplace_stream", False))     # (absent unless given: the parser suppresses its default)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
@@ -162,7 +167,7 @@ def run(a):
         csizes[m] = (wts > 0).sum()
         if use_mcmc:
             if csizes[m] > 0:
-                cst, t_cst = mcmc.run(pts[wts > 0], wts[wts > 0], a.mcmc_samples_coreset, a.model, a.trial)
+                cst, t_cst, _ = mcmc.run(pts[wts > 0], wts[wts > 0], a.mcmc_samples_coreset, a.model, a.trial, kernel=mcmc_kernel)
             else:
                 cst, t_cst = np.random.RandomState(a.trial).randn(a.mcmc_samples_coreset, D), 0.0      # the prior
             muw, Sigw = cst.mean(axis=0), np.cov(cst, rowvar=False)
@@ -196,6 +201,9 @@ def parser():
     ap.add_argument("--mcmc_samples_coreset", type=int, default=10000, help="--eval mcmc: draws from every coreset's posterior")
     ap.add_argument("--eval", type=str, choices=["laplace", "mcmc"], default="laplace",
                     help="score a coreset by the Laplace approximation of its posterior, or by HMC on it (bc.DeviceHMC)")
+    ap.add_argument("--mcmc_kernel", type=str, choices=["hmc", "nuts"], default=argparse.SUPPRESS,    # (absent = hmc: result files keep their argument set)
+                    help="--eval mcmc: the transition on every coreset's posterior, default hmc (nuts: bc.DeviceHMC(kernel='nuts')); the full "
+                         "data stays HMC")
     ap.add_argument("--proj_dim", type=int, default=500)
     ap.add_argument("--coreset_size_max", type=int, default=1000)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)

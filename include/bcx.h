@@ -568,6 +568,26 @@ int bcx_hmc_stream(void* stream, int32_t family, int64_t N, int32_t D, const voi
                    int32_t leapfrog, double eps0, double fixed_eps, const void* noise_dev, int32_t ld, void* samples_dev,
                    void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev, void* work_dev,
                    int64_t work_bytes);
+/* The No-U-Turn sampler (Hoffman & Gelman 2014) on the same target, frame and start as bcx_hmc_coreset, for the (k, D) that fit one
+ * workgroup's LDS (csrc/nuts.hip; there is no streamed NUTS): ONE launch, a workgroup per chain, no leapfrog count to choose.
+ * With J = max_depth (1 .. 10), transition t of chain c reads R = D + 3 J + 2 (2^J - 1) standard normals at
+ * noise_dev[(c T + t) noise_ld ..] (noise_ld >= R): D momenta; per doubling j the direction (>= 0: forward) and two for the
+ * threshold e_j = (a^2 + b^2) / 2; per leaf slot 2^j - 1 + i two for e_leaf.  Doubling j takes 2^j leapfrog steps of the base
+ * step (no jitter) from the right or left endpoint; a leaf with delta = H0 - H_leaf not finite or <= -1000 is a divergence; the
+ * leaf replaces the doubling's proposal iff logS - delta <= e_leaf, a completed doubling the tree's iff logW - logS <= e_j; a
+ * U-turn of any balanced span of the doubling discards it and stops the tree, a U-turn of the tree's endpoints stops it.  The
+ * warm-up is the dual averaging of bcx_hmc_coreset on the mean of min(1, exp delta) over the transition's leaves.
+ * Outputs as bcx_hmc_coreset (prop_dev: the selected state, equal to xi_dev) except diag_dev (chains x T x 8: the mean accept
+ * statistic, the depth = completed doublings, the leapfrog steps, the next transition's base step, Hbar, log eps-bar, divergent
+ * 0 / 1, H of the selected state - H0) and accept_dev (chains: the mean accept statistic of the sampling transitions);
+ * status_dev[0]: 0 ok / 1 a leaf's energy was not finite / 2 the log joint at the start is not finite. */
+int bcx_nuts_coreset_ok(int32_t k, int32_t D);
+int64_t bcx_nuts_coreset_lds_bytes(int32_t k, int32_t D);
+int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                     const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                     int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
+                     void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
+                     void* status_dev);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 

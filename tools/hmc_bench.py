@@ -1,9 +1,11 @@
 """Dev tool: time of the device HMC (bc.DeviceHMC, csrc/hmc.hip) per leapfrog step and per transition, and effective samples
 per second -- coreset path at k in {30, 300, 1000}, D = 10, 64 and 256 chains; streamed path at N = 1M, D = 10, 64 chains -- next
 to the NumPy restatement's time per transition on the host (tests/hmc_restatement.py) and the log-joint pass against its
-fp64-VALU model.  One JSON line per case.
+fp64-VALU model.  One JSON line per case.  `--kernel nuts`: the coreset cases only, every one with the NUTS
+kernel (csrc/nuts.hip, max_depth 8) beside the HMC kernel at L = 8 from the same run -- time per leaf (one target evaluation), time
+per transition, mean tree depth, mean leapfrog steps, effective samples per second pooled over the chains.
 
-    python tools/hmc_bench.py [--quick]
+    python tools/hmc_bench.py [--quick] [--kernel nuts]
 """
 import json
 import os
@@ -60,6 +62,28 @@ def case(bc, torch, name, pts, wts, chains, n, center=None, transform=None):
     return res
 
 
+def case_nuts(bc, name, pts, wts, chains, n, center, transform, hmc_res):
+    """The NUTS kernel on the case `hmc_res` ran.  A launch ends with its slowest chain (a workgroup each, all resident at
+    once), so the time per leaf is the launch time over the largest number of evaluations any chain made."""
+    D = pts.shape[1]
+    nuts = bc.DeviceHMC("logistic", D, chains=chains, seed=1, kernel="nuts", max_depth=8)
+    nuts.sample(pts, wts, 10, 10, center=center, transform=transform)              # (first-use costs)
+    res = nuts.sample(pts, wts, n, n, center=center, transform=transform)
+    rows = []
+    for kernel, r in (("hmc", hmc_res), ("nuts", res)):
+        per_tr = r.seconds_per_iteration
+        ess = np.mean([ess_per_chain(r.samples[c, :, j]) for c in range(min(chains, 16)) for j in range(D)]) * chains
+        if kernel == "nuts":
+            evals, depth, leaps = float(r.leapfrog_total.max()) + 1.0, float(r.tree_depth.mean()), float(r.n_leapfrog.mean())
+        else:
+            evals, depth, leaps = 2.0 * n * L + 1.0, None, float(L)
+        rows.append(dict(case=name, kernel=kernel, k=int(pts.shape[0]), D=D, chains=chains, us_per_leaf=per_tr * 2 * n * 1e6 / evals,
+                         us_per_transition=per_tr * 1e6, mean_tree_depth=depth, mean_leapfrogs=leaps, accept=float(r.accept_rate.mean()),
+                         step=float(r.step_size.mean()), rhat_max=float(np.nanmax(r.rhat)), ess_per_second=float(ess / (per_tr * 2 * n))))
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
 def host_baseline(pts, wts, center, transform, n=30):
     D = pts.shape[1]
     host = pts.cpu().numpy() if hasattr(pts, "cpu") else pts
@@ -74,16 +98,23 @@ def main():
     import torch
     import bayesiancoresets_amd as bc
     quick = "--quick" in sys.argv
+    nuts = "--kernel" in sys.argv and sys.argv[sys.argv.index("--kernel") + 1:][:1] == ["nuts"]
     rs = np.random.RandomState(0)
     D = 10
     for k in (30, 300, 1000):
         pts, wts = data(k, D, rs), rs.uniform(1.0, 50.0, k)
         mu, cov = model_lr.laplace_fit(pts, wts)
         W = np.linalg.cholesky(cov).T
-        host = host_baseline(pts, wts, mu, W)
+        host = None if nuts else host_baseline(pts, wts, mu, W)
         for chains in (64, 256):
-            case(bc, torch, "coreset k=%d" % k, pts, wts, chains, 100 if quick else 500, mu, W)
+            res = case(bc, torch, "coreset k=%d" % k, pts, wts, chains, 100 if quick else 500, mu, W)
+            if nuts:
+                case_nuts(bc, "coreset k=%d" % k, pts, wts, chains, 100 if quick else 500, mu, W, res)
+        if nuts:
+            continue
         print(json.dumps(dict(case="host restatement k=%d" % k, us_per_transition_per_chain=host * 1e6)), flush=True)
+    if nuts:
+        return
     N = 100000 if quick else 1000000
     Z = torch.from_numpy(data(N, D, rs)).cuda()
     mu, cov = model_lr.laplace_fit(Z)
