@@ -10,12 +10,14 @@ experiment scores every coreset by running Stan on it with ``'w': wts`` (example
   counter-based generator (``_DeviceNormals``): a seed fixes the run.
 * ``DeviceHMC(..., kernel="nuts", max_depth=8)``: the same chains with the No-U-Turn transition (csrc/nuts.hip) in
   place of the fixed leapfrog count -- trees of up to ``max_depth`` doublings, no step jitter, dual averaging on the tree's mean
-  accept statistic -- for points that fit the LDS of one workgroup, as ONE launch.
+  accept statistic -- for points that fit the LDS of one workgroup, as ONE launch.  ``stream=True`` adds the rows that do not
+  (csrc/nuts_stream.hip): one persistent launch of co-resident workgroups, one pass over the rows per leaf for
+  all chains still running, at most 256 chains.
 * ``log_joint_grad(family, pts, wts, thetas)``: the weighted log joint and its gradient for many parameter vectors at once
   (model_lr.py:34-39, 59-64; model_poiss.py:40-46, 69-74) -- what the experiment's ``Fs`` metric is made of.
 
-Fixed-length HMC is the default; NUTS runs only on the LDS-resident path (there is no streamed NUTS: more points than one
-workgroup holds raise, use ``kernel="hmc"``), with up to 10 doublings and a noise tensor of chains x transitions x
+Fixed-length HMC is the default; without ``stream=True`` NUTS runs only on the LDS-resident path (more points than one
+workgroup holds raise, use ``kernel="hmc"`` or ``stream=True``), with up to 10 doublings and a noise tensor of chains x transitions x
 (D + 3 max_depth + 2 (2^max_depth - 1)) doubles of at most 2 GiB.  Both use a unit mass matrix in xi (no learned mass matrix);
 logistic and Poisson only (the linreg / Gaussian posteriors are closed-form and sampled exactly by their own samplers), D <= 32,
 one device.  There is no CPU fallback."""
@@ -133,7 +135,8 @@ def log_joint_grad(family, pts, wts, thetas, device="cuda"):
 class DeviceHMC(_DeviceNormals):
     STEP0 = 0.5        # the step the dual averaging starts from (the whitened target is near N(0, I))
 
-    def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda", *, device_frame=False, kernel="hmc", max_depth=8):
+    def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda", *, device_frame=False, kernel="hmc", max_depth=8,
+                 stream=False):
         if family not in FAMILIES:
             raise ValueError("family must be 'logistic' or 'poisson'")
         if not 1 <= int(D) <= DMAX:
@@ -144,6 +147,8 @@ class DeviceHMC(_DeviceNormals):
             raise ValueError("DeviceHMC: kernel must be 'hmc' or 'nuts', not %r" % (kernel,))
         if not 1 <= int(max_depth) <= NUTS_DEPTH_MAX:
             raise ValueError("DeviceHMC: max_depth = %d (1 <= max_depth <= %d)" % (max_depth, NUTS_DEPTH_MAX))
+        if stream and kernel != "nuts":
+            raise ValueError("DeviceHMC: stream=True selects the streamed NUTS (kernel=\"nuts\"); kernel=\"hmc\" streams on its own")
         import torch
         from . import _native
         self._torch, self._nat = torch, _native
@@ -154,6 +159,8 @@ class DeviceHMC(_DeviceNormals):
         self.device = torch.device(device)
         self.D, self.chains, self.leapfrog = int(D), int(chains), int(leapfrog)
         self.kernel, self.max_depth = kernel, int(max_depth)
+        self.stream = bool(stream)                          # kernel="nuts": rows past one workgroup's LDS take csrc/nuts_stream.hip
+        self._scratch = None                                # (its scratch: the sampler's, grown on demand)
         self.ld = self.D + (self.D % 2)
         self.cols = self.D + (1 if family == "poisson" else 0)
         self._seed, self._offset = (0 if seed is None else int(seed)) & 0xFFFFFFFFFFFFFFFF, 0
@@ -166,7 +173,7 @@ class DeviceHMC(_DeviceNormals):
         return bool(self._lib.bcx_hmc_coreset_ok(int(k), self.D))
 
     def nuts_path(self, k):
-        """Whether k points fit the NUTS kernel (``kernel="nuts"``: the only path it has)."""
+        """Whether k points fit the LDS-resident NUTS kernel (``kernel="nuts"``: the only path it has without ``stream=True``)."""
         return bool(self._lib.bcx_nuts_coreset_ok(int(k), self.D))
 
     def _default_frame(self, k, pts, wts, Z=None, w=None):
@@ -199,8 +206,9 @@ class DeviceHMC(_DeviceNormals):
         k = 0 if pts is None else len(pts)
         nuts = self.kernel == "nuts"
         R = D + 3 * self.max_depth + 2 * ((1 << self.max_depth) - 1) if nuts else D + 3
+        nuts_streamed = nuts and self.stream and (bool(_dev_force_stream) or not self.nuts_path(k))
         if nuts:
-            if _dev_force_stream or not self.nuts_path(k):
+            if not self.stream and (_dev_force_stream or not self.nuts_path(k)):
                 raise ValueError("DeviceHMC: there is no streamed NUTS -- %d points of %d parameters do not fit the LDS of one workgroup "
                                  "(or the streamed path was forced); use kernel=\"hmc\"" % (k, D))
             if 8 * C * T * R > NUTS_NOISE_BYTES_MAX:
@@ -219,7 +227,7 @@ class DeviceHMC(_DeviceNormals):
         Wm = None if transform is None else np.ascontiguousarray(transform, dtype=np.float64).reshape(D, D)
         mu_dev = torch.from_numpy(mu).to(self.device)
         W_dev = None if Wm is None else torch.from_numpy(Wm).to(self.device)
-        streamed = not nuts and (bool(_dev_force_stream) or not self.coreset_path(k))
+        streamed = nuts_streamed or (not nuts and (bool(_dev_force_stream) or not self.coreset_path(k)))
         if streamed and C > STREAM_CHAINS_MAX:
             raise ValueError("DeviceHMC: the streamed path takes at most %d chains" % STREAM_CHAINS_MAX)
         noise = self._normal(C, T, R)
@@ -237,7 +245,16 @@ class DeviceHMC(_DeviceNormals):
             stream = int(torch.cuda.current_stream(self.device).cuda_stream)
             torch.cuda.synchronize(self.device)
             t0 = time.perf_counter()
-            if nuts:
+            if nuts_streamed:
+                fixed = 0.0 if _dev_step_size is None else float(_dev_step_size)
+                nbytes = int(lib.bcx_nuts_stream_scratch_bytes(k, D, C, self.max_depth))
+                if self._scratch is None or self._scratch.numel() * 8 < nbytes:
+                    self._scratch = torch.empty(nbytes // 8 + 1, **f64)
+                rc = lib.bcx_nuts_stream(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, ptr(mu_dev), ptr(W_dev), D,
+                                         C, n_warmup, n_samples, self.max_depth, self.STEP0, fixed, noise.data_ptr(), R, ld,
+                                         samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(), eps.data_ptr(),
+                                         self._status.data_ptr(), self._scratch.data_ptr(), nbytes)
+            elif nuts:
                 fixed = 0.0 if _dev_step_size is None else float(_dev_step_size)
                 rc = lib.bcx_nuts_coreset(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, ptr(mu_dev), ptr(W_dev), D,
                                           C, n_warmup, n_samples, self.max_depth, self.STEP0, fixed, noise.data_ptr(), R, ld,
@@ -254,6 +271,8 @@ class DeviceHMC(_DeviceNormals):
             torch.cuda.synchronize(self.device)
             seconds = time.perf_counter() - t0
         st = self._status.cpu().numpy()
+        if st[0] == 3:
+            raise self._nat.EngineError(self._nat.ERR_TIMEOUT, "NUTS on the device: a wait between the workgroups of the streamed launch expired")
         if st[0] == 2:
             raise self._nat.EngineError(self._nat.ERR_STATE, "HMC on the device: the log joint at the start is not finite (NaN weights or points)")
         out = samples[:, n_warmup:, :D].cpu().numpy()

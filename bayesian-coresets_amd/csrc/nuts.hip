@@ -20,10 +20,7 @@
 #include <string>
 #include "bcx_internal.h"
 #include "hmc_core.h"
-
-#define NUTS_JMAX 10
-#define NUTS_DIAG 8
-#define NUTS_DIVERGENT -1000.0
+#include "nuts_core.h"
 
 void bcx_project_set_error(const std::string& msg);   // proj.hip
 
@@ -34,16 +31,7 @@ struct NutsArgs {
   int64_t ldp, noise_ld;
   int family, k, J;
 };
-struct NutsTree {
-  double xl[32], pl[32], gl[32], xr[32], pr[32], gr[32];     // the tree's endpoints: xi, momentum, xi-gradient
-  double gm[32];                                             // the xi-gradient at the moving end (its xi and momentum: S.s.xp, S.s.p)
-  double xs[32], gs[32], ths[32];                            // the doubling's proposal: xi, xi-gradient, theta
-  double ckx[NUTS_JMAX][32], ckp[NUTS_JMAX][32];             // checkpoints: xi and momentum of even leaves, slot popcount(leaf)
-};
-
-static __device__ __forceinline__ double nuts_logaddexp(double a, double b) { return fmax(a, b) + log1p(exp(-fabs(a - b))); }
-static __device__ __forceinline__ double nuts_threshold(const double* z) { return 0.5 * (z[0] * z[0] + z[1] * z[1]); }
-
+// (NutsTree, nuts_logaddexp, nuts_threshold and the limits: csrc/nuts_core.h, shared with csrc/nuts_stream.hip)
 __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(NutsArgs a) {
   extern __shared__ __attribute__((aligned(16))) double nuts_dyn[];
   __shared__ HmcLds S;

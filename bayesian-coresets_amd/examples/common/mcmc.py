@@ -1,16 +1,17 @@
 """MCMC for the experiments' evaluation: the role of the reference's examples/common/mcmc.py:60-70 (`run`: Stan on the data
 with per-point weights, as many warm-up as sampling iterations), on ``bc.DeviceHMC`` -- Hamiltonian Monte Carlo on the GPU,
 whitened by the Laplace approximation of the same weighted posterior; ``kernel="nuts"``: its No-U-Turn transition (Stan's
-sampler) where the rows fit one workgroup's LDS, i.e. on coresets."""
+sampler) where the rows fit one workgroup's LDS, i.e. on coresets; with ``nuts_stream=True`` on any rows (the streamed NUTS of
+csrc/nuts_stream.hip: larger coresets, the full data set)."""
 import numpy as np
 
 FAMILY = {"lr": "logistic", "poiss": "poisson"}
 MIN_WARMUP = 200
 
 
-def run(Z, wts, n_samples, model_name, seed, chains=64, leapfrog=8, device="cuda", kernel="hmc", max_depth=8):
+def run(Z, wts, n_samples, model_name, seed, chains=64, leapfrog=8, device="cuda", kernel="hmc", max_depth=8, nuts_stream=False):
     """(samples (n_samples x D), seconds, the kernel that ran -- "nuts" only where it was asked for and the rows fit its
-    LDS-resident path, else "hmc" with ``leapfrog`` steps): ``n_samples`` draws from the posterior of the rows ``Z`` (host array or device
+    LDS-resident path or ``nuts_stream`` lets the others stream, else "hmc" with ``leapfrog`` steps): ``n_samples`` draws from the posterior of the rows ``Z`` (host array or device
     tensor, the model's layout; None / empty: the prior) with weights ``wts`` (None: ones), pooled over ``chains`` chains
     that each warm up for as long as they sample (at least MIN_WARMUP transitions)."""
     import bayesiancoresets_amd as bc
@@ -20,9 +21,10 @@ def run(Z, wts, n_samples, model_name, seed, chains=64, leapfrog=8, device="cuda
         raise ValueError("mcmc.run: no rows (the prior needs no sampler)")
     D = Z.shape[1] - (1 if family == "poisson" else 0)
     per_chain = -(-int(n_samples) // chains)
-    hmc = bc.DeviceHMC(family, D, chains=chains, leapfrog=leapfrog, seed=seed, device=device, kernel=kernel, max_depth=max_depth)
+    hmc = bc.DeviceHMC(family, D, chains=chains, leapfrog=leapfrog, seed=seed, device=device, kernel=kernel, max_depth=max_depth,
+                       stream=bool(nuts_stream) and kernel == "nuts")
     ran = kernel
-    if kernel == "nuts" and not hmc.nuts_path(k):
+    if kernel == "nuts" and not hmc.stream and not hmc.nuts_path(k):
         hmc = bc.DeviceHMC(family, D, chains=chains, leapfrog=leapfrog, seed=seed, device=device)
         ran = "hmc"
     res = hmc.sample(Z, wts, per_chain, max(per_chain, MIN_WARMUP))

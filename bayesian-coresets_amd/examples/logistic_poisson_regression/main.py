@@ -20,7 +20,8 @@ bc.DeviceHMC (examples/common/mcmc.py; `--mcmc_samples_full` / `--mcmc_samples_c
 (the mean squared difference of the coreset's and the full data's log-joint gradients over the full-data draws, two
 bc.log_joint_grad calls), `full_mcmc_time_per_itr`, `mcmc_time_per_itr`.  `--mcmc_kernel nuts` samples every coreset's posterior
 with the No-U-Turn transition (bc.DeviceHMC(kernel="nuts"): Stan's sampler; a coreset past one workgroup's LDS falls back to HMC);
-the full-data chain stays HMC."""
+the full-data chain stays HMC.  `--mcmc_kernel nuts --mcmc_nuts_stream`: coresets past the LDS and the full-data chain run the
+streamed NUTS (bc.DeviceHMC(kernel="nuts", stream=True)); the full-data cache file then carries the kernel in its name."""
 import argparse
 import os
 import sys
@@ -57,15 +58,21 @@ def load(a, rs):
     return model_poiss.synthetic_rows(a.data_num, a.data_dim, rs)
 
 
-def full_data_samples(a, Z):
-    """The full-data draws and the sampler's time per iteration, cached per model / data set / trial (main.py:107-127)."""
+def full_data_samples(a, Z, nuts_stream=False):
+    """The full-data draws and the sampler's time per iteration, cached per model / data set / trial (main.py:107-127) -- and per
+    kernel when the full-data chain is the streamed NUTS: a cached HMC run is never read as a NUTS one, nor the reverse."""
     folder = os.path.join(a.results_folder, "mcmc_cache")
-    name = "full_samples_%s_%s_%d_%d_%d_%d.npz" % (a.model, os.path.basename(a.dataset), a.data_num, a.data_dim, a.trial, a.mcmc_samples_full)
+    name = "full_samples_%s_%s_%d_%d_%d_%d%s.npz" % (a.model, os.path.basename(a.dataset), a.data_num, a.data_dim, a.trial, a.mcmc_samples_full,
+                                                     "_nuts" if nuts_stream else "")
     path = os.path.join(folder, name)
     if os.path.exists(path):
         d = np.load(path)
         return d["samples"], float(d["t"])
-    samples, t, _ = mcmc.run(Z, None, a.mcmc_samples_full, a.model, a.trial)
+    if nuts_stream:
+        samples, t, ran = mcmc.run(Z, None, a.mcmc_samples_full, a.model, a.trial, kernel="nuts", nuts_stream=True)
+        print("full-data chain: %s" % ran)
+    else:
+        samples, t, _ = mcmc.run(Z, None, a.mcmc_samples_full, a.model, a.trial)
     t_per_itr = t / (a.mcmc_samples_full * 2)                                  # (main.py:123-124: warm-up = sampling)
     os.makedirs(folder, exist_ok=True)
     np.savez(path, samples=samples, t=t_per_itr)
@@ -79,6 +86,9 @@ def run(a):
     mcmc_kernel = getattr(a, "mcmc_kernel", "hmc")
     if mcmc_kernel == "hmc" and hasattr(a, "mcmc_kernel"):
         delattr(a, "mcmc_kernel")       # (likewise, given explicitly: the default sampler's result files keep their names)
+    nuts_stream = bool(getattr(a, "mcmc_nuts_stream", False))      # (absent unless given: the parser suppresses its default)
+    if nuts_stream and not (use_mcmc and mcmc_kernel == "nuts"):
+        raise ValueError("--mcmc_nuts_stream goes with --eval mcmc --mcmc_kernel nuts")
     stream = bool(getattr(a, "laplace_stream", False))     # (absent unless given: the parser suppresses its default)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
@@ -150,7 +160,7 @@ def run(a):
     n = Ms.shape[0]
     extra = {}
     if use_mcmc:
-        full_samples, full_t = full_data_samples(a, Z)
+        full_samples, full_t = full_data_samples(a, Z, nuts_stream)
         mup, Sigp = full_samples.mean(axis=0), np.cov(full_samples, rowvar=False)     # main.py:137-138
         SigpInv = np.linalg.inv(Sigp)
         _, gfs = bc.log_joint_grad(family, Z, None, full_samples)
@@ -167,7 +177,8 @@ def run(a):
         csizes[m] = (wts > 0).sum()
         if use_mcmc:
             if csizes[m] > 0:
-                cst, t_cst, _ = mcmc.run(pts[wts > 0], wts[wts > 0], a.mcmc_samples_coreset, a.model, a.trial, kernel=mcmc_kernel)
+                cst, t_cst, _ = mcmc.run(pts[wts > 0], wts[wts > 0], a.mcmc_samples_coreset, a.model, a.trial, kernel=mcmc_kernel,
+                                           nuts_stream=nuts_stream)
             else:
                 cst, t_cst = np.random.RandomState(a.trial).randn(a.mcmc_samples_coreset, D), 0.0      # the prior
             muw, Sigw = cst.mean(axis=0), np.cov(cst, rowvar=False)
@@ -204,6 +215,9 @@ def parser():
     ap.add_argument("--mcmc_kernel", type=str, choices=["hmc", "nuts"], default=argparse.SUPPRESS,    # (absent = hmc: result files keep their argument set)
                     help="--eval mcmc: the transition on every coreset's posterior, default hmc (nuts: bc.DeviceHMC(kernel='nuts')); the full "
                          "data stays HMC")
+    ap.add_argument("--mcmc_nuts_stream", action="store_true", default=argparse.SUPPRESS,   # (result files keep their argument set)
+                    help="with --mcmc_kernel nuts: coresets past one workgroup's LDS and the full-data chain run the streamed NUTS "
+                         "(bc.DeviceHMC(kernel='nuts', stream=True))")
     ap.add_argument("--proj_dim", type=int, default=500)
     ap.add_argument("--coreset_size_max", type=int, default=1000)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)

@@ -569,7 +569,7 @@ int bcx_hmc_stream(void* stream, int32_t family, int64_t N, int32_t D, const voi
                    void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev, void* work_dev,
                    int64_t work_bytes);
 /* The No-U-Turn sampler (Hoffman & Gelman 2014) on the same target, frame and start as bcx_hmc_coreset, for the (k, D) that fit one
- * workgroup's LDS (csrc/nuts.hip; there is no streamed NUTS): ONE launch, a workgroup per chain, no leapfrog count to choose.
+ * workgroup's LDS (csrc/nuts.hip; any N: bcx_nuts_stream below): ONE launch, a workgroup per chain, no leapfrog count to choose.
  * With J = max_depth (1 .. 10), transition t of chain c reads R = D + 3 J + 2 (2^J - 1) standard normals at
  * noise_dev[(c T + t) noise_ld ..] (noise_ld >= R): D momenta; per doubling j the direction (>= 0: forward) and two for the
  * threshold e_j = (a^2 + b^2) / 2; per leaf slot 2^j - 1 + i two for e_leaf.  Doubling j takes 2^j leapfrog steps of the base
@@ -588,6 +588,21 @@ int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t D, const v
                      int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
                      void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
                      void* status_dev);
+/* The same transition, noise layout, outputs and diagnostics for any N (rows past one workgroup's LDS, the resident full data set)
+ * and at most 256 chains (csrc/nuts_stream.hip): ONE persistent launch of G = max(1, min(128-row tiles of N, CUs, 256)) co-resident
+ * workgroups.  A round evaluates one leaf of every chain still running: all workgroups pass over their rows for the active chains
+ * and leave one partial record each, a grid barrier, the chain's owner (workgroup c mod G) adds the records in workgroup order and
+ * moves the chain's NUTS state machine one leaf on, a second barrier.  No floating-point atomics: the same inputs on the same device
+ * give the same bits.  Every barrier wait is bounded.  scratch_dev: bcx_nuts_stream_scratch_bytes(N, D, chains, max_depth) bytes
+ * (-1: N < 0, D outside 1 .. 32, chains outside 1 .. 256, max_depth outside 1 .. 10).  BCX_ERR_STATE when the device cannot hold
+ * the workgroups together.  status_dev[0]: 0 ok / 1 a leaf's energy was not finite / 2 the log joint at the start is not finite / 3
+ * a barrier wait expired (the outputs are then incomplete); [1]: the worst [0] since the caller zeroed it. */
+int64_t bcx_nuts_stream_scratch_bytes(int64_t N, int32_t D, int32_t chains, int32_t max_depth);
+int bcx_nuts_stream(void* stream, int32_t family, int64_t N, int32_t D, const void* w_dev, const void* Z_dev, int64_t ldz,
+                    const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                    int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
+                    void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
+                    void* status_dev, void* scratch_dev, int64_t scratch_bytes);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 

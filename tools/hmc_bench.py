@@ -4,8 +4,12 @@ to the NumPy restatement's time per transition on the host (tests/hmc_restatemen
 fp64-VALU model.  One JSON line per case.  `--kernel nuts`: the coreset cases only, every one with the NUTS
 kernel (csrc/nuts.hip, max_depth 8) beside the HMC kernel at L = 8 from the same run -- time per leaf (one target evaluation), time
 per transition, mean tree depth, mean leapfrog steps, effective samples per second pooled over the chains.
+`--kernel nuts --stream`: the streamed NUTS (csrc/nuts_stream.hip) at k = 4096 and N = 1M, D = 10, 64 and 256 chains,
+each beside the streamed HMC at L = 8 on the same rows, the two alternating -- time per round (one leaf of every running chain), time
+per transition, the rounds of the launch over the mean leaves per chain (the price of ending with the slowest chain), effective
+samples per second, and the passes' share of the fp64-VALU model of DESIGN.md 4.12.
 
-    python tools/hmc_bench.py [--quick] [--kernel nuts]
+    python tools/hmc_bench.py [--quick] [--kernel nuts [--stream]]
 """
 import json
 import os
@@ -84,6 +88,39 @@ def case_nuts(bc, name, pts, wts, chains, n, center, transform, hmc_res):
     return rows
 
 
+def case_stream(bc, name, pts, wts, chains, n, center, transform, reps=2):
+    """Streamed HMC and streamed NUTS on the same rows, alternating.  A round of the NUTS launch is one pass over the rows for
+    the chains still running and one leaf of each; the launch takes 1 + (the most leaves any chain took) rounds."""
+    D, N = pts.shape[1], int(pts.shape[0])
+    hmc = bc.DeviceHMC("logistic", D, chains=chains, leapfrog=L, seed=1)
+    nuts = bc.DeviceHMC("logistic", D, chains=chains, seed=1, kernel="nuts", max_depth=8, stream=True)
+    kw = dict(center=center, transform=transform, _dev_force_stream=True)
+    hmc.sample(pts, wts, 2, 2, **kw)                                               # (first-use costs)
+    nuts.sample(pts, wts, 2, 2, **kw)
+    rate = 256 * 4 * 16 * 2.4e9                                                    # fp64 lane-operations per second (DESIGN.md 4.12)
+    for rep in range(reps):
+        for kernel, smp in (("hmc", hmc), ("nuts", nuts)):
+            r = smp.sample(pts, wts, n, n, **kw)
+            assert r.streamed
+            total = r.seconds_per_iteration * 2 * n
+            ess = np.mean([ess_per_chain(r.samples[c, :, j]) for c in range(min(chains, 16)) for j in range(D)]) * chains
+            row = dict(case=name, kernel=kernel, rep=rep, N=N, D=D, chains=chains, transitions=2 * n, us_per_transition=total * 1e6 / (2 * n),
+                       accept=float(r.accept_rate.mean()), step=float(r.step_size.mean()), rhat_max=float(np.nanmax(r.rhat)),
+                       ess_per_second=float(ess / total))
+            if kernel == "nuts":
+                leaves = r.leapfrog_total.astype(np.float64)
+                rounds = float(leaves.max()) + 1.0
+                evals = float((leaves + 1.0).sum())                                # chain evaluations of all passes
+                row.update(rounds=rounds, us_per_round=total * 1e6 / rounds, mean_leaves_per_chain=float(leaves.mean()),
+                           rounds_over_mean_leaves=rounds / float(leaves.mean()), mean_tree_depth=float(r.tree_depth.mean()),
+                           mean_leapfrogs=float(r.n_leapfrog.mean()), mean_active_chains=evals / rounds,
+                           pass_fraction_of_valu_model=evals * N * (100 + 2 * D) / rate / total)
+            else:
+                evals = chains * (2.0 * n * L + 1.0)
+                row.update(us_per_leapfrog=total * 1e6 / (2 * n * L), pass_fraction_of_valu_model=evals * N * (100 + 2 * D) / rate / total)
+            print(json.dumps(row), flush=True)
+
+
 def host_baseline(pts, wts, center, transform, n=30):
     D = pts.shape[1]
     host = pts.cpu().numpy() if hasattr(pts, "cpu") else pts
@@ -101,6 +138,18 @@ def main():
     nuts = "--kernel" in sys.argv and sys.argv[sys.argv.index("--kernel") + 1:][:1] == ["nuts"]
     rs = np.random.RandomState(0)
     D = 10
+    if nuts and "--stream" in sys.argv:
+        k = 4096
+        pts, wts = data(k, D, rs), rs.uniform(1.0, 50.0, k)
+        mu, cov = model_lr.laplace_fit(pts, wts)
+        for chains in (64, 256):
+            case_stream(bc, "k=%d" % k, pts, wts, chains, 50 if quick else 200, mu, np.linalg.cholesky(cov).T)
+        N = 100000 if quick else 1000000
+        Z = torch.from_numpy(data(N, D, rs)).cuda()
+        mu, cov = model_lr.laplace_fit(Z)
+        for chains in (64, 256):
+            case_stream(bc, "N=%d" % N, Z, None, chains, 10 if quick else 50, mu, np.linalg.cholesky(cov).T)
+        return
     for k in (30, 300, 1000):
         pts, wts = data(k, D, rs), rs.uniform(1.0, 50.0, k)
         mu, cov = model_lr.laplace_fit(pts, wts)
