@@ -89,6 +89,17 @@ def _device_rows(torch, device, pts, cols, what):
     return t
 
 
+def _device_weights(torch, device, wts, n, who):
+    """The n weights as a contiguous fp64 device tensor; None (ones) without weights or points."""
+    if wts is None or not n:
+        return None
+    w = wts.to(device=device, dtype=torch.float64).contiguous() if isinstance(wts, torch.Tensor) else \
+        torch.from_numpy(np.ascontiguousarray(wts, dtype=np.float64)).to(device)
+    if w.shape != (n,):
+        raise ValueError("%s: %d weights for %d points" % (who, w.numel(), n))
+    return w
+
+
 def log_joint_grad(family, pts, wts, thetas, device="cuda"):
     """(values (C), gradients (C x D)) of the weighted log joint at the rows of ``thetas`` -- ndarrays, or device tensors when
     ``thetas`` is one.  ``pts``: rows y x (logistic) or [x, y] (Poisson), host array or device tensor; ``wts=None``: ones."""
@@ -112,12 +123,7 @@ def log_joint_grad(family, pts, wts, thetas, device="cuda"):
     cols = D + (1 if family == "poisson" else 0)
     N = 0 if pts is None else len(pts)
     Z = _device_rows(torch, device, pts, cols, "points") if N else None
-    w = None
-    if wts is not None and N:
-        w = wts.to(device=device, dtype=torch.float64).contiguous() if isinstance(wts, torch.Tensor) else \
-            torch.from_numpy(np.ascontiguousarray(wts, dtype=np.float64)).to(device)
-        if w.shape != (N,):
-            raise ValueError("log_joint_grad: %d weights for %d points" % (w.numel(), N))
+    w = _device_weights(torch, device, wts, N, "log_joint_grad")
     value = torch.empty(C, dtype=torch.float64, device=device)
     grad = torch.empty(C, D, dtype=torch.float64, device=device)
     work = torch.empty(max(int(lib.bcx_log_joint_grad_scratch_bytes(N, D, C)), 8) // 8, dtype=torch.float64, device=device)
@@ -209,18 +215,13 @@ class DeviceHMC(_DeviceNormals):
         nuts_streamed = nuts and self.stream and (bool(_dev_force_stream) or not self.nuts_path(k))
         if nuts:
             if not self.stream and (_dev_force_stream or not self.nuts_path(k)):
-                raise ValueError("DeviceHMC: there is no streamed NUTS -- %d points of %d parameters do not fit the LDS of one workgroup "
-                                 "(or the streamed path was forced); use kernel=\"hmc\"" % (k, D))
+                raise ValueError("DeviceHMC: NUTS without `stream=True` runs only where the points fit one workgroup's LDS; pass "
+                                 "`stream=True` or `kernel=\"hmc\"`")
             if 8 * C * T * R > NUTS_NOISE_BYTES_MAX:
                 raise ValueError("DeviceHMC: the NUTS noise (chains x transitions x %d doubles = %d bytes) exceeds 2 GiB; lower max_depth "
                                  "(%d), chains (%d) or the number of transitions (%d)" % (R, 8 * C * T * R, self.max_depth, C, T))
         Z = _device_rows(torch, self.device, pts, self.cols, "points") if k else None
-        w = None
-        if wts is not None and k:
-            w = wts.to(device=self.device, dtype=torch.float64).contiguous() if isinstance(wts, torch.Tensor) else \
-                torch.from_numpy(np.ascontiguousarray(wts, dtype=np.float64)).to(self.device)
-            if w.shape != (k,):
-                raise ValueError("DeviceHMC.sample: %d weights for %d points" % (w.numel(), k))
+        w = _device_weights(torch, self.device, wts, k, "DeviceHMC.sample")
         if center is None and transform is None:
             center, transform = self._default_frame(k, pts, wts, Z, w)
         mu = np.zeros(D) if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(D)
@@ -238,34 +239,35 @@ class DeviceHMC(_DeviceNormals):
         diag = torch.empty(C, T, NUTS_DIAG if nuts else DIAG, **f64)
         acc, eps = torch.empty(C, **f64), torch.empty(C, **f64)
         ptr = lambda t: None if t is None else t.data_ptr()
-        common = [ptr(mu_dev), ptr(W_dev), D, C, n_warmup, n_samples, self.leapfrog, self.STEP0,
-                  0.0 if _dev_step_size is None else float(_dev_step_size), noise.data_ptr(), ld, samples.data_ptr(), ptr(xis), ptr(props),
-                  diag.data_ptr(), acc.data_ptr(), eps.data_ptr(), self._status.data_ptr()]
+        fixed = 0.0 if _dev_step_size is None else float(_dev_step_size)
+
+        def native_args(stream, *scratch):
+            # the four entry points' arguments.  Head: stream, family, k, D, weights, rows, row stride.  Tail: frame, counts, steps,
+            # noise, outputs, status.  In between what differs: the leapfrog count, or max_depth and (behind the noise) its row length
+            # R; the streamed ones end with their scratch and its bytes.
+            depth_or_leapfrog, noise_ld = (self.max_depth, [R]) if nuts else (self.leapfrog, [])
+            return ([stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, ptr(mu_dev), ptr(W_dev), D, C, n_warmup,
+                     n_samples, depth_or_leapfrog, self.STEP0, fixed, noise.data_ptr()] + noise_ld +
+                    [ld, samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(), eps.data_ptr(), self._status.data_ptr()] +
+                    list(scratch))
+
         with torch.cuda.device(self.device):
             stream = int(torch.cuda.current_stream(self.device).cuda_stream)
             torch.cuda.synchronize(self.device)
             t0 = time.perf_counter()
             if nuts_streamed:
-                fixed = 0.0 if _dev_step_size is None else float(_dev_step_size)
                 nbytes = int(lib.bcx_nuts_stream_scratch_bytes(k, D, C, self.max_depth))
                 if self._scratch is None or self._scratch.numel() * 8 < nbytes:
                     self._scratch = torch.empty(nbytes // 8 + 1, **f64)
-                rc = lib.bcx_nuts_stream(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, ptr(mu_dev), ptr(W_dev), D,
-                                         C, n_warmup, n_samples, self.max_depth, self.STEP0, fixed, noise.data_ptr(), R, ld,
-                                         samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(), eps.data_ptr(),
-                                         self._status.data_ptr(), self._scratch.data_ptr(), nbytes)
+                rc = lib.bcx_nuts_stream(*native_args(stream, self._scratch.data_ptr(), nbytes))
             elif nuts:
-                fixed = 0.0 if _dev_step_size is None else float(_dev_step_size)
-                rc = lib.bcx_nuts_coreset(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, ptr(mu_dev), ptr(W_dev), D,
-                                          C, n_warmup, n_samples, self.max_depth, self.STEP0, fixed, noise.data_ptr(), R, ld,
-                                          samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(), eps.data_ptr(),
-                                          self._status.data_ptr())
+                rc = lib.bcx_nuts_coreset(*native_args(stream))
             elif streamed:
                 nbytes = int(lib.bcx_hmc_stream_scratch_bytes(k, D, C))
                 work = torch.empty(nbytes // 8 + 1, **f64)
-                rc = lib.bcx_hmc_stream(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, *(common + [work.data_ptr(), nbytes]))
+                rc = lib.bcx_hmc_stream(*native_args(stream, work.data_ptr(), nbytes))
             else:
-                rc = lib.bcx_hmc_coreset(stream, self._fam, k, D, ptr(w), ptr(Z), Z.stride(0) if k else self.cols, *common)
+                rc = lib.bcx_hmc_coreset(*native_args(stream))
             if rc != 0:
                 raise self._nat.EngineError(rc, lib.bcx_project_last_error().decode())
             torch.cuda.synchronize(self.device)

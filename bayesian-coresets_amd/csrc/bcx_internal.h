@@ -237,6 +237,8 @@ bool bcx_screen_on(const bcx_solver* s);
 int bcx_screen_build(bcx_solver* s);
 int bcx_launch_screen(bcx_solver* s);
 int bcx_launch_resume_store(bcx_solver* s);
+// proj.hip: sets the message bcx_project_last_error() returns (the entry points outside the solver report through it)
+void bcx_project_set_error(const std::string& msg);
 
 #ifdef BCX_TIMING
 #define BCX_STAMP(st, i) do { if (threadIdx.x == 0) (st)->dbg_t[i] = wall_clock64(); } while (0)

@@ -18,7 +18,6 @@
 #include "bcx_internal.h"
 #include "dev_util.h"
 
-void bcx_project_set_error(const std::string& msg);   // proj.hip
 
 #define GS_HIP(call)                                                              \
   do {                                                                            \

@@ -19,11 +19,11 @@
 // two for the accept threshold e = (z1^2 + z2^2) / 2 ~ Exp(1) (accept iff dH <= e), one for the step jitter
 // eps_t = eps exp(0.1 z).  A fixed number L of leapfrog steps; the warm-up adapts eps per chain by dual averaging (Hoffman &
 // Gelman 2014, Alg. 5: delta 0.8, gamma 0.05, t0 10, kappa 0.75), sampling uses the averaged step.
-#include <atomic>
 #include <math.h>
 #include <string>
 #include "bcx_internal.h"
 #include "hmc_core.h"
+#include "launch_host.h"
 
 #define HMC_STEP_THREADS 64
 #define HMC_DIAG 6
@@ -32,8 +32,6 @@
 #define LJ_MAX_WG 512        // workgroups along the rows (the second level adds that many partials per output)
 #define LJ_CCHUNK 256        // theta columns of one launch (bounds the partials)
 #define HMC_STREAM_CMAX LJ_CCHUNK
-
-void bcx_project_set_error(const std::string& msg);   // proj.hip
 
 // ---------------------------------------------------------------------------------------------------------------- log joint
 struct LjArgs {
@@ -280,58 +278,24 @@ __global__ __launch_bounds__(HMC_THREADS) void hmc_coreset_kernel(HmcCoresetArgs
     for (int l = 1; l <= a.par.L; ++l) hmc_consume(S, a.par, chain, l, t, eval());
 }
 
-static bool hmc_common_ok(int32_t family, int32_t D, int32_t chains, int32_t n_warmup, int32_t n_samples, int32_t leapfrog, double eps0,
-                          int32_t ld, const void* noise, const void* samples, const void* diag, const void* acc, const void* eps,
-                          const void* status) {
-  return (family == LAP_LOGISTIC || family == LAP_POISSON) && D >= 1 && D <= HMC_DMAX && chains >= 1 && n_warmup >= 0 && n_samples >= 0 &&
-         n_warmup + n_samples >= 1 && leapfrog >= 1 && eps0 > 0.0 && ld >= D && ld <= 32 && noise && samples && diag && acc && eps && status;
-}
-static HmcPar hmc_par(int32_t D, const void* mu, const void* W, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples, int32_t leapfrog,
-                      double eps0, double fixed_eps, const void* noise, int32_t ld, void* samples, void* xi, void* prop, void* diag,
-                      void* acc, void* eps, void* status) {
-  HmcPar p;
-  p.mu = (const double*)mu; p.W = (const double*)W; p.noise = (const double*)noise; p.samples = (double*)samples; p.xis = (double*)xi;
-  p.props = (double*)prop; p.diag = (double*)diag; p.accept_rate = (double*)acc; p.eps_final = (double*)eps; p.status = (int*)status;
-  p.eps0 = eps0; p.fixed_eps = fixed_eps; p.ldw = ldw; p.D = D; p.ld = ld; p.L = leapfrog; p.T = n_warmup + n_samples; p.nwarm = n_warmup;
-  p.C = chains;
-  return p;
-}
-
+// (the entry points' shared argument check and HmcPar fill, hmc_common_ok and hmc_par: csrc/hmc_core.h)
 extern "C" int64_t bcx_hmc_coreset_lds_bytes(int32_t k, int32_t D) {
   if (k < 0 || D < 1 || D > HMC_DMAX) return -1;
   return hmc_points_lds_bytes(k, D);
 }
-// dynamic LDS one workgroup of the coreset kernel may have: the device's limit minus the kernel's static use (-1: no device)
-static int64_t hmc_coreset_lds_room() {
-  static std::atomic<int64_t> room[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  int64_t r = room[dev].load(std::memory_order_acquire);
-  if (r != 0) return r;
-  int maxb = 0;
-  hipFuncAttributes fa;
-  if (hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
-      hipFuncGetAttributes(&fa, (const void*)hmc_coreset_kernel) != hipSuccess) {
-    (void)hipGetLastError();
-    return -1;
-  }
-  r = (int64_t)maxb - (int64_t)fa.sharedSizeBytes;
-  if (r <= 0) r = -1;
-  room[dev].store(r, std::memory_order_release);
-  return r;
-}
 // 1 when one workgroup can hold the k points (D <= 32, the points and three doubles each within the LDS the device gives a
 // workgroup, less what the kernel uses itself)
 extern "C" int bcx_hmc_coreset_ok(int32_t k, int32_t D) {
+  static PerDevice<int64_t> room;
   const int64_t b = bcx_hmc_coreset_lds_bytes(k, D);
-  return b >= 0 && b <= hmc_coreset_lds_room();
+  return b >= 0 && b <= lds_room((const void*)hmc_coreset_kernel, room);
 }
 extern "C" int bcx_hmc_coreset(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
                                const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
                                int32_t leapfrog, double eps0, double fixed_eps, const void* noise_dev, int32_t ld, void* samples_dev,
                                void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev) {
-  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, leapfrog, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev,
-                     status_dev) || !bcx_hmc_coreset_ok(k, D) || (W_dev && ldw < D) ||
+  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
+      leapfrog < 1 || !bcx_hmc_coreset_ok(k, D) || (W_dev && ldw < D) ||
       (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0)))) {
     bcx_project_set_error("bcx_hmc_coreset: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, the points within "
                           "bcx_hmc_coreset_ok, at least one transition and leapfrog step, eps0 > 0)");
@@ -343,17 +307,10 @@ extern "C" int bcx_hmc_coreset(void* stream, int32_t family, int32_t k, int32_t 
   a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.ldp = ldp; a.family = family; a.k = k;
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)bcx_hmc_coreset_lds_bytes(k, D);
-  if (lds > 16 * 1024) {
-    static std::atomic<size_t> lds_max[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > lds_max[dev].load(std::memory_order_acquire)) {
-      if (hipFuncSetAttribute((const void*)hmc_coreset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        bcx_project_set_error("bcx_hmc_coreset: hipFuncSetAttribute failed");
-        return BCX_ERR_HIP;
-      }
-      lds_max[dev].store(lds, std::memory_order_release);
-    }
+  static PerDevice<size_t> lds_max;
+  if (raise_dynamic_lds((const void*)hmc_coreset_kernel, lds, 16 * 1024, lds_max) != hipSuccess) {
+    bcx_project_set_error("bcx_hmc_coreset: hipFuncSetAttribute failed");
+    return BCX_ERR_HIP;
   }
   if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_hmc_coreset: memset failed"); return BCX_ERR_HIP; }
   hipLaunchKernelGGL(hmc_coreset_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);
@@ -415,8 +372,8 @@ extern "C" int bcx_hmc_stream(void* stream, int32_t family, int64_t N, int32_t D
                               int32_t leapfrog, double eps0, double fixed_eps, const void* noise_dev, int32_t ld, void* samples_dev,
                               void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev, void* work_dev,
                               int64_t work_bytes) {
-  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, leapfrog, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev,
-                     status_dev) || chains > HMC_STREAM_CMAX || N < 0 || (W_dev && ldw < D) || !work_dev ||
+  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
+      leapfrog < 1 || chains > HMC_STREAM_CMAX || N < 0 || (W_dev && ldw < D) || !work_dev ||
       work_bytes < bcx_hmc_stream_scratch_bytes(N, D, chains) || (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0)))) {
     bcx_project_set_error("bcx_hmc_stream: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, at most 256 chains, work_dev of "
                           "bcx_hmc_stream_scratch_bytes, at least one transition and leapfrog step, eps0 > 0)");

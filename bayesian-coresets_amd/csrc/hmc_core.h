@@ -1,6 +1,7 @@
 // hmc_core.h -- what the samplers on the weighted points share: the chain's frame theta = mu + W^T xi, the target with the k
 // points resident in LDS, and the dual averaging of the warm-up.  ONE text for the fixed-length HMC kernels (csrc/hmc.hip) and
-// the NUTS kernel (csrc/nuts.hip).
+// the two NUTS kernels (csrc/nuts.hip, csrc/nuts_stream.hip).  At the end, the host side of the same sharing: the argument check
+// their four entry points start with (hmc_common_ok) and the fill of HmcPar (hmc_par).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -134,4 +135,27 @@ static __device__ __forceinline__ double hmc_eval_points(HmcLds& S, const HmcPoi
   }
   __syncthreads();
   return part[0] - hmc_half_sq(S.s.th, D);
+}
+
+// ------------------------------------------------------------------------------------ host side: what every entry point checks
+// The arguments bcx_hmc_coreset, bcx_hmc_stream, bcx_nuts_coreset and bcx_nuts_stream have in common; each adds its own next to
+// the call (the leapfrog count or the tree depth, where the points are, the scratch).  T = n_warmup + n_samples is formed in 64
+// bits: HmcPar::T is an int.
+static inline bool hmc_common_ok(int32_t family, int32_t D, int32_t chains, int32_t n_warmup, int32_t n_samples, double eps0, int32_t ld,
+                                 const void* noise, const void* samples, const void* diag, const void* acc, const void* eps,
+                                 const void* status) {
+  const int64_t T = (int64_t)n_warmup + n_samples;
+  return (family == LAP_LOGISTIC || family == LAP_POISSON) && D >= 1 && D <= HMC_DMAX && chains >= 1 && n_warmup >= 0 && n_samples >= 0 &&
+         T >= 1 && T <= INT32_MAX && eps0 > 0.0 && ld >= D && ld <= 32 && noise && samples && diag && acc && eps && status;
+}
+// (leapfrog: the fixed number of steps; NUTS passes 0)
+static inline HmcPar hmc_par(int32_t D, const void* mu, const void* W, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                             int32_t leapfrog, double eps0, double fixed_eps, const void* noise, int32_t ld, void* samples, void* xi,
+                             void* prop, void* diag, void* acc, void* eps, void* status) {
+  HmcPar p;
+  p.mu = (const double*)mu; p.W = (const double*)W; p.noise = (const double*)noise; p.samples = (double*)samples; p.xis = (double*)xi;
+  p.props = (double*)prop; p.diag = (double*)diag; p.accept_rate = (double*)acc; p.eps_final = (double*)eps; p.status = (int*)status;
+  p.eps0 = eps0; p.fixed_eps = fixed_eps; p.ldw = ldw; p.D = D; p.ld = ld; p.L = leapfrog; p.T = n_warmup + n_samples; p.nwarm = n_warmup;
+  p.C = chains;
+  return p;
 }

@@ -14,12 +14,12 @@
 // in the linear predictor everywhere: a Newton matrix that is not positive definite gets a multiple of the identity added
 // (ten-fold until the factorisation succeeds).  The mode of the previous call is kept on the device and may seed the next
 // one (warm: the weights of consecutive ADAM steps differ little: 2-3 Newton steps instead of ~10).
-#include <atomic>
 #include <string>
 #include "bcx_internal.h"
 #include "dev_util.h"
 #include "chol32.h"
 #include "lik_point.h"
+#include "launch_host.h"
 
 #define LAP_DMAX 32
 #define LAP_THREADS 256
@@ -189,7 +189,6 @@ __global__ __launch_bounds__(LAP_THREADS) void laplace_sampler_kernel(LapArgs a)
   }
 }
 
-void bcx_project_set_error(const std::string& msg);   // proj.hip
 extern "C" int64_t bcx_laplace_sampler_lds_bytes(int32_t k, int32_t D) {
   if (k < 0 || D < 1 || D > LAP_DMAX) return -1;
   return ((int64_t)k * (D + 1) + 4 * (int64_t)k) * (int64_t)sizeof(double);
@@ -214,17 +213,10 @@ extern "C" int bcx_laplace_sampler(void* stream, int32_t family, int32_t k, int3
   a.Rbar = (const double*)Rbar_dev; a.theta = (double*)theta_dev; a.tbar = (double*)tbar_dev; a.status = (int*)status_dev;
   a.tol = tol; a.family = family; a.k = k; a.D = D; a.ldp = (int)ldp; a.S = S; a.ld = ld; a.max_iter = max_iter; a.warm = warm;
   const size_t lds = (size_t)bcx_laplace_sampler_lds_bytes(k, D);
-  if (lds > 32 * 1024) {
-    static std::atomic<size_t> lds_max[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > lds_max[dev].load(std::memory_order_acquire)) {
-      if (hipFuncSetAttribute((const void*)laplace_sampler_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        bcx_project_set_error("bcx_laplace_sampler: hipFuncSetAttribute failed");
-        return BCX_ERR_HIP;
-      }
-      lds_max[dev].store(lds, std::memory_order_release);
-    }
+  static PerDevice<size_t> lds_max;
+  if (raise_dynamic_lds((const void*)laplace_sampler_kernel, lds, 32 * 1024, lds_max) != hipSuccess) {
+    bcx_project_set_error("bcx_laplace_sampler: hipFuncSetAttribute failed");
+    return BCX_ERR_HIP;
   }
   hipLaunchKernelGGL(laplace_sampler_kernel, dim3(1), dim3(LAP_THREADS), lds, (hipStream_t)stream, a);
   if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_laplace_sampler: launch failed"); return BCX_ERR_HIP; }

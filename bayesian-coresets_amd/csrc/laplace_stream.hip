@@ -17,13 +17,13 @@
 // which every reader of pass p has reached -- no workgroup is ever more than one barrier ahead of another (the invariant the
 // barrier of nnls_common.h rests on).
 #include <algorithm>
-#include <atomic>
 #include <string>
 #include "bcx_internal.h"
 #include "dev_util.h"
 #include "nnls_common.h"
 #include "chol32.h"
 #include "lik_point.h"
+#include "launch_host.h"
 
 #define LS_DMAX 32
 #define LS_THREADS 256
@@ -334,27 +334,9 @@ __global__ __launch_bounds__(LS_THREADS) void laplace_stream_kernel(LapStreamArg
   }
 }
 
-void bcx_project_set_error(const std::string& msg);   // proj.hip
-
 static int ls_cap_wgs(int64_t k) {
   const int64_t tiles = (k + LS_TILE - 1) / LS_TILE;
   return (int)(tiles < 1 ? 1 : tiles > LS_MAX_WGS ? LS_MAX_WGS : tiles);
-}
-// Workgroups of the kernel that are resident together on the CURRENT device: one per CU, when the occupancy query admits one.
-static int ls_resident_wgs() {
-  static std::atomic<int> cache[64];                  // 0: not yet asked on that device; -1: none
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  int n = cache[dev].load(std::memory_order_acquire);
-  if (n != 0) return n;
-  int cus = 0, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)laplace_stream_kernel, LS_THREADS, 0) != hipSuccess || per_cu < 1)
-    n = -1;
-  else
-    n = cus;                                          // (the query over-reports for some kernels; one per CU keeps a margin)
-  cache[dev].store(n, std::memory_order_release);
-  return n;
 }
 
 extern "C" int64_t bcx_laplace_stream_scratch_bytes(int32_t k, int32_t D) {
@@ -373,7 +355,8 @@ extern "C" int bcx_laplace_sampler_stream(void* stream, int32_t family, int32_t 
                           "bcx_laplace_stream_scratch_bytes)");
     return BCX_ERR_ARG;
   }
-  const int resident = ls_resident_wgs();
+  static PerDevice<int> resident_of;
+  const int resident = one_wg_per_cu((const void*)laplace_stream_kernel, LS_THREADS, resident_of);
   if (resident < 1) {
     bcx_project_set_error("bcx_laplace_sampler_stream: the kernel's workgroups cannot be resident together on this device");
     return BCX_ERR_STATE;
@@ -385,12 +368,7 @@ extern "C" int bcx_laplace_sampler_stream(void* stream, int32_t family, int32_t 
   a.part = (double*)((char*)work_dev + LS_SYNC_BYTES);
   a.tol = tol; a.ldp = ldp; a.family = family; a.k = k; a.D = D; a.S = S; a.ld = ld; a.max_iter = max_iter; a.warm = warm;
   a.rec = ls_record(D);
-  GridSync gs;
-  gs.counter = (unsigned long long*)work_dev;
-  gs.base = 0;
-  gs.timeout_ticks = 200000000LL;                     // 2 s of the 100 MHz wall clock per wait
-  gs.gen = nullptr;
-  gs.fences = 1;
+  const GridSync gs = grid_sync_at((unsigned long long*)work_dev, 200000000LL);         // 2 s of the 100 MHz wall clock per wait
   if (hipMemsetAsync(work_dev, 0, LS_SYNC_BYTES, (hipStream_t)stream) != hipSuccess) {
     bcx_project_set_error("bcx_laplace_sampler_stream: memset failed");
     return BCX_ERR_HIP;

@@ -682,7 +682,6 @@ __global__ __launch_bounds__(256) void lrp_draw_kernel(LpDrawArgs a) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-void bcx_project_set_error(const std::string& msg);   // proj.hip
 #define LRP_HIP(call)                                                             \
   do {                                                                            \
     hipError_t _e = (call);                                                       \

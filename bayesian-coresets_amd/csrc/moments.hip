@@ -164,7 +164,6 @@ __global__ __launch_bounds__(256) void moments_mean_kernel(const double* __restr
 template <bool AL>
 __global__ __launch_bounds__(256) void moments_quad_kernel(MqArgs q) { moments_quad_body<AL>(q, blockIdx.x, gridDim.x); }
 
-void bcx_project_set_error(const std::string& msg);   // proj.hip: the message bcx_project_last_error() returns
 #define MOM_HIP(call)                                                             \
   do {                                                                            \
     hipError_t _e = (call);                                                       \

@@ -69,6 +69,12 @@ struct GridSync {
   int fences;       // 1 (default): agent-scope release before every arrival and acquire after every wait; 0 (dev switch of
                     // omp_lh.hip): none -- valid where all cross-workgroup data is written write-through and read with sc1 loads
 };
+// host: the plain set-up -- a zeroed arrival counter at `counter`, every workgroup polls it, fences on
+static inline GridSync grid_sync_at(unsigned long long* counter, long long timeout_ticks) {
+  GridSync g;
+  g.counter = counter; g.base = 0; g.timeout_ticks = timeout_ticks; g.gen = nullptr; g.fences = 1;
+  return g;
+}
 
 // write-through (sc1) store / sc1 load of one double: the pair that is coherent across XCDs without relying on
 // what the reader's L2 happens to hold

@@ -235,12 +235,7 @@ int bcx_launch_optimize_grid(bcx_solver* s, double tol, int k) {
   if (lds > 150 * 1024) return 1;      // (long rows with a large support: the single-workgroup kernel)
   if (lds > 48 * 1024)
     BCX_HIP(hipFuncSetAttribute((const void*)optimize_grid_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  GridSync gs;
-  gs.counter = s->grid_counter;
-  gs.base = 0;
-  gs.timeout_ticks = 1000000000LL;   // 10 s
-  gs.fences = 1;
-  gs.gen = nullptr;
+  const GridSync gs = grid_sync_at(s->grid_counter, 1000000000LL);   // 10 s
   hipLaunchKernelGGL(optimize_grid_kernel, dim3(OPT_WGS), dim3(NN_THREADS), lds, s->stream, n, gs, tol, kcap, dpad);
   BCX_HIP(hipGetLastError());
   s->grid_dirty = true;   // counter[0] now holds this launch's arrivals; an OMP step that follows without a build_begin re-zeroes

@@ -16,13 +16,11 @@
 //
 // Every branch is taken by the whole workgroup: each thread computes the decision from the same LDS values (or from scalars
 // every thread derived identically from them), and all loops are bounded by integers -- at most 2^J - 1 leaves per transition.
-#include <atomic>
 #include <string>
 #include "bcx_internal.h"
 #include "hmc_core.h"
 #include "nuts_core.h"
-
-void bcx_project_set_error(const std::string& msg);   // proj.hip
+#include "launch_host.h"
 
 struct NutsArgs {
   HmcPar par;           // (noise: C x T rows of stride noise_ld; L unused; diag: C x T x 8)
@@ -193,39 +191,19 @@ extern "C" int64_t bcx_nuts_coreset_lds_bytes(int32_t k, int32_t D) {
   if (k < 0 || D < 1 || D > HMC_DMAX) return -1;
   return hmc_points_lds_bytes(k, D);
 }
-// dynamic LDS one workgroup of the NUTS kernel may have: the device's limit minus this kernel's static use (-1: no device)
-static int64_t nuts_coreset_lds_room() {
-  static std::atomic<int64_t> room[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -1;
-  int64_t r = room[dev].load(std::memory_order_acquire);
-  if (r != 0) return r;
-  int maxb = 0;
-  hipFuncAttributes fa;
-  if (hipDeviceGetAttribute(&maxb, hipDeviceAttributeMaxSharedMemoryPerBlock, dev) != hipSuccess ||
-      hipFuncGetAttributes(&fa, (const void*)nuts_coreset_kernel) != hipSuccess) {
-    (void)hipGetLastError();
-    return -1;
-  }
-  r = (int64_t)maxb - (int64_t)fa.sharedSizeBytes;
-  if (r <= 0) r = -1;
-  room[dev].store(r, std::memory_order_release);
-  return r;
-}
+// 1 when one workgroup can hold the k points: within the LDS the device gives a workgroup, less this kernel's static use
 extern "C" int bcx_nuts_coreset_ok(int32_t k, int32_t D) {
+  static PerDevice<int64_t> room;
   const int64_t b = bcx_nuts_coreset_lds_bytes(k, D);
-  return b >= 0 && b <= nuts_coreset_lds_room();
+  return b >= 0 && b <= lds_room((const void*)nuts_coreset_kernel, room);
 }
 extern "C" int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
                                 const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
                                 int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
                                 void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
                                 void* status_dev) {
-  const bool shape_ok = (family == LAP_LOGISTIC || family == LAP_POISSON) && D >= 1 && D <= HMC_DMAX && chains >= 1 && n_warmup >= 0 &&
-                        n_samples >= 0 && (int64_t)n_warmup + n_samples >= 1 && (int64_t)n_warmup + n_samples <= INT32_MAX &&
-                        max_depth >= 1 && max_depth <= NUTS_JMAX && eps0 > 0.0 && ld >= D && ld <= 32 && noise_dev && samples_dev &&
-                        diag_dev && accept_dev && eps_dev && status_dev;
-  if (!shape_ok || noise_ld < (int64_t)D + 3 * (int64_t)max_depth + 2 * (((int64_t)1 << max_depth) - 1) || !bcx_nuts_coreset_ok(k, D) ||
+  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
+      max_depth < 1 || max_depth > NUTS_JMAX || noise_ld < nuts_noise_row(D, max_depth) || !bcx_nuts_coreset_ok(k, D) ||
       (W_dev && ldw < D) || (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0)))) {
     bcx_project_set_error("bcx_nuts_coreset: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, the points within "
                           "bcx_nuts_coreset_ok, at least one transition, max_depth 1 .. 10, noise_ld >= D + 3 max_depth + "
@@ -233,25 +211,15 @@ extern "C" int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t
     return BCX_ERR_ARG;
   }
   NutsArgs a;
-  HmcPar& p = a.par;
-  p.mu = (const double*)mu_dev; p.W = (const double*)W_dev; p.noise = (const double*)noise_dev; p.samples = (double*)samples_dev;
-  p.xis = (double*)xi_dev; p.props = (double*)prop_dev; p.diag = (double*)diag_dev; p.accept_rate = (double*)accept_dev;
-  p.eps_final = (double*)eps_dev; p.status = (int*)status_dev; p.eps0 = eps0; p.fixed_eps = fixed_eps; p.ldw = ldw; p.D = D; p.ld = ld;
-  p.L = 0; p.T = n_warmup + n_samples; p.nwarm = n_warmup; p.C = chains;
+  a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, 0, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev, prop_dev,
+                  diag_dev, accept_dev, eps_dev, status_dev);
   a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.ldp = ldp; a.noise_ld = noise_ld; a.family = family; a.k = k; a.J = max_depth;
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)bcx_nuts_coreset_lds_bytes(k, D);
-  if (lds > 16 * 1024) {
-    static std::atomic<size_t> lds_max[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > lds_max[dev].load(std::memory_order_acquire)) {
-      if (hipFuncSetAttribute((const void*)nuts_coreset_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) {
-        bcx_project_set_error("bcx_nuts_coreset: hipFuncSetAttribute failed");
-        return BCX_ERR_HIP;
-      }
-      lds_max[dev].store(lds, std::memory_order_release);
-    }
+  static PerDevice<size_t> lds_max;
+  if (raise_dynamic_lds((const void*)nuts_coreset_kernel, lds, 16 * 1024, lds_max) != hipSuccess) {
+    bcx_project_set_error("bcx_nuts_coreset: hipFuncSetAttribute failed");
+    return BCX_ERR_HIP;
   }
   if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_nuts_coreset: memset failed"); return BCX_ERR_HIP; }
   hipLaunchKernelGGL(nuts_coreset_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);

@@ -16,3 +16,6 @@ struct NutsTree {
 
 static __device__ __forceinline__ double nuts_logaddexp(double a, double b) { return fmax(a, b) + log1p(exp(-fabs(a - b))); }
 static __device__ __forceinline__ double nuts_threshold(const double* z) { return 0.5 * (z[0] * z[0] + z[1] * z[1]); }
+
+// standard normals one NUTS transition reads with J = max_depth (1 .. NUTS_JMAX): D momenta, three per doubling, two per leaf slot
+static inline int64_t nuts_noise_row(int32_t D, int32_t J) { return (int64_t)D + 3 * (int64_t)J + 2 * (((int64_t)1 << J) - 1); }

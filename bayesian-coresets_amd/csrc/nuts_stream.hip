@@ -34,12 +34,12 @@
 //    lies between a write and the next read.
 //  * the active list (LDS) is rebuilt behind barrier 2 r + 2 from flags nobody writes before 2 r + 3.
 #include <algorithm>
-#include <atomic>
 #include <string>
 #include "bcx_internal.h"
 #include "nnls_common.h"
 #include "hmc_core.h"
 #include "nuts_core.h"
+#include "launch_host.h"
 
 #define NS_THREADS 256
 #define NS_WAVES (NS_THREADS / 64)
@@ -429,27 +429,9 @@ __global__ __launch_bounds__(NS_THREADS) void nuts_stream_kernel(NsArgs a, GridS
   }
 }
 
-void bcx_project_set_error(const std::string& msg);   // proj.hip
-
 static int ns_cap_wgs(int64_t N) {
   const int64_t tiles = (N + NS_ROWS - 1) / NS_ROWS;
   return (int)(tiles < 1 ? 1 : tiles > NS_MAX_WGS ? NS_MAX_WGS : tiles);
-}
-// Workgroups of the kernel that are resident together on the CURRENT device: one per CU, when the occupancy query admits one.
-static int ns_resident_wgs() {
-  static std::atomic<int> cache[64];                  // 0: not yet asked on that device; -1: none
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  int n = cache[dev].load(std::memory_order_acquire);
-  if (n != 0) return n;
-  int cus = 0, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)nuts_stream_kernel, NS_THREADS, 0) != hipSuccess || per_cu < 1)
-    n = -1;
-  else
-    n = cus;                                          // (the query over-reports for some kernels; one per CU keeps a margin)
-  cache[dev].store(n, std::memory_order_release);
-  return n;
 }
 
 // the scratch: counter | flags | Theta | records | part
@@ -468,41 +450,31 @@ extern "C" int bcx_nuts_stream(void* stream, int32_t family, int64_t N, int32_t 
                                int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
                                void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
                                void* status_dev, void* scratch_dev, int64_t scratch_bytes) {
-  const bool shape_ok = (family == LAP_LOGISTIC || family == LAP_POISSON) && N >= 0 && D >= 1 && D <= HMC_DMAX && chains >= 1 &&
-                        chains <= NS_CMAX && n_warmup >= 0 && n_samples >= 0 && (int64_t)n_warmup + n_samples >= 1 &&
-                        (int64_t)n_warmup + n_samples <= INT32_MAX && max_depth >= 1 && max_depth <= NUTS_JMAX && eps0 > 0.0 && ld >= D &&
-                        ld <= 32 && noise_dev && samples_dev && diag_dev && accept_dev && eps_dev && status_dev && scratch_dev;
-  if (!shape_ok || noise_ld < (int64_t)D + 3 * (int64_t)max_depth + 2 * (((int64_t)1 << max_depth) - 1) || (W_dev && ldw < D) ||
-      scratch_bytes < bcx_nuts_stream_scratch_bytes(N, D, chains, max_depth) ||
+  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
+      N < 0 || chains > NS_CMAX || max_depth < 1 || max_depth > NUTS_JMAX || !scratch_dev || noise_ld < nuts_noise_row(D, max_depth) ||
+      (W_dev && ldw < D) || scratch_bytes < bcx_nuts_stream_scratch_bytes(N, D, chains, max_depth) ||
       (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0)))) {
     bcx_project_set_error("bcx_nuts_stream: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, at most 256 chains, at least one "
                           "transition, max_depth 1 .. 10, noise_ld >= D + 3 max_depth + 2 (2^max_depth - 1), eps0 > 0, ldw >= D, ldz >= D "
                           "(Poisson: D + 1), scratch_dev of bcx_nuts_stream_scratch_bytes)");
     return BCX_ERR_ARG;
   }
-  const int resident = ns_resident_wgs();
+  static PerDevice<int> resident_of;
+  const int resident = one_wg_per_cu((const void*)nuts_stream_kernel, NS_THREADS, resident_of);
   if (resident < 1) {
     bcx_project_set_error("bcx_nuts_stream: the kernel's workgroups cannot be resident together on this device");
     return BCX_ERR_STATE;
   }
   const int G = std::max(1, std::min(ns_cap_wgs(N), resident));
   NsArgs a;
-  HmcPar& p = a.par;
-  p.mu = (const double*)mu_dev; p.W = (const double*)W_dev; p.noise = (const double*)noise_dev; p.samples = (double*)samples_dev;
-  p.xis = (double*)xi_dev; p.props = (double*)prop_dev; p.diag = (double*)diag_dev; p.accept_rate = (double*)accept_dev;
-  p.eps_final = (double*)eps_dev; p.status = (int*)status_dev; p.eps0 = eps0; p.fixed_eps = fixed_eps; p.ldw = ldw; p.D = D; p.ld = ld;
-  p.L = 0; p.T = n_warmup + n_samples; p.nwarm = n_warmup; p.C = chains;
+  a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, 0, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev, prop_dev,
+                  diag_dev, accept_dev, eps_dev, status_dev);
   char* base = (char*)scratch_dev;
   a.w = (const double*)w_dev; a.Z = (const double*)Z_dev;
   a.flags = (int*)(base + ns_flags_offset()); a.Theta = (double*)(base + ns_theta_offset());
   a.recs = (double*)(base + ns_recs_offset(chains)); a.part = (double*)(base + ns_part_offset(chains, max_depth));
   a.N = N; a.ldz = ldz; a.noise_ld = noise_ld; a.family = family; a.J = max_depth; a.rec = ns_record_doubles(max_depth);
-  GridSync gs;
-  gs.counter = (unsigned long long*)scratch_dev;
-  gs.base = 0;
-  gs.timeout_ticks = 200000000LL;                     // 2 s of the 100 MHz wall clock per wait
-  gs.gen = nullptr;
-  gs.fences = 1;
+  const GridSync gs = grid_sync_at((unsigned long long*)scratch_dev, 200000000LL);      // 2 s of the 100 MHz wall clock per wait
   hipStream_t st = (hipStream_t)stream;
   if (hipMemsetAsync(scratch_dev, 0, NS_SYNC_BYTES, st) != hipSuccess || hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) {
     bcx_project_set_error("bcx_nuts_stream: memset failed");

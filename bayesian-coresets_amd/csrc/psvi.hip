@@ -35,7 +35,6 @@
 
 enum { PS_LOGISTIC = 0, PS_POISSON = 1, PS_LINREG = 2, PS_GAUSSIAN = 3 };
 
-void bcx_project_set_error(const std::string& msg);   // proj.hip: the message bcx_project_last_error() returns
 
 typedef double ps4d __attribute__((ext_vector_type(4)));
 

@@ -25,10 +25,10 @@
 //                     zero, on the device-resident weights; the step-size schedule and the bias corrections arrive as data
 //                     (the caller evaluates step_sched(i), 1 - b1^(i+1), 1 - b2^(i+1) on the host once per greedy step).
 // The host enqueues opt_itrs x (draw, column sums, coreset projection, ADAM) and reads the weights back once.
-#include <atomic>
 #include <string>
 #include "bcx_internal.h"
 #include "dev_util.h"
+#include "launch_host.h"
 
 typedef double sv4d __attribute__((ext_vector_type(4)));
 
@@ -623,7 +623,6 @@ __global__ __launch_bounds__(256) void svi_colmean_kernel(const double* __restri
   if (g == 0 && c < ld) out[(size_t)blockIdx.x * out_stride + c] = (((sp[0][c & 63] + sp[1][c & 63]) + sp[2][c & 63]) + sp[3][c & 63]) / (double)n;
 }
 
-void bcx_project_set_error(const std::string& msg);   // proj.hip
 #define SVI_HIP(call)                                                             \
   do {                                                                            \
     hipError_t _e = (call);                                                       \
@@ -676,16 +675,8 @@ extern "C" int bcx_linreg_posterior_apply(void* stream, int32_t k, int32_t D, in
   a.Gbar = (const double*)Gbar_dev; a.gscale = (const double*)gscale_dev; a.theta = (double*)theta_dev; a.tbar = (double*)tbar_dev;
   a.sigsq = sigsq; a.k = k; a.D = D; a.S = S; a.ld = ld;
   const size_t lds = (size_t)2 * k * ld * sizeof(double);
-  if (lds > 32 * 1024) {
-    // per DEVICE (a process may drive several): the largest request so far on the current one
-    static std::atomic<size_t> lds_max[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (lds > lds_max[dev].load(std::memory_order_acquire)) {
-      SVI_HIP(hipFuncSetAttribute((const void*)lrs_apply_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      lds_max[dev].store(lds, std::memory_order_release);
-    }
-  }
+  static PerDevice<size_t> lds_max;      // per DEVICE (a process may drive several): the largest request so far on the current one
+  SVI_HIP(raise_dynamic_lds((const void*)lrs_apply_kernel, lds, 32 * 1024, lds_max));
   hipLaunchKernelGGL(lrs_apply_kernel, dim3((S + 1 + 3) / 4), dim3(256), lds, (hipStream_t)stream, a);
   SVI_HIP(hipGetLastError());
   return BCX_OK;

@@ -244,6 +244,47 @@ def test_failures_stick_and_limits(bc, gold):
         assert b"bcx_nuts_stream" in lib.bcx_project_last_error()
 
 
+def test_the_one_argument_check_counts_transitions_in_64_bits(bc):
+    """The four sampler entry points share one argument check (hmc_common_ok, csrc/hmc_core.h).  n_warmup = n_samples = 2^30 is
+    one transition past what HmcPar::T holds: each entry point refuses under its own name before anything is enqueued (the
+    outputs and the status word keep their sentinels); the same calls with 1 + 1 transitions run."""
+    import torch
+    from bayesiancoresets_amd import _native
+    lib = _native.load()
+    k, D, C, J, ld = 4, 2, 2, 2, 2
+    R = nr.noise_columns(D, J)
+    f64 = dict(dtype=torch.float64, device="cuda")
+    rs = np.random.RandomState(3)
+    pts, w = torch.from_numpy(rs.randn(k, D)).cuda(), torch.from_numpy(rs.uniform(0.5, 2.0, k)).cuda()
+    mu, W = torch.zeros(D, **f64), torch.eye(D, **f64)
+    noise = torch.from_numpy(rs.randn(C, 2, R)).cuda()          # (rows of R >= D + 3 doubles: enough for either transition)
+    samples, diag = torch.empty(C, 2, ld, **f64), torch.empty(C, 2, 8, **f64)
+    acc, eps = torch.empty(C, **f64), torch.empty(C, **f64)
+    status = torch.empty(2, dtype=torch.int32, device="cuda")
+    work = {"bcx_hmc_stream": int(lib.bcx_hmc_stream_scratch_bytes(k, D, C)), "bcx_nuts_stream": int(lib.bcx_nuts_stream_scratch_bytes(k, D, C, J))}
+    assert min(work.values()) > 0
+    scratch = torch.empty(max(work.values()) // 8 + 1, **f64)
+
+    def call(name, n_warmup, n_samples):
+        nuts = "nuts" in name
+        a = [None, 0, k, D, w.data_ptr(), pts.data_ptr(), D, mu.data_ptr(), W.data_ptr(), D, C, n_warmup, n_samples, J if nuts else 3, 0.5, 0.0,
+             noise.data_ptr()] + ([R] if nuts else []) + [ld, samples.data_ptr(), None, None, diag.data_ptr(), acc.data_ptr(), eps.data_ptr(),
+                                                          status.data_ptr()] + ([scratch.data_ptr(), work[name]] if name in work else [])
+        samples.fill_(float("nan"))
+        status.fill_(7)
+        torch.cuda.synchronize()
+        rc = getattr(lib, name)(*a)
+        torch.cuda.synchronize()
+        return rc
+
+    for name in ("bcx_hmc_coreset", "bcx_hmc_stream", "bcx_nuts_coreset", "bcx_nuts_stream"):
+        assert call(name, 2 ** 30, 2 ** 30) == _native.ERR_ARG, name
+        assert lib.bcx_project_last_error().startswith(name.encode() + b":"), lib.bcx_project_last_error()
+        assert bool(torch.isnan(samples).all()) and status.cpu().tolist() == [7, 7], name          # nothing was enqueued
+        assert call(name, 1, 1) == _native.OK, (name, lib.bcx_project_last_error())
+        assert int(status[0]) == 0 and bool(torch.isfinite(samples).all()), name
+
+
 # ---------------------------------------------------------------------------------------------------------------- 7
 def test_reproducible(bc, gold):
     rs = np.random.RandomState(7)
