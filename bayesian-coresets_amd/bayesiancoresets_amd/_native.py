@@ -49,6 +49,7 @@ SYMBOLS = (
     "bcx_log_joint_grad", "bcx_log_joint_grad_scratch_bytes", "bcx_hmc_coreset", "bcx_hmc_coreset_ok", "bcx_hmc_coreset_lds_bytes",
     "bcx_hmc_stream", "bcx_hmc_stream_scratch_bytes",
     "bcx_nuts_coreset", "bcx_nuts_coreset_ok", "bcx_nuts_coreset_lds_bytes",
+    "bcx_nuts_adapt", "bcx_nuts_adapt_ok", "bcx_nuts_adapt_schedule",
     "bcx_nuts_stream", "bcx_nuts_stream_scratch_bytes",
     "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
 )
@@ -219,6 +220,9 @@ def load():
     sigs["bcx_nuts_coreset_ok"] = [i32, i32]
     lib.bcx_nuts_coreset_lds_bytes.restype = ctypes.c_int64
     lib.bcx_nuts_coreset_lds_bytes.argtypes = [i32, i32]
+    sigs["bcx_nuts_adapt"] = sigs["bcx_nuts_coreset"] + [i32, vp, vp]
+    sigs["bcx_nuts_adapt_ok"] = [i32, i32]
+    sigs["bcx_nuts_adapt_schedule"] = [i32, ctypes.POINTER(ctypes.c_int32), i32]
     sigs["bcx_nuts_stream"] = [vp, i32, i64, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp,
                                vp, i64]
     lib.bcx_nuts_stream_scratch_bytes.restype = ctypes.c_int64

@@ -13,12 +13,17 @@ experiment scores every coreset by running Stan on it with ``'w': wts`` (example
   accept statistic -- for points that fit the LDS of one workgroup, as ONE launch.  ``stream=True`` adds the rows that do not
   (csrc/nuts_stream.hip): one persistent launch of co-resident workgroups, one pass over the rows per leaf for
   all chains still running, at most 256 chains.
+* ``DeviceHMC(..., kernel="nuts", adapt_metric="diag" | "dense")``: the LDS-resident NUTS learns a metric per chain in Stan's
+  windowed warm-up (csrc/nuts_adapt.h) -- for a frame that is not the Laplace fit of the posterior (``transform=
+  np.eye(D)``, features that were not standardised).  The metric is a frame: M^-1 = L L^T in the coordinates of ``transform`` is
+  a unit metric in eta with theta = center + (L^T transform)^T eta, re-expressed at the end of every window.
 * ``log_joint_grad(family, pts, wts, thetas)``: the weighted log joint and its gradient for many parameter vectors at once
   (model_lr.py:34-39, 59-64; model_poiss.py:40-46, 69-74) -- what the experiment's ``Fs`` metric is made of.
 
 Fixed-length HMC is the default; without ``stream=True`` NUTS runs only on the LDS-resident path (more points than one
 workgroup holds raise, use ``kernel="hmc"`` or ``stream=True``), with up to 10 doublings and a noise tensor of chains x transitions x
-(D + 3 max_depth + 2 (2^max_depth - 1)) doubles of at most 2 GiB.  Both use a unit mass matrix in xi (no learned mass matrix);
+(D + 3 max_depth + 2 (2^max_depth - 1)) doubles of at most 2 GiB.  Both use a unit mass matrix in xi; only the LDS-resident NUTS
+learns one (``adapt_metric``), the streamed NUTS and the fixed-length HMC do not;
 logistic and Poisson only (the linreg / Gaussian posteriors are closed-form and sampled exactly by their own samplers), D <= 32,
 one device.  There is no CPU fallback."""
 import importlib.util
@@ -36,6 +41,8 @@ DIAG = 6
 NUTS_DIAG = 8
 NUTS_DEPTH_MAX = 10
 NUTS_NOISE_BYTES_MAX = 2 << 30
+NUTS_METRICS = {"diag": 1, "dense": 2}
+NUTS_WINDOWS_MAX = 32
 
 
 def _example_model(family):
@@ -71,7 +78,11 @@ class HMCResult(object):
     ``kernel="nuts"`` adds ``tree_depth`` / ``n_leapfrog`` / ``divergent`` / ``accept_stat`` (chains, n_samples) and
     ``leapfrog_total`` (chains: the leapfrog steps of all transitions, warm-up included); there
     ``accept_rate`` is the per-chain mean of the accept statistic, ``delta_h`` the selected state's energy minus the start's and
-    ``accepted`` whether the state moved."""
+    ``accepted`` whether the state moved.  ``adapt_metric`` ("diag" / "dense") adds ``metric`` (chains, D, D: the final lower
+    triangular L, M^-1 = L L^T in the coordinates of ``transform``) and ``metric_windows`` (the warm-up windows, rows start, end);
+    ``transform`` stays the frame that was passed, ``step_size`` is the step in the final frame, ``trace["xi"]`` the state in
+    the frame current at that transition (``trace["proposal"]`` at a window's last transition: the same state in the new frame)
+    and ``trace["frames"]`` (chains, windows, D, D) the L after each window."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -142,7 +153,7 @@ class DeviceHMC(_DeviceNormals):
     STEP0 = 0.5        # the step the dual averaging starts from (the whitened target is near N(0, I))
 
     def __init__(self, family, D, chains=64, leapfrog=8, seed=None, device="cuda", *, device_frame=False, kernel="hmc", max_depth=8,
-                 stream=False):
+                 stream=False, adapt_metric=None):
         if family not in FAMILIES:
             raise ValueError("family must be 'logistic' or 'poisson'")
         if not 1 <= int(D) <= DMAX:
@@ -155,12 +166,21 @@ class DeviceHMC(_DeviceNormals):
             raise ValueError("DeviceHMC: max_depth = %d (1 <= max_depth <= %d)" % (max_depth, NUTS_DEPTH_MAX))
         if stream and kernel != "nuts":
             raise ValueError("DeviceHMC: stream=True selects the streamed NUTS (kernel=\"nuts\"); kernel=\"hmc\" streams on its own")
+        if adapt_metric is not None:
+            if adapt_metric not in NUTS_METRICS:
+                raise ValueError("DeviceHMC: adapt_metric must be None, 'diag' or 'dense', not %r" % (adapt_metric,))
+            if kernel != "nuts":
+                raise ValueError("DeviceHMC: adapt_metric needs kernel=\"nuts\" (the fixed-length HMC learns no metric); drop adapt_metric")
+            if stream:
+                raise ValueError("DeviceHMC: adapt_metric runs on the LDS-resident NUTS only (the streamed NUTS learns no metric); drop "
+                                 "stream=True or adapt_metric")
         import torch
         from . import _native
         self._torch, self._nat = torch, _native
         self._lib = _native.load()
         if not torch.cuda.is_available():
             raise RuntimeError("DeviceHMC needs a GPU (there is no CPU fallback)")
+        self.adapt_metric = adapt_metric
         self.family, self._fam = family, FAMILIES[family]
         self.device = torch.device(device)
         self.D, self.chains, self.leapfrog = int(D), int(chains), int(leapfrog)
@@ -181,6 +201,19 @@ class DeviceHMC(_DeviceNormals):
     def nuts_path(self, k):
         """Whether k points fit the LDS-resident NUTS kernel (``kernel="nuts"``: the only path it has without ``stream=True``)."""
         return bool(self._lib.bcx_nuts_coreset_ok(int(k), self.D))
+
+    def adapt_path(self, k):
+        """Whether k points fit the LDS-resident NUTS kernel that learns a metric (``adapt_metric``: the only path it has)."""
+        return bool(self._lib.bcx_nuts_adapt_ok(int(k), self.D))
+
+    @staticmethod
+    def metric_windows(n_warmup):
+        """The slow windows of a warm-up of ``n_warmup`` transitions, rows start, end (bcx_nuts_adapt_schedule)."""
+        import ctypes
+        from . import _native
+        buf = (ctypes.c_int32 * (2 * NUTS_WINDOWS_MAX))()
+        n = int(_native.load().bcx_nuts_adapt_schedule(int(n_warmup), buf, NUTS_WINDOWS_MAX))
+        return np.array(buf[:2 * n], dtype=np.int64).reshape(n, 2)
 
     def _default_frame(self, k, pts, wts, Z=None, w=None):
         if k == 0:
@@ -213,6 +246,12 @@ class DeviceHMC(_DeviceNormals):
         nuts = self.kernel == "nuts"
         R = D + 3 * self.max_depth + 2 * ((1 << self.max_depth) - 1) if nuts else D + 3
         nuts_streamed = nuts and self.stream and (bool(_dev_force_stream) or not self.nuts_path(k))
+        if self.adapt_metric is not None:
+            if _dev_step_size is not None:
+                raise ValueError("DeviceHMC: a fixed step (_dev_step_size) does not go with adapt_metric; drop one of them")
+            if _dev_force_stream or not self.adapt_path(k):
+                raise ValueError("DeviceHMC: adapt_metric runs only where the points fit one workgroup's LDS next to the metric's "
+                                 "accumulators (%d points of %d parameters do not); drop adapt_metric, or pass fewer points" % (k, D))
         if nuts:
             if not self.stream and (_dev_force_stream or not self.nuts_path(k)):
                 raise ValueError("DeviceHMC: NUTS without `stream=True` runs only where the points fit one workgroup's LDS; pass "
@@ -240,6 +279,9 @@ class DeviceHMC(_DeviceNormals):
         acc, eps = torch.empty(C, **f64), torch.empty(C, **f64)
         ptr = lambda t: None if t is None else t.data_ptr()
         fixed = 0.0 if _dev_step_size is None else float(_dev_step_size)
+        windows = self.metric_windows(n_warmup) if self.adapt_metric is not None else None
+        frames = None if windows is None else torch.empty(C, max(len(windows), 1), D, D, **f64)
+        metric = None if windows is None else torch.empty(C, D, D, **f64)
 
         def native_args(stream, *scratch):
             # the four entry points' arguments.  Head: stream, family, k, D, weights, rows, row stride.  Tail: frame, counts, steps,
@@ -260,6 +302,8 @@ class DeviceHMC(_DeviceNormals):
                 if self._scratch is None or self._scratch.numel() * 8 < nbytes:
                     self._scratch = torch.empty(nbytes // 8 + 1, **f64)
                 rc = lib.bcx_nuts_stream(*native_args(stream, self._scratch.data_ptr(), nbytes))
+            elif self.adapt_metric is not None:
+                rc = lib.bcx_nuts_adapt(*(native_args(stream) + [NUTS_METRICS[self.adapt_metric], frames.data_ptr(), metric.data_ptr()]))
             elif nuts:
                 rc = lib.bcx_nuts_coreset(*native_args(stream))
             elif streamed:
@@ -285,7 +329,9 @@ class DeviceHMC(_DeviceNormals):
             extra = dict(delta_h=dg[:, n_warmup:, 7], accepted=(th != before).any(axis=2)[:, n_warmup:], accept_stat=dg[:, n_warmup:, 0],
                          tree_depth=dg[:, n_warmup:, 1].astype(np.int64), n_leapfrog=dg[:, n_warmup:, 2].astype(np.int64),
                          divergent=dg[:, n_warmup:, 6] > 0.5, leapfrog_total=dg[:, :, 2].sum(axis=1).astype(np.int64), kernel="nuts",
-                         max_depth=self.max_depth)
+                         max_depth=self.max_depth, adapt_metric=self.adapt_metric)
+            if self.adapt_metric is not None:
+                extra.update(metric=metric.cpu().numpy(), metric_windows=windows)
         else:
             extra = dict(delta_h=dg[:, n_warmup:, 0], accepted=dg[:, n_warmup:, 1] > 0.5, kernel="hmc")
         res = HMCResult(samples=out, accept_rate=acc.cpu().numpy(), step_size=eps.cpu().numpy(), rhat=split_rhat(out) if n_samples >= 4 else np.full(D, np.nan),
@@ -294,4 +340,6 @@ class DeviceHMC(_DeviceNormals):
         if keep_trace:
             res.trace = dict(noise=noise.cpu().numpy(), theta=samples[:, :, :D].cpu().numpy(), xi=xis[:, :, :D].cpu().numpy(),
                              proposal=props[:, :, :D].cpu().numpy(), diag=dg, step0=self.STEP0)
+            if self.adapt_metric is not None:
+                res.trace["frames"] = frames[:, :len(windows)].cpu().numpy()
         return res

@@ -16,10 +16,17 @@
 //
 // Every branch is taken by the whole workgroup: each thread computes the decision from the same LDS values (or from scalars
 // every thread derived identically from them), and all loops are bounded by integers -- at most 2^J - 1 leaves per transition.
+//
+// The kernel is a template on whether it learns a metric in the warm-up (bcx_nuts_adapt; csrc/nuts_adapt.h).  A
+// metric is a frame: at the end of each warm-up window the chain's S.W, coordinate and carried gradient are re-expressed, the
+// dual averaging starts a new segment, and the transition itself is the text below either way.  The instantiation that does not
+// adapt carries none of it.
 #include <string>
+#include <type_traits>
 #include "bcx_internal.h"
 #include "hmc_core.h"
 #include "nuts_core.h"
+#include "nuts_adapt.h"
 #include "launch_host.h"
 
 struct NutsArgs {
@@ -29,8 +36,19 @@ struct NutsArgs {
   int64_t ldp, noise_ld;
   int family, k, J;
 };
+struct NutsAdaptArgs {
+  NutsArgs nuts;
+  double* frames;       // C x max(nwin, 1) x D x D: L after each window
+  double* metric_out;   // C x D x D: the final L
+  int metric, nwin;
+  int win[2 * NUTS_ADAPT_WINDOWS];   // start, end of every window
+};
+static __device__ __forceinline__ const NutsArgs& nuts_args(const NutsArgs& a) { return a; }
+static __device__ __forceinline__ const NutsArgs& nuts_args(const NutsAdaptArgs& a) { return a.nuts; }
 // (NutsTree, nuts_logaddexp, nuts_threshold and the limits: csrc/nuts_core.h, shared with csrc/nuts_stream.hip)
-__global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(NutsArgs a) {
+template <bool ADAPT>
+__global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(std::conditional_t<ADAPT, NutsAdaptArgs, NutsArgs> args) {
+  const NutsArgs& a = nuts_args(args);
   extern __shared__ __attribute__((aligned(16))) double nuts_dyn[];
   __shared__ HmcLds S;
   __shared__ NutsTree Tr;
@@ -58,6 +76,16 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(NutsArgs a) {
 
   const bool adapt = !(a.par.fixed_eps > 0.0);
   double base = adapt ? a.par.eps0 : a.par.fixed_eps, hbar = 0.0, lebar = 0.0, acc_sum = 0.0;
+  // ADAPT: the window being filled (wi, its draws so far wn) and the dual-averaging segment [seg0, seg1) with its start step
+  // (without it A is a byte nobody touches, which the compiler drops: the static LDS stays 20 864 B)
+  __shared__ std::conditional_t<ADAPT, NutsAdaptLds, char> A;
+  int wi = 0, wn = 0, seg0 = 0, seg1 = nwarm;
+  double seg_eps = a.par.eps0;
+  if constexpr (ADAPT) {
+    nuts_adapt_init(A, S);
+    if (args.nwin > 0) seg1 = args.win[1];
+    __syncthreads();
+  }
   for (int t = 0; t < T; ++t) {
     const double* z = a.par.noise + ((size_t)chain * T + t) * a.noise_ld;
     const double eps = base;
@@ -171,7 +199,11 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(NutsArgs a) {
       if (a.par.props) a.par.props[o * ld + tid] = tid < D ? S.s.xi[tid] : 0.0;
     }
     const double alpha = asum / (double)nleaf;
-    if (adapt && t < nwarm) base = hmc_dual_average(t, nwarm, a.par.eps0, alpha, hbar, lebar);
+    if constexpr (ADAPT) {
+      if (adapt && t < nwarm) base = hmc_dual_average(t - seg0, seg1 - seg0, seg_eps, alpha, hbar, lebar);
+    } else {
+      if (adapt && t < nwarm) base = hmc_dual_average(t, nwarm, a.par.eps0, alpha, hbar, lebar);
+    }
     if (t >= nwarm || nwarm >= T) acc_sum += alpha;
     if (tid == 0) {
       double* dg = a.par.diag + o * NUTS_DIAG;
@@ -184,6 +216,42 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(NutsArgs a) {
       }
     }
     __syncthreads();
+    if constexpr (ADAPT) {
+      if (wi < args.nwin && t >= args.win[2 * wi]) {
+        const int wend = args.win[2 * wi + 1];
+        nuts_adapt_accumulate(A, S, D, ++wn);
+        if (t + 1 == wend) {
+          // the window's metric becomes the frame; the state in it, its log target and gradient (theta moves by rounding only)
+          nuts_adapt_window_end(A, S, D, wn, args.metric);
+          if (tid < D) S.s.xp[tid] = S.s.xi[tid];
+          __syncthreads();
+          hmc_theta(S, D);
+          __syncthreads();
+          logp_cur = hmc_eval_points(S, P, D, s_part, scratch);
+          if (tid < D) {
+            double gx = 0.0;
+            for (int c = 0; c < D; ++c) gx = fma(S.W[tid * HMC_LDW + c], S.gth[c], gx);
+            S.s.gcur[tid] = gx;
+            S.s.thcur[tid] = S.s.th[tid];
+          }
+          if (a.par.props && tid < ld) a.par.props[o * ld + tid] = tid < D ? S.s.xi[tid] : 0.0;    // (the state in the new frame)
+          double* fr = args.frames + ((size_t)chain * args.nwin + wi) * D * D;
+          for (int e = tid; e < D * D; e += HMC_THREADS) { const int i = e / D; fr[e] = A.L[i * HMC_LDW + (e - i * D)]; }
+          hbar = 0.0; lebar = 0.0; seg_eps = base; seg0 = wend;
+          ++wi; wn = 0;
+          seg1 = wi < args.nwin ? args.win[2 * wi + 1] : nwarm;
+          __syncthreads();
+        }
+      }
+    }
+  }
+  if constexpr (ADAPT) {
+    double* mo = args.metric_out + (size_t)chain * D * D;
+    for (int e = tid; e < D * D; e += HMC_THREADS) { const int i = e / D; mo[e] = A.L[i * HMC_LDW + (e - i * D)]; }
+    if (args.nwin == 0) {                   // (no window: the one frame slot holds the identity)
+      double* fr = args.frames + (size_t)chain * D * D;
+      for (int e = tid; e < D * D; e += HMC_THREADS) { const int i = e / D; fr[e] = A.L[i * HMC_LDW + (e - i * D)]; }
+    }
   }
 }
 
@@ -195,7 +263,7 @@ extern "C" int64_t bcx_nuts_coreset_lds_bytes(int32_t k, int32_t D) {
 extern "C" int bcx_nuts_coreset_ok(int32_t k, int32_t D) {
   static PerDevice<int64_t> room;
   const int64_t b = bcx_nuts_coreset_lds_bytes(k, D);
-  return b >= 0 && b <= lds_room((const void*)nuts_coreset_kernel, room);
+  return b >= 0 && b <= lds_room((const void*)nuts_coreset_kernel<false>, room);
 }
 extern "C" int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
                                 const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
@@ -217,12 +285,57 @@ extern "C" int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)bcx_nuts_coreset_lds_bytes(k, D);
   static PerDevice<size_t> lds_max;
-  if (raise_dynamic_lds((const void*)nuts_coreset_kernel, lds, 16 * 1024, lds_max) != hipSuccess) {
+  if (raise_dynamic_lds((const void*)nuts_coreset_kernel<false>, lds, 16 * 1024, lds_max) != hipSuccess) {
     bcx_project_set_error("bcx_nuts_coreset: hipFuncSetAttribute failed");
     return BCX_ERR_HIP;
   }
   if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_nuts_coreset: memset failed"); return BCX_ERR_HIP; }
-  hipLaunchKernelGGL(nuts_coreset_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);
+  hipLaunchKernelGGL(nuts_coreset_kernel<false>, dim3(chains), dim3(HMC_THREADS), lds, st, a);
   if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_coreset: launch failed"); return BCX_ERR_HIP; }
+  return BCX_OK;
+}
+
+// ------------------------------------------------------------------------------- the same with a metric learned in the warm-up
+extern "C" int32_t bcx_nuts_adapt_schedule(int32_t n_warmup, int32_t* bounds, int32_t cap) {
+  return nuts_adapt_schedule(n_warmup, bounds, cap < 0 ? 0 : cap);
+}
+// 1 when one workgroup can hold the k points next to the adapting instantiation's static LDS (the accumulators, L and W0)
+extern "C" int bcx_nuts_adapt_ok(int32_t k, int32_t D) {
+  static PerDevice<int64_t> room;
+  const int64_t b = bcx_nuts_coreset_lds_bytes(k, D);
+  return b >= 0 && b <= lds_room((const void*)nuts_coreset_kernel<true>, room);
+}
+extern "C" int bcx_nuts_adapt(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                              const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                              int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
+                              void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
+                              void* status_dev, int32_t metric, void* frames_dev, void* metric_dev) {
+  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
+      max_depth < 1 || max_depth > NUTS_JMAX || noise_ld < nuts_noise_row(D, max_depth) || !bcx_nuts_adapt_ok(k, D) ||
+      (W_dev && ldw < D) || (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0))) ||
+      (metric != NUTS_METRIC_DIAG && metric != NUTS_METRIC_DENSE) || fixed_eps > 0.0 || !frames_dev || !metric_dev) {
+    bcx_project_set_error("bcx_nuts_adapt: bad arguments (those of bcx_nuts_coreset with the points within bcx_nuts_adapt_ok; metric 1 "
+                          "diag / 2 dense; no fixed_eps with a metric; frames_dev and metric_dev)");
+    return BCX_ERR_ARG;
+  }
+  NutsAdaptArgs g;
+  NutsArgs& a = g.nuts;
+  a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, 0, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev, prop_dev,
+                  diag_dev, accept_dev, eps_dev, status_dev);
+  a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.ldp = ldp; a.noise_ld = noise_ld; a.family = family; a.k = k; a.J = max_depth;
+  g.frames = (double*)frames_dev; g.metric_out = (double*)metric_dev; g.metric = metric;
+  for (int i = 0; i < 2 * NUTS_ADAPT_WINDOWS; ++i) g.win[i] = 0;
+  g.nwin = nuts_adapt_schedule(n_warmup, g.win, NUTS_ADAPT_WINDOWS);
+  if (g.nwin > NUTS_ADAPT_WINDOWS) { bcx_project_set_error("bcx_nuts_adapt: more than 32 warm-up windows"); return BCX_ERR_ARG; }
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)bcx_nuts_coreset_lds_bytes(k, D);
+  static PerDevice<size_t> lds_max;
+  if (raise_dynamic_lds((const void*)nuts_coreset_kernel<true>, lds, 0, lds_max) != hipSuccess) {   // (its static LDS is past 48 KiB)
+    bcx_project_set_error("bcx_nuts_adapt: hipFuncSetAttribute failed");
+    return BCX_ERR_HIP;
+  }
+  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_nuts_adapt: memset failed"); return BCX_ERR_HIP; }
+  hipLaunchKernelGGL(nuts_coreset_kernel<true>, dim3(chains), dim3(HMC_THREADS), lds, st, g);
+  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_adapt: launch failed"); return BCX_ERR_HIP; }
   return BCX_OK;
 }

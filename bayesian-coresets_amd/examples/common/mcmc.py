@@ -9,9 +9,12 @@ FAMILY = {"lr": "logistic", "poiss": "poisson"}
 MIN_WARMUP = 200
 
 
-def run(Z, wts, n_samples, model_name, seed, chains=64, leapfrog=8, device="cuda", kernel="hmc", max_depth=8, nuts_stream=False):
+def run(Z, wts, n_samples, model_name, seed, chains=64, leapfrog=8, device="cuda", kernel="hmc", max_depth=8, nuts_stream=False,
+        adapt_metric=None):
     """(samples (n_samples x D), seconds, the kernel that ran -- "nuts" only where it was asked for and the rows fit its
-    LDS-resident path or ``nuts_stream`` lets the others stream, else "hmc" with ``leapfrog`` steps): ``n_samples`` draws from the posterior of the rows ``Z`` (host array or device
+    LDS-resident path or ``nuts_stream`` lets the others stream, else "hmc" with ``leapfrog`` steps; ``adapt_metric`` ("diag" /
+    "dense", with ``kernel="nuts"``): the LDS-resident NUTS learns a metric in its warm-up where the rows fit next to its
+    accumulators, elsewhere the same fallbacks without one): ``n_samples`` draws from the posterior of the rows ``Z`` (host array or device
     tensor, the model's layout; None / empty: the prior) with weights ``wts`` (None: ones), pooled over ``chains`` chains
     that each warm up for as long as they sample (at least MIN_WARMUP transitions)."""
     import bayesiancoresets_amd as bc
@@ -24,6 +27,12 @@ def run(Z, wts, n_samples, model_name, seed, chains=64, leapfrog=8, device="cuda
     hmc = bc.DeviceHMC(family, D, chains=chains, leapfrog=leapfrog, seed=seed, device=device, kernel=kernel, max_depth=max_depth,
                        stream=bool(nuts_stream) and kernel == "nuts")
     ran = kernel
+    if adapt_metric is not None:
+        if kernel != "nuts":
+            raise ValueError("mcmc.run: adapt_metric goes with kernel=\"nuts\"")
+        if hmc.adapt_path(k):             # (the rows fit next to the metric's accumulators; else the fallbacks below, no metric)
+            hmc = bc.DeviceHMC(family, D, chains=chains, seed=seed, device=device, kernel="nuts", max_depth=max_depth,
+                               adapt_metric=adapt_metric)
     if kernel == "nuts" and not hmc.stream and not hmc.nuts_path(k):
         hmc = bc.DeviceHMC(family, D, chains=chains, leapfrog=leapfrog, seed=seed, device=device)
         ran = "hmc"

@@ -21,7 +21,8 @@ bc.DeviceHMC (examples/common/mcmc.py; `--mcmc_samples_full` / `--mcmc_samples_c
 bc.log_joint_grad calls), `full_mcmc_time_per_itr`, `mcmc_time_per_itr`.  `--mcmc_kernel nuts` samples every coreset's posterior
 with the No-U-Turn transition (bc.DeviceHMC(kernel="nuts"): Stan's sampler; a coreset past one workgroup's LDS falls back to HMC);
 the full-data chain stays HMC.  `--mcmc_kernel nuts --mcmc_nuts_stream`: coresets past the LDS and the full-data chain run the
-streamed NUTS (bc.DeviceHMC(kernel="nuts", stream=True)); the full-data cache file then carries the kernel in its name."""
+streamed NUTS (bc.DeviceHMC(kernel="nuts", stream=True)); the full-data cache file then carries the kernel in its name.  `--mcmc_kernel nuts --mcmc_adapt_metric diag|dense`: every coreset
+that fits the adapting LDS-resident NUTS learns a metric in its windowed warm-up; the others run as without it."""
 import argparse
 import os
 import sys
@@ -89,6 +90,9 @@ def run(a):
     nuts_stream = bool(getattr(a, "mcmc_nuts_stream", False))      # (absent unless given: the parser suppresses its default)
     if nuts_stream and not (use_mcmc and mcmc_kernel == "nuts"):
         raise ValueError("--mcmc_nuts_stream goes with --eval mcmc --mcmc_kernel nuts")
+    adapt_metric = getattr(a, "mcmc_adapt_metric", None)           # (absent unless given: the parser suppresses its default)
+    if adapt_metric is not None and not (use_mcmc and mcmc_kernel == "nuts"):
+        raise ValueError("--mcmc_adapt_metric goes with --eval mcmc --mcmc_kernel nuts")
     stream = bool(getattr(a, "laplace_stream", False))     # (absent unless given: the parser suppresses its default)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
@@ -178,7 +182,7 @@ def run(a):
         if use_mcmc:
             if csizes[m] > 0:
                 cst, t_cst, _ = mcmc.run(pts[wts > 0], wts[wts > 0], a.mcmc_samples_coreset, a.model, a.trial, kernel=mcmc_kernel,
-                                           nuts_stream=nuts_stream)
+                                           nuts_stream=nuts_stream, adapt_metric=adapt_metric)
             else:
                 cst, t_cst = np.random.RandomState(a.trial).randn(a.mcmc_samples_coreset, D), 0.0      # the prior
             muw, Sigw = cst.mean(axis=0), np.cov(cst, rowvar=False)
@@ -218,6 +222,9 @@ def parser():
     ap.add_argument("--mcmc_nuts_stream", action="store_true", default=argparse.SUPPRESS,   # (result files keep their argument set)
                     help="with --mcmc_kernel nuts: coresets past one workgroup's LDS and the full-data chain run the streamed NUTS "
                          "(bc.DeviceHMC(kernel='nuts', stream=True))")
+    ap.add_argument("--mcmc_adapt_metric", type=str, choices=["diag", "dense"], default=argparse.SUPPRESS,   # (result files keep their argument set)
+                    help="with --mcmc_kernel nuts: every coreset that fits the adapting LDS-resident NUTS learns a metric in its warm-up "
+                         "(bc.DeviceHMC(kernel='nuts', adapt_metric=...)); the others run as without it")
     ap.add_argument("--proj_dim", type=int, default=500)
     ap.add_argument("--coreset_size_max", type=int, default=1000)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)

@@ -588,6 +588,30 @@ int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t D, const v
                      int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
                      void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
                      void* status_dev);
+/* bcx_nuts_coreset with a metric learned in the warm-up (csrc/nuts_adapt.h).  A metric M^-1 = L L^T in the
+ * coordinates xi0 of the frame passed (theta = mu + W^T xi0) is a unit metric in eta, xi0 = L eta, so the chain moves in eta with
+ * the frame L^T W and the transition above; L is lower triangular, per chain, the identity at the start.
+ * bcx_nuts_adapt_schedule (host only) gives the warm-up's slow windows [start, end) as `start, end` pairs in bounds (at most cap
+ * pairs are written; bounds may be NULL) and returns their number (at most 32): none below 20 warm-up transitions; else init = 75,
+ * term = 50, base = 25, or floor(0.15 n), floor(0.1 n) and the rest when those exceed n_warmup; windows from init, each twice as
+ * long as the one before, the one whose successor would not fit before n_warmup - term extended to there.
+ * After every transition of a window xi0 = L eta joins a running mean and sum of outer products (Welford).  At a window's end
+ * with n draws: Sigma = n / (n + 5) S + 1e-3 * 5 / (n + 5) I (S: the sample covariance, ddof 1; metric 1 keeps its diagonal,
+ * metric 2 all of it), L = chol(Sigma), eta = L^-1 xi0, the frame L^T W, the target evaluated once at the state, the accumulators
+ * cleared and the dual averaging restarted from the step the ended segment averaged to (a pivot that is not positive keeps the
+ * previous L).  The dual averaging runs in segments that end where a window ends and at n_warmup, each handing on exp(log
+ * eps-bar).  Sampling transitions never adapt; below 20 warm-up transitions every output equals bcx_nuts_coreset's.
+ * xi_dev holds eta in the frame current at that transition; at a window's last transition prop_dev holds the same state in the
+ * new frame, and its diag_dev row the ended segment's Hbar and log eps-bar.  frames_dev: chains x max(windows, 1) x D x D doubles, L
+ * after each window, row-major (the identity without windows); metric_dev: chains x D x D, the final L.  fixed_eps > 0 is
+ * BCX_ERR_ARG; bcx_nuts_adapt_ok: the (k, D) that fit next to the adapting kernel's larger static LDS. */
+int32_t bcx_nuts_adapt_schedule(int32_t n_warmup, int32_t* bounds, int32_t cap);
+int bcx_nuts_adapt_ok(int32_t k, int32_t D);
+int bcx_nuts_adapt(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                   const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t n_warmup, int32_t n_samples,
+                   int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
+                   void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
+                   void* status_dev, int32_t metric, void* frames_dev, void* metric_dev);
 /* The same transition, noise layout, outputs and diagnostics for any N (rows past one workgroup's LDS, the resident full data set)
  * and at most 256 chains (csrc/nuts_stream.hip): ONE persistent launch of G = max(1, min(128-row tiles of N, CUs, 256)) co-resident
  * workgroups.  A round evaluates one leaf of every chain still running: all workgroups pass over their rows for the active chains

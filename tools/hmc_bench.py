@@ -8,8 +8,11 @@ per transition, mean tree depth, mean leapfrog steps, effective samples per seco
 each beside the streamed HMC at L = 8 on the same rows, the two alternating -- time per round (one leaf of every running chain), time
 per transition, the rounds of the launch over the mean leaves per chain (the price of ending with the slowest chain), effective
 samples per second, and the passes' share of the fp64-VALU model of DESIGN.md 4.12.
+`--kernel nuts --adapt_metric diag|dense`: the NUTS rows with the metric learned in the windowed warm-up (csrc/nuts_adapt.h,
+DESIGN.md 4.17).  `--identity`: center 0 and transform I in place of the Laplace frame; `--scale S`: the feature columns scaled
+geometrically from 1 to S (badly scaled data, where a learned metric pays).
 
-    python tools/hmc_bench.py [--quick] [--kernel nuts [--stream]]
+    python tools/hmc_bench.py [--quick] [--kernel nuts [--stream | [--adapt_metric diag|dense] [--identity] [--scale S]]]
 """
 import json
 import os
@@ -66,11 +69,11 @@ def case(bc, torch, name, pts, wts, chains, n, center=None, transform=None):
     return res
 
 
-def case_nuts(bc, name, pts, wts, chains, n, center, transform, hmc_res):
+def case_nuts(bc, name, pts, wts, chains, n, center, transform, hmc_res, adapt_metric=None):
     """The NUTS kernel on the case `hmc_res` ran.  A launch ends with its slowest chain (a workgroup each, all resident at
     once), so the time per leaf is the launch time over the largest number of evaluations any chain made."""
     D = pts.shape[1]
-    nuts = bc.DeviceHMC("logistic", D, chains=chains, seed=1, kernel="nuts", max_depth=8)
+    nuts = bc.DeviceHMC("logistic", D, chains=chains, seed=1, kernel="nuts", max_depth=8, adapt_metric=adapt_metric)
     nuts.sample(pts, wts, 10, 10, center=center, transform=transform)              # (first-use costs)
     res = nuts.sample(pts, wts, n, n, center=center, transform=transform)
     rows = []
@@ -84,8 +87,14 @@ def case_nuts(bc, name, pts, wts, chains, n, center, transform, hmc_res):
         rows.append(dict(case=name, kernel=kernel, k=int(pts.shape[0]), D=D, chains=chains, us_per_leaf=per_tr * 2 * n * 1e6 / evals,
                          us_per_transition=per_tr * 1e6, mean_tree_depth=depth, mean_leapfrogs=leaps, accept=float(r.accept_rate.mean()),
                          step=float(r.step_size.mean()), rhat_max=float(np.nanmax(r.rhat)), ess_per_second=float(ess / (per_tr * 2 * n))))
+        if kernel == "nuts":
+            rows[-1].update(adapt_metric=adapt_metric, divergent=int(r.divergent.sum()))
         print(json.dumps(rows[-1]), flush=True)
     return rows
+
+
+def option(name):
+    return sys.argv[sys.argv.index(name) + 1] if name in sys.argv else None
 
 
 def case_stream(bc, name, pts, wts, chains, n, center, transform, reps=2):
@@ -150,15 +159,20 @@ def main():
         for chains in (64, 256):
             case_stream(bc, "N=%d" % N, Z, None, chains, 10 if quick else 50, mu, np.linalg.cholesky(cov).T)
         return
+    adapt_metric, identity, scale = option("--adapt_metric"), "--identity" in sys.argv, float(option("--scale") or 1.0)
     for k in (30, 300, 1000):
         pts, wts = data(k, D, rs), rs.uniform(1.0, 50.0, k)
+        pts[:, :D - 1] *= scale ** (np.arange(D - 1) / (D - 2.0))
         mu, cov = model_lr.laplace_fit(pts, wts)
         W = np.linalg.cholesky(cov).T
+        if identity:
+            mu, W = np.zeros(D), np.eye(D)
         host = None if nuts else host_baseline(pts, wts, mu, W)
         for chains in (64, 256):
             res = case(bc, torch, "coreset k=%d" % k, pts, wts, chains, 100 if quick else 500, mu, W)
             if nuts:
-                case_nuts(bc, "coreset k=%d" % k, pts, wts, chains, 100 if quick else 500, mu, W, res)
+                case_nuts(bc, "coreset k=%d%s%s" % (k, " identity" if identity else "", " scale %g" % scale if scale != 1.0 else ""), pts, wts,
+                          chains, 100 if quick else 500, mu, W, res, adapt_metric)
         if nuts:
             continue
         print(json.dumps(dict(case="host restatement k=%d" % k, us_per_transition_per_chain=host * 1e6)), flush=True)
