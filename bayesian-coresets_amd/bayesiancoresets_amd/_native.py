@@ -50,6 +50,7 @@ SYMBOLS = (
     "bcx_hmc_stream", "bcx_hmc_stream_scratch_bytes",
     "bcx_nuts_coreset", "bcx_nuts_coreset_ok", "bcx_nuts_coreset_lds_bytes",
     "bcx_nuts_adapt", "bcx_nuts_adapt_ok", "bcx_nuts_adapt_schedule",
+    "bcx_nuts_batch", "bcx_nuts_batch_table_bytes",
     "bcx_nuts_stream", "bcx_nuts_stream_scratch_bytes",
     "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
 )
@@ -61,6 +62,15 @@ class Config(ctypes.Structure):
         ("device", ctypes.c_int32), ("d", ctypes.c_int32), ("world_size", ctypes.c_int32),
         ("rank", ctypes.c_int32), ("refresh_every", ctypes.c_int32),
         ("n_local", ctypes.c_int64), ("n_global", ctypes.c_int64), ("row_offset", ctypes.c_int64),
+    ]
+
+
+class NutsProblem(ctypes.Structure):
+    """bcx_nuts_problem (include/bcx.h): one posterior of a bcx_nuts_batch call."""
+    _fields_ = [
+        ("w_dev", ctypes.c_void_p), ("pts_dev", ctypes.c_void_p), ("ldp", ctypes.c_int64),
+        ("mu_dev", ctypes.c_void_p), ("W_dev", ctypes.c_void_p), ("ldw", ctypes.c_int64),
+        ("k", ctypes.c_int32), ("index", ctypes.c_int32),
     ]
 
 
@@ -223,6 +233,10 @@ def load():
     sigs["bcx_nuts_adapt"] = sigs["bcx_nuts_coreset"] + [i32, vp, vp]
     sigs["bcx_nuts_adapt_ok"] = [i32, i32]
     sigs["bcx_nuts_adapt_schedule"] = [i32, ctypes.POINTER(ctypes.c_int32), i32]
+    sigs["bcx_nuts_batch"] = [vp, i32, i32, ctypes.POINTER(NutsProblem), vp, i32, i32, i32, i32, i32, dbl, vp, i64, i32, vp, vp, vp, vp, vp, vp,
+                              vp, i32, vp, vp]
+    lib.bcx_nuts_batch_table_bytes.restype = ctypes.c_int64
+    lib.bcx_nuts_batch_table_bytes.argtypes = [i32]
     sigs["bcx_nuts_stream"] = [vp, i32, i64, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp,
                                vp, i64]
     lib.bcx_nuts_stream_scratch_bytes.restype = ctypes.c_int64

@@ -17,6 +17,10 @@ experiment scores every coreset by running Stan on it with ``'w': wts`` (example
   windowed warm-up (csrc/nuts_adapt.h) -- for a frame that is not the Laplace fit of the posterior (``transform=
   np.eye(D)``, features that were not standardised).  The metric is a frame: M^-1 = L L^T in the coordinates of ``transform`` is
   a unit metric in eta with theta = center + (L^T transform)^T eta, re-expressed at the end of every window.
+* ``DeviceHMC(..., kernel="nuts").sample_many(problems, n_samples, ...)``: many weighted posteriors of one family and D -- the
+  coresets of a size schedule, of several algorithms or trials -- in ONE launch of problems x chains workgroups (csrc/nuts.hip
+  nuts_batch_kernel), with or without ``adapt_metric``; every result is bit for bit what ``sample`` returns for
+  that problem.  LDS-resident NUTS only: no fixed-length HMC, no streamed rows, one D / depth / transition count per call.
 * ``log_joint_grad(family, pts, wts, thetas)``: the weighted log joint and its gradient for many parameter vectors at once
   (model_lr.py:34-39, 59-64; model_poiss.py:40-46, 69-74) -- what the experiment's ``Fs`` metric is made of.
 
@@ -321,6 +325,15 @@ class DeviceHMC(_DeviceNormals):
             raise self._nat.EngineError(self._nat.ERR_TIMEOUT, "NUTS on the device: a wait between the workgroups of the streamed launch expired")
         if st[0] == 2:
             raise self._nat.EngineError(self._nat.ERR_STATE, "HMC on the device: the log joint at the start is not finite (NaN weights or points)")
+        return self._result(n_samples, n_warmup, mu, Wm, seconds, streamed, int(st[0]), noise, samples, xis, props, diag, acc, eps, frames,
+                            metric, windows)
+
+    def _result(self, n_samples, n_warmup, mu, Wm, seconds, streamed, status, noise, samples, xis, props, diag, acc, eps, frames, metric,
+                windows):
+        """The HMCResult of one posterior from its device arrays (``sample``: the launch's; ``sample_many``: one problem's slices);
+        ``xis`` / ``props``: None without ``keep_trace``; ``frames`` / ``metric`` / ``windows``: None without ``adapt_metric``."""
+        D, C, T = self.D, self.chains, n_samples + n_warmup
+        nuts, keep_trace = self.kernel == "nuts", xis is not None
         out = samples[:, n_warmup:, :D].cpu().numpy()
         dg = diag.cpu().numpy()
         if nuts:
@@ -335,7 +348,7 @@ class DeviceHMC(_DeviceNormals):
         else:
             extra = dict(delta_h=dg[:, n_warmup:, 0], accepted=dg[:, n_warmup:, 1] > 0.5, kernel="hmc")
         res = HMCResult(samples=out, accept_rate=acc.cpu().numpy(), step_size=eps.cpu().numpy(), rhat=split_rhat(out) if n_samples >= 4 else np.full(D, np.nan),
-                        seconds_per_iteration=seconds / T, streamed=streamed, nonfinite_rejected=bool(st[0] == 1),
+                        seconds_per_iteration=seconds / T, streamed=streamed, nonfinite_rejected=bool(status == 1),
                         center=mu, transform=np.eye(D) if Wm is None else Wm, n_warmup=n_warmup, trace=None, **extra)
         if keep_trace:
             res.trace = dict(noise=noise.cpu().numpy(), theta=samples[:, :, :D].cpu().numpy(), xi=xis[:, :, :D].cpu().numpy(),
@@ -343,3 +356,115 @@ class DeviceHMC(_DeviceNormals):
             if self.adapt_metric is not None:
                 res.trace["frames"] = frames[:, :len(windows)].cpu().numpy()
         return res
+
+    def sample_many(self, problems, n_samples, n_warmup=None, *, seeds=None, keep_trace=False):
+        """Many weighted posteriors in ONE launch (``kernel="nuts"``, with or without ``adapt_metric``; bcx_nuts_batch, DESIGN.md
+        4.18): a list of HMCResult, the p-th bit for bit what ``sample(pts, wts, n_samples, n_warmup, center, transform,
+        keep_trace)`` returns for ``problems[p]`` -- a ``(pts, wts)`` pair or a dict with ``pts``, ``wts``, ``center``,
+        ``transform`` (the last three optional; a missing frame is the Laplace fit of that problem, as in ``sample``).
+        ``seeds=None``: the noise of problem p is what the p-th of P successive ``sample`` calls on this sampler would draw, and
+        the sampler's stream advances as it would.  ``seeds=[s_0, ...]``: problem p reads what a fresh ``DeviceHMC(seed=s_p)``
+        reads first, and this sampler's stream does not move.  ``seconds_per_iteration`` is the launch's wall time over the
+        transitions, the same for every problem; ``batch_seconds`` that wall time.  A problem whose log joint at the start is not
+        finite raises EngineError naming it (and those like it); the workgroups are dispatched by k descending (a heuristic)."""
+        import ctypes
+        torch, lib, nat, D, C, ld = self._torch, self._lib, self._nat, self.D, self.chains, self.ld
+        if self.kernel != "nuts":
+            raise ValueError("DeviceHMC.sample_many: kernel=\"nuts\" only (the fixed-length HMC has no batched launch); call sample per problem")
+        if self.stream:
+            raise ValueError("DeviceHMC.sample_many: the LDS-resident NUTS only (stream=True has no batched launch); drop stream=True")
+        problems = list(problems)
+        P = len(problems)
+        if P == 0:
+            raise ValueError("DeviceHMC.sample_many: no problems")
+        if seeds is not None:
+            seeds = list(seeds)
+            if len(seeds) != P:
+                raise ValueError("DeviceHMC.sample_many: %d seeds for %d problems" % (len(seeds), P))
+        n_samples = int(n_samples)
+        n_warmup = n_samples if n_warmup is None else int(n_warmup)
+        if n_samples < 0 or n_warmup < 0 or n_samples + n_warmup < 1:
+            raise ValueError("DeviceHMC.sample_many: at least one transition")
+        T = n_samples + n_warmup
+        R = D + 3 * self.max_depth + 2 * ((1 << self.max_depth) - 1)
+        adapt = self.adapt_metric is not None
+        items = []
+        for p, prob in enumerate(problems):
+            if isinstance(prob, dict):
+                pts, wts, center, transform = prob.get("pts"), prob.get("wts"), prob.get("center"), prob.get("transform")
+            else:
+                (pts, wts), center, transform = prob, None, None
+            k = 0 if pts is None else len(pts)
+            if adapt and not self.adapt_path(k):
+                raise ValueError("DeviceHMC.sample_many: problem %d: adapt_metric runs only where the points fit one workgroup's LDS next to "
+                                 "the metric's accumulators (%d points of %d parameters do not)" % (p, k, D))
+            if not self.nuts_path(k):
+                raise ValueError("DeviceHMC.sample_many: problem %d: %d points of %d parameters do not fit one workgroup's LDS; sample it on "
+                                 "its own with `stream=True` or `kernel=\"hmc\"`" % (p, k, D))
+            items.append((pts, wts, center, transform, k))
+        if 8 * P * C * T * R > NUTS_NOISE_BYTES_MAX:
+            raise ValueError("DeviceHMC.sample_many: the NUTS noise (problems x chains x transitions x %d doubles = %d bytes) exceeds 2 GiB; "
+                             "pass fewer problems (%d), or lower max_depth (%d), chains (%d) or the number of transitions (%d)"
+                             % (R, 8 * P * C * T * R, P, self.max_depth, C, T))
+        records = (nat.NutsProblem * P)()
+        frames_host, keep = [], []
+        for p, (pts, wts, center, transform, k) in enumerate(items):
+            Z = _device_rows(torch, self.device, pts, self.cols, "points") if k else None
+            w = _device_weights(torch, self.device, wts, k, "DeviceHMC.sample_many")
+            if center is None and transform is None:
+                center, transform = self._default_frame(k, pts, wts, Z, w)
+            mu = np.zeros(D) if center is None else np.ascontiguousarray(center, dtype=np.float64).reshape(D)
+            Wm = None if transform is None else np.ascontiguousarray(transform, dtype=np.float64).reshape(D, D)
+            mu_dev = torch.from_numpy(mu).to(self.device)
+            W_dev = None if Wm is None else torch.from_numpy(Wm).to(self.device)
+            frames_host.append((mu, Wm))
+            keep.append((Z, w, mu_dev, W_dev))
+            r = records[p]
+            r.w_dev, r.pts_dev, r.ldp = (None if w is None else w.data_ptr()), (Z.data_ptr() if k else None), (Z.stride(0) if k else self.cols)
+            r.mu_dev, r.W_dev, r.ldw, r.k, r.index = mu_dev.data_ptr(), (None if W_dev is None else W_dev.data_ptr()), D, k, p
+        f64 = dict(dtype=torch.float64, device=self.device)
+        noise = torch.empty(P, C, T, R, **f64)
+        pairs = (C * T * R + 1) // 2
+        with torch.cuda.device(self.device):
+            stream = int(torch.cuda.current_stream(self.device).cuda_stream)
+            for p in range(P):      # (the _normal(C, T, R) call of the p-th sample, into its slice)
+                seed, offset = (self._seed, self._offset + p * pairs) if seeds is None else (int(seeds[p]) & 0xFFFFFFFFFFFFFFFF, 0)
+                rc = lib.bcx_standard_normal(stream, seed, offset, C * T * R, noise[p].data_ptr())
+                if rc != 0:
+                    raise nat.EngineError(rc, lib.bcx_project_last_error().decode())
+            if seeds is None:
+                self._offset += P * pairs
+            samples = torch.empty(P, C, T, ld, **f64)
+            xis = torch.empty(P, C, T, ld, **f64) if keep_trace else None
+            props = torch.empty(P, C, T, ld, **f64) if keep_trace else None
+            diag = torch.empty(P, C, T, NUTS_DIAG, **f64)
+            acc, eps = torch.empty(P, C, **f64), torch.empty(P, C, **f64)
+            windows = self.metric_windows(n_warmup) if adapt else None
+            frames = torch.empty(P, C, max(len(windows), 1), D, D, **f64) if adapt else None
+            metric = torch.empty(P, C, D, D, **f64) if adapt else None
+            status = torch.zeros(2 * P, dtype=torch.int32, device=self.device)
+            table = torch.empty(int(lib.bcx_nuts_batch_table_bytes(P)), dtype=torch.uint8, device=self.device)
+            ptr = lambda t: None if t is None else t.data_ptr()
+            torch.cuda.synchronize(self.device)
+            t0 = time.perf_counter()
+            rc = lib.bcx_nuts_batch(stream, self._fam, P, records, table.data_ptr(), D, C, n_warmup, n_samples, self.max_depth, self.STEP0,
+                                    noise.data_ptr(), R, ld, samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(),
+                                    eps.data_ptr(), status.data_ptr(), NUTS_METRICS[self.adapt_metric] if adapt else 0, ptr(frames), ptr(metric))
+            if rc != 0:
+                raise nat.EngineError(rc, lib.bcx_project_last_error().decode())
+            torch.cuda.synchronize(self.device)
+            seconds = time.perf_counter() - t0
+        del keep
+        st = status.cpu().numpy().reshape(P, 2)[:, 0]
+        bad = [p for p in range(P) if st[p] == 2]
+        if bad:
+            raise nat.EngineError(nat.ERR_STATE, "NUTS on the device: the log joint at the start is not finite (NaN weights or points) in "
+                                  "problem%s %s" % ("" if len(bad) == 1 else "s", ", ".join(str(p) for p in bad)))
+        at = lambda t, p: None if t is None else t[p]
+        results = []
+        for p, (mu, Wm) in enumerate(frames_host):
+            res = self._result(n_samples, n_warmup, mu, Wm, seconds, False, int(st[p]), noise[p], samples[p], at(xis, p), at(props, p), diag[p],
+                               acc[p], eps[p], at(frames, p), at(metric, p), windows)
+            res.batch_seconds = seconds
+            results.append(res)
+        return results

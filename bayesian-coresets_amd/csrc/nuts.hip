@@ -21,8 +21,14 @@
 // metric is a frame: at the end of each warm-up window the chain's S.W, coordinate and carried gradient are re-expressed, the
 // dual averaging starts a new segment, and the transition itself is the text below either way.  The instantiation that does not
 // adapt carries none of it.
+//
+// The chain is one device function, nuts_chain, that two kernels call: nuts_coreset_kernel (one posterior, a workgroup per chain)
+// and nuts_batch_kernel (bcx_nuts_batch, DESIGN.md 4.18: P posteriors of one family, D, depth and transition counts, P x C
+// workgroups, a table in device memory from dispatch slot to problem).
+#include <algorithm>
 #include <string>
 #include <type_traits>
+#include <vector>
 #include "bcx_internal.h"
 #include "hmc_core.h"
 #include "nuts_core.h"
@@ -46,15 +52,18 @@ struct NutsAdaptArgs {
 static __device__ __forceinline__ const NutsArgs& nuts_args(const NutsArgs& a) { return a; }
 static __device__ __forceinline__ const NutsArgs& nuts_args(const NutsAdaptArgs& a) { return a.nuts; }
 // (NutsTree, nuts_logaddexp, nuts_threshold and the limits: csrc/nuts_core.h, shared with csrc/nuts_stream.hip)
+// One chain, start to end: what a workgroup of either kernel below runs.  `a` is the NutsArgs view the chain works from -- that of
+// `args`, or a copy with one problem's points, frame and status put in (nuts_batch_kernel) -- and `chain` the chain's index into
+// the noise and every output; `args` itself is read for the metric's fields only.
 template <bool ADAPT>
-__global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(std::conditional_t<ADAPT, NutsAdaptArgs, NutsArgs> args) {
-  const NutsArgs& a = nuts_args(args);
+static __device__ __forceinline__ void nuts_chain(const std::conditional_t<ADAPT, NutsAdaptArgs, NutsArgs>& args, const NutsArgs& a,
+                                                  const size_t chain) {
   extern __shared__ __attribute__((aligned(16))) double nuts_dyn[];
   __shared__ HmcLds S;
   __shared__ NutsTree Tr;
   __shared__ double s_part[8 * 32];
   __shared__ double scratch[BCX_SCRATCH];
-  const int tid = threadIdx.x, chain = blockIdx.x;
+  const int tid = threadIdx.x;
   const int D = a.par.D, J = a.J, T = a.par.T, nwarm = a.par.nwarm, ld = a.par.ld;
   const HmcPoints P = hmc_load_points(nuts_dyn, a.family, a.k, D, a.w, a.pts, a.ldp);
   hmc_load_frame(S, a.par);
@@ -87,7 +96,7 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(std::conditio
     __syncthreads();
   }
   for (int t = 0; t < T; ++t) {
-    const double* z = a.par.noise + ((size_t)chain * T + t) * a.noise_ld;
+    const double* z = a.par.noise + (chain * T + t) * a.noise_ld;
     const double eps = base;
     const double H0 = hmc_half_sq(z, D) - logp_cur;
     if (tid < D) {
@@ -192,7 +201,7 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(std::conditio
     }
     __syncthreads();
     // the new state is the selected one; outputs, adaptation
-    const size_t o = (size_t)chain * T + t;
+    const size_t o = chain * T + t;
     if (tid < ld) {
       a.par.samples[o * ld + tid] = tid < D ? S.s.thcur[tid] : 0.0;
       if (a.par.xis) a.par.xis[o * ld + tid] = tid < D ? S.s.xi[tid] : 0.0;
@@ -235,7 +244,7 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(std::conditio
             S.s.thcur[tid] = S.s.th[tid];
           }
           if (a.par.props && tid < ld) a.par.props[o * ld + tid] = tid < D ? S.s.xi[tid] : 0.0;    // (the state in the new frame)
-          double* fr = args.frames + ((size_t)chain * args.nwin + wi) * D * D;
+          double* fr = args.frames + (chain * args.nwin + wi) * D * D;
           for (int e = tid; e < D * D; e += HMC_THREADS) { const int i = e / D; fr[e] = A.L[i * HMC_LDW + (e - i * D)]; }
           hbar = 0.0; lebar = 0.0; seg_eps = base; seg0 = wend;
           ++wi; wn = 0;
@@ -246,13 +255,32 @@ __global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(std::conditio
     }
   }
   if constexpr (ADAPT) {
-    double* mo = args.metric_out + (size_t)chain * D * D;
+    double* mo = args.metric_out + chain * D * D;
     for (int e = tid; e < D * D; e += HMC_THREADS) { const int i = e / D; mo[e] = A.L[i * HMC_LDW + (e - i * D)]; }
     if (args.nwin == 0) {                   // (no window: the one frame slot holds the identity)
-      double* fr = args.frames + (size_t)chain * D * D;
+      double* fr = args.frames + chain * D * D;
       for (int e = tid; e < D * D; e += HMC_THREADS) { const int i = e / D; fr[e] = A.L[i * HMC_LDW + (e - i * D)]; }
     }
   }
+}
+template <bool ADAPT>
+__global__ __launch_bounds__(HMC_THREADS) void nuts_coreset_kernel(std::conditional_t<ADAPT, NutsAdaptArgs, NutsArgs> args) {
+  nuts_chain<ADAPT>(args, nuts_args(args), blockIdx.x);
+}
+// P posteriors in one launch (bcx_nuts_batch): P x C workgroups, workgroup b chain b % C of dispatch slot b / C.
+// `table` maps the slot to its problem: the record read once, here, into workgroup-uniform values -- the points, the frame, the
+// problem's place p in the caller's order, which is where its noise, outputs (chain p C + c) and two status words are.  The
+// launch's dynamic LDS is that of the largest problem; a workgroup lays out its own k points in it.
+template <bool ADAPT>
+__global__ __launch_bounds__(HMC_THREADS) void nuts_batch_kernel(std::conditional_t<ADAPT, NutsAdaptArgs, NutsArgs> args,
+                                                                 const bcx_nuts_problem* __restrict__ table) {
+  NutsArgs a = nuts_args(args);
+  const int C = a.par.C, slot = (int)blockIdx.x / C;
+  const bcx_nuts_problem q = table[slot];
+  a.w = (const double*)q.w_dev; a.pts = (const double*)q.pts_dev; a.ldp = q.ldp; a.k = q.k;
+  a.par.mu = (const double*)q.mu_dev; a.par.W = (const double*)q.W_dev; a.par.ldw = q.ldw;
+  a.par.status += 2 * (size_t)q.index;
+  nuts_chain<ADAPT>(args, a, (size_t)q.index * C + ((int)blockIdx.x - slot * C));
 }
 
 extern "C" int64_t bcx_nuts_coreset_lds_bytes(int32_t k, int32_t D) {
@@ -338,4 +366,89 @@ extern "C" int bcx_nuts_adapt(void* stream, int32_t family, int32_t k, int32_t D
   hipLaunchKernelGGL(nuts_coreset_kernel<true>, dim3(chains), dim3(HMC_THREADS), lds, st, g);
   if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_adapt: launch failed"); return BCX_ERR_HIP; }
   return BCX_OK;
+}
+
+// ------------------------------------------------------------------------------------------ many posteriors in one launch
+extern "C" int64_t bcx_nuts_batch_table_bytes(int32_t P) {
+  return P < 1 ? -1 : (int64_t)P * (int64_t)sizeof(bcx_nuts_problem);
+}
+// room for dynamic LDS next to the batch kernel's own static use (the same text as the single kernel's, asked of the kernel launched)
+template <bool ADAPT>
+static bool nuts_batch_fits(int64_t bytes) {
+  static PerDevice<int64_t> room;
+  return bytes >= 0 && bytes <= lds_room((const void*)nuts_batch_kernel<ADAPT>, room);
+}
+template <bool ADAPT, class Args>
+static int nuts_batch_launch(const Args& g, const bcx_nuts_problem* table, int32_t P, int32_t chains, size_t lds, size_t threshold,
+                             hipStream_t st) {
+  static PerDevice<size_t> lds_max;
+  if (raise_dynamic_lds((const void*)nuts_batch_kernel<ADAPT>, lds, threshold, lds_max) != hipSuccess) {
+    bcx_project_set_error("bcx_nuts_batch: hipFuncSetAttribute failed");
+    return BCX_ERR_HIP;
+  }
+  hipLaunchKernelGGL(nuts_batch_kernel<ADAPT>, dim3((unsigned)P * (unsigned)chains), dim3(HMC_THREADS), lds, st, g, table);
+  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_batch: launch failed"); return BCX_ERR_HIP; }
+  return BCX_OK;
+}
+extern "C" int bcx_nuts_batch(void* stream, int32_t family, int32_t P, const bcx_nuts_problem* problems, void* table_dev, int32_t D,
+                              int32_t chains, int32_t n_warmup, int32_t n_samples, int32_t max_depth, double eps0, const void* noise_dev,
+                              int64_t noise_ld, int32_t ld, void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev,
+                              void* eps_dev, void* status_dev, int32_t metric, void* frames_dev, void* metric_dev) {
+  // what needs no device first: a caller without one reaches every one of these
+  if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
+      P < 1 || (int64_t)P * chains > INT32_MAX || !problems || !table_dev || max_depth < 1 || max_depth > NUTS_JMAX ||
+      noise_ld < nuts_noise_row(D, max_depth) || (metric != 0 && metric != NUTS_METRIC_DIAG && metric != NUTS_METRIC_DENSE) ||
+      (metric != 0) != (frames_dev != nullptr) || (metric != 0) != (metric_dev != nullptr)) {
+    bcx_project_set_error("bcx_nuts_batch: bad arguments (those of bcx_nuts_coreset without fixed_eps; P >= 1 problems, P x chains "
+                          "<= 2^31 - 1, problems and table_dev; metric 0 none / 1 diag / 2 dense, frames_dev and metric_dev iff a metric)");
+    return BCX_ERR_ARG;
+  }
+  const int64_t row = D + (family == LAP_POISSON ? 1 : 0);
+  for (int32_t p = 0; p < P; ++p) {
+    const bcx_nuts_problem& q = problems[p];
+    if (q.k < 0 || (q.W_dev && q.ldw < D) || (q.k > 0 && (!q.pts_dev || q.ldp < row))) {
+      bcx_project_set_error(("bcx_nuts_batch: problem " + std::to_string(p) + ": bad arguments (k >= 0, ldw >= D with W_dev, pts_dev and "
+                             "ldp >= the row with k > 0)").c_str());
+      return BCX_ERR_ARG;
+    }
+  }
+  // what asks the device: every problem within one workgroup's LDS, next to the static LDS of the kernel that runs
+  int64_t lds = 0;
+  for (int32_t p = 0; p < P; ++p) {
+    const int32_t k = problems[p].k;
+    const int64_t b = bcx_nuts_coreset_lds_bytes(k, D);
+    if (!(metric ? bcx_nuts_adapt_ok(k, D) && nuts_batch_fits<true>(b) : bcx_nuts_coreset_ok(k, D) && nuts_batch_fits<false>(b))) {
+      bcx_project_set_error(("bcx_nuts_batch: problem " + std::to_string(p) + ": " + std::to_string(k) + " points of " + std::to_string(D) +
+                             " parameters are outside " + (metric ? "bcx_nuts_adapt_ok" : "bcx_nuts_coreset_ok")).c_str());
+      return BCX_ERR_ARG;
+    }
+    if (b > lds) lds = b;
+  }
+  int win[2 * NUTS_ADAPT_WINDOWS] = {0};
+  const int nwin = metric ? nuts_adapt_schedule(n_warmup, win, NUTS_ADAPT_WINDOWS) : 0;
+  if (nwin > NUTS_ADAPT_WINDOWS) { bcx_project_set_error("bcx_nuts_batch: more than 32 warm-up windows"); return BCX_ERR_ARG; }
+  // the dispatch order: k descending (the caller's order among equals), each record with its place in the caller's order
+  std::vector<bcx_nuts_problem> table(problems, problems + P);
+  for (int32_t p = 0; p < P; ++p) table[p].index = p;
+  std::stable_sort(table.begin(), table.end(), [](const bcx_nuts_problem& x, const bcx_nuts_problem& y) { return x.k > y.k; });
+  hipStream_t st = (hipStream_t)stream;
+  // (the records are pageable host memory that ends with this call: the copy is waited for)
+  if (hipMemcpyAsync(table_dev, table.data(), (size_t)P * sizeof(bcx_nuts_problem), hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess) {
+    bcx_project_set_error("bcx_nuts_batch: the upload of the problem table failed");
+    return BCX_ERR_HIP;
+  }
+  if (hipMemset2DAsync(status_dev, 2 * sizeof(int), 0, sizeof(int), (size_t)P, st) != hipSuccess) {      // status[2 p] of every problem
+    bcx_project_set_error("bcx_nuts_batch: memset failed");
+    return BCX_ERR_HIP;
+  }
+  NutsAdaptArgs g;
+  NutsArgs& a = g.nuts;
+  a.par = hmc_par(D, nullptr, nullptr, D, chains, n_warmup, n_samples, 0, eps0, 0.0, noise_dev, ld, samples_dev, xi_dev, prop_dev, diag_dev,
+                  accept_dev, eps_dev, status_dev);
+  a.w = nullptr; a.pts = nullptr; a.ldp = row; a.noise_ld = noise_ld; a.family = family; a.k = 0; a.J = max_depth;
+  if (!metric) return nuts_batch_launch<false>(a, (const bcx_nuts_problem*)table_dev, P, chains, (size_t)lds, 16 * 1024, st);
+  g.frames = (double*)frames_dev; g.metric_out = (double*)metric_dev; g.metric = metric; g.nwin = nwin;
+  for (int i = 0; i < 2 * NUTS_ADAPT_WINDOWS; ++i) g.win[i] = win[i];
+  return nuts_batch_launch<true>(g, (const bcx_nuts_problem*)table_dev, P, chains, (size_t)lds, 0, st);   // (its static LDS is past 48 KiB)
 }

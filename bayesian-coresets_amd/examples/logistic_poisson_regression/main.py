@@ -22,7 +22,10 @@ bc.log_joint_grad calls), `full_mcmc_time_per_itr`, `mcmc_time_per_itr`.  `--mcm
 with the No-U-Turn transition (bc.DeviceHMC(kernel="nuts"): Stan's sampler; a coreset past one workgroup's LDS falls back to HMC);
 the full-data chain stays HMC.  `--mcmc_kernel nuts --mcmc_nuts_stream`: coresets past the LDS and the full-data chain run the
 streamed NUTS (bc.DeviceHMC(kernel="nuts", stream=True)); the full-data cache file then carries the kernel in its name.  `--mcmc_kernel nuts --mcmc_adapt_metric diag|dense`: every coreset
-that fits the adapting LDS-resident NUTS learns a metric in its windowed warm-up; the others run as without it."""
+that fits the adapting LDS-resident NUTS learns a metric in its windowed warm-up; the others run as without it.
+`--mcmc_kernel nuts --mcmc_batch`: the coresets of all sizes are kept during the build and scored after it by one
+mcmc.run_many -- ONE launch for all that fit the LDS-resident NUTS; every column is the unbatched run's but
+`mcmc_time_per_itr`, which is the launch's time over the coresets in it."""
 import argparse
 import os
 import sys
@@ -93,6 +96,9 @@ def run(a):
     adapt_metric = getattr(a, "mcmc_adapt_metric", None)           # (absent unless given: the parser suppresses its default)
     if adapt_metric is not None and not (use_mcmc and mcmc_kernel == "nuts"):
         raise ValueError("--mcmc_adapt_metric goes with --eval mcmc --mcmc_kernel nuts")
+    batch = bool(getattr(a, "mcmc_batch", False))                  # (absent unless given: the parser suppresses its default)
+    if batch and not (use_mcmc and mcmc_kernel == "nuts"):
+        raise ValueError("--mcmc_batch goes with --eval mcmc --mcmc_kernel nuts")
     stream = bool(getattr(a, "laplace_stream", False))     # (absent unless given: the parser suppresses its default)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
@@ -171,6 +177,20 @@ def run(a):
         extra = dict(Fs=np.zeros(n), full_mcmc_time_per_itr=np.full(n, full_t), mcmc_time_per_itr=np.zeros(n))
     cputs, walls, csizes = np.zeros(n), np.zeros(n), np.zeros(n)
     rklw, fklw, mu_errs, Sig_errs = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
+
+    def score(m, muw, Sigw):
+        rklw[m] = gaussian_kl(muw, Sigw, mup, SigpInv)
+        fklw[m] = gaussian_kl(mup, Sigp, muw, np.linalg.inv(Sigw))
+        mu_errs[m] = np.sqrt(((mup - muw) ** 2).sum()) / np.sqrt((mup ** 2).sum())
+        Sig_errs[m] = np.sqrt(((Sigp - Sigw) ** 2).sum()) / np.sqrt((Sigp ** 2).sum())
+
+    def score_draws(m, cst, t_cst, cpts, cwts):
+        _, gcs = bc.log_joint_grad(family, cpts, cwts, full_samples)
+        extra["Fs"][m] = ((gcs - gfs) ** 2).sum(axis=1).mean()                  # main.py:226-228
+        extra["mcmc_time_per_itr"][m] = t_cst / (a.mcmc_samples_coreset * 2)
+        score(m, cst.mean(axis=0), np.cov(cst, rowvar=False))
+
+    kept = []                               # --mcmc_batch: (m, points, weights) of every size, scored behind the loop
     for m in range(n):
         print("M = %d: coreset construction, %s %s %d" % (Ms[m], a.alg, a.dataset, a.trial))
         c0, t0 = time.process_time(), time.perf_counter()
@@ -180,23 +200,23 @@ def run(a):
         wts, pts, idcs = alg.get()
         csizes[m] = (wts > 0).sum()
         if use_mcmc:
-            if csizes[m] > 0:
+            if csizes[m] > 0 and batch:
+                kept.append((m, pts[wts > 0], wts[wts > 0]))
+            elif csizes[m] > 0:
                 cst, t_cst, _ = mcmc.run(pts[wts > 0], wts[wts > 0], a.mcmc_samples_coreset, a.model, a.trial, kernel=mcmc_kernel,
                                            nuts_stream=nuts_stream, adapt_metric=adapt_metric)
+                score_draws(m, cst, t_cst, pts[wts > 0], wts[wts > 0])
             else:
-                cst, t_cst = np.random.RandomState(a.trial).randn(a.mcmc_samples_coreset, D), 0.0      # the prior
-            muw, Sigw = cst.mean(axis=0), np.cov(cst, rowvar=False)
-            _, gcs = bc.log_joint_grad(family, pts[wts > 0], wts[wts > 0], full_samples)
-            extra["Fs"][m] = ((gcs - gfs) ** 2).sum(axis=1).mean()              # main.py:226-228
-            extra["mcmc_time_per_itr"][m] = t_cst / (a.mcmc_samples_coreset * 2)
+                score_draws(m, np.random.RandomState(a.trial).randn(a.mcmc_samples_coreset, D), 0.0, pts[wts > 0], wts[wts > 0])   # the prior
         elif csizes[m] > 0:
-            muw, Sigw = laplace(pts[wts > 0], wts[wts > 0])
+            score(m, *laplace(pts[wts > 0], wts[wts > 0]))
         else:
-            muw, Sigw = np.zeros(D), np.eye(D)
-        rklw[m] = gaussian_kl(muw, Sigw, mup, SigpInv)
-        fklw[m] = gaussian_kl(mup, Sigp, muw, np.linalg.inv(Sigw))
-        mu_errs[m] = np.sqrt(((mup - muw) ** 2).sum()) / np.sqrt((mup ** 2).sum())
-        Sig_errs[m] = np.sqrt(((Sigp - Sigw) ** 2).sum()) / np.sqrt((Sigp ** 2).sum())
+            score(m, np.zeros(D), np.eye(D))
+    if kept:
+        scored = mcmc.run_many([(cpts, cwts) for _, cpts, cwts in kept], a.mcmc_samples_coreset, a.model, a.trial, kernel=mcmc_kernel,
+                               nuts_stream=nuts_stream, adapt_metric=adapt_metric)
+        for (m, cpts, cwts), (cst, t_cst, _) in zip(kept, scored):
+            score_draws(m, cst, t_cst, cpts, cwts)
     print("final: csize %d, reverse KL %.6g, forward KL %.6g, %.2f s wall" % (csizes[-1], rklw[-1], fklw[-1], walls[-1]))
     results.save(a, a.results_folder, csizes=csizes, Ms=Ms, cputs=cputs, walls=walls, rklw=rklw, fklw=fklw, mu_errs=mu_errs,
                  Sig_errs=Sig_errs, **extra)
@@ -225,6 +245,9 @@ def parser():
     ap.add_argument("--mcmc_adapt_metric", type=str, choices=["diag", "dense"], default=argparse.SUPPRESS,   # (result files keep their argument set)
                     help="with --mcmc_kernel nuts: every coreset that fits the adapting LDS-resident NUTS learns a metric in its warm-up "
                          "(bc.DeviceHMC(kernel='nuts', adapt_metric=...)); the others run as without it")
+    ap.add_argument("--mcmc_batch", action="store_true", default=argparse.SUPPRESS,         # (result files keep their argument set)
+                    help="with --mcmc_kernel nuts: keep every size's coreset and score them behind the build in one launch "
+                         "(bc.DeviceHMC.sample_many); mcmc_time_per_itr is then the launch's time over the coresets in it")
     ap.add_argument("--proj_dim", type=int, default=500)
     ap.add_argument("--coreset_size_max", type=int, default=1000)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)

@@ -612,6 +612,34 @@ int bcx_nuts_adapt(void* stream, int32_t family, int32_t k, int32_t D, const voi
                    int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
                    void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
                    void* status_dev, int32_t metric, void* frames_dev, void* metric_dev);
+/* P weighted posteriors of one family, D, depth and transition counts in ONE launch of P x chains workgroups (csrc/nuts.hip
+ * nuts_batch_kernel): problem p is what bcx_nuts_coreset (metric 0) or bcx_nuts_adapt (metric 1 diag / 2 dense)
+ * computes for problems[p], bit for bit, with chain p chains + c in the place of chain c: noise_dev, samples_dev, xi_dev, prop_dev,
+ * diag_dev, accept_dev, eps_dev, frames_dev and metric_dev are the single call's arrays with a leading dimension P, and
+ * status_dev holds two words per problem ([2p] this launch, zeroed here; [2p + 1] the worst since the caller zeroed it), so a
+ * start that is not finite is one problem's and the others' draws stand.  problems: a HOST array of P records; `index` is written
+ * by the library (the record's place in that array), the rest as the single call's arguments (w_dev NULL: ones; mu_dev NULL: zero;
+ * W_dev NULL: the identity; pts_dev may be NULL when k = 0).  table_dev: bcx_nuts_batch_table_bytes(P) bytes of device memory (-1:
+ * P < 1) the records are uploaded into, in dispatch order -- k descending, so that the longest leaves start first (a heuristic
+ * that was not measured); the library allocates nothing.  The launch's dynamic LDS is the largest problem's.  There is no
+ * fixed_eps.  frames_dev and metric_dev are required iff metric is non-zero.  BCX_ERR_ARG: what bcx_nuts_coreset refuses, P < 1,
+ * P x chains past 2^31 - 1, NULL problems or table_dev, a problem outside bcx_nuts_coreset_ok (bcx_nuts_adapt_ok with a metric),
+ * a row stride below the row, ldw < D with W_dev, metric outside 0 .. 2; the message names the first bad problem. */
+typedef struct bcx_nuts_problem {
+  const void* w_dev;    /* k weights or NULL */
+  const void* pts_dev;  /* k rows, stride ldp */
+  int64_t ldp;
+  const void* mu_dev;   /* D or NULL */
+  const void* W_dev;    /* D x D, row stride ldw, or NULL */
+  int64_t ldw;
+  int32_t k;
+  int32_t index;
+} bcx_nuts_problem;
+int64_t bcx_nuts_batch_table_bytes(int32_t P);
+int bcx_nuts_batch(void* stream, int32_t family, int32_t P, const bcx_nuts_problem* problems, void* table_dev, int32_t D,
+                   int32_t chains, int32_t n_warmup, int32_t n_samples, int32_t max_depth, double eps0, const void* noise_dev,
+                   int64_t noise_ld, int32_t ld, void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev,
+                   void* eps_dev, void* status_dev, int32_t metric, void* frames_dev, void* metric_dev);
 /* The same transition, noise layout, outputs and diagnostics for any N (rows past one workgroup's LDS, the resident full data set)
  * and at most 256 chains (csrc/nuts_stream.hip): ONE persistent launch of G = max(1, min(128-row tiles of N, CUs, 256)) co-resident
  * workgroups.  A round evaluates one leaf of every chain still running: all workgroups pass over their rows for the active chains

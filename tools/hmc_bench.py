@@ -11,8 +11,13 @@ samples per second, and the passes' share of the fp64-VALU model of DESIGN.md 4.
 `--kernel nuts --adapt_metric diag|dense`: the NUTS rows with the metric learned in the windowed warm-up (csrc/nuts_adapt.h,
 DESIGN.md 4.17).  `--identity`: center 0 and transform I in place of the Laplace frame; `--scale S`: the feature columns scaled
 geometrically from 1 to S (badly scaled data, where a learned metric pays).
+`--kernel nuts --batch [--adapt_metric diag|dense]`: the seven coreset sizes of the logistic / Poisson harness at `coreset_size_max`
+1000 (k = 1, 3, 10, 31, 100, 316, 1000), 64 chains, scored by seven successive `sample` calls and by one `sample_many` with the same
+seeds (csrc/nuts.hip nuts_batch_kernel), the two alternating, three repeats each: both wall times, and the largest
+problem alone and inside the batch in us per leaf.  The draws are checked to be equal before anything is printed.
 
-    python tools/hmc_bench.py [--quick] [--kernel nuts [--stream | [--adapt_metric diag|dense] [--identity] [--scale S]]]
+    python tools/hmc_bench.py [--quick] [--kernel nuts [--stream | --batch [--adapt_metric diag|dense] |
+                                                         [--adapt_metric diag|dense] [--identity] [--scale S]]]
 """
 import json
 import os
@@ -130,6 +135,42 @@ def case_stream(bc, name, pts, wts, chains, n, center, transform, reps=2):
             print(json.dumps(row), flush=True)
 
 
+def case_batch(bc, rs, D, chains, n, adapt_metric, reps=3):
+    """Seven successive sample calls against one sample_many on the harness's size schedule, alternating."""
+    sizes = [int(k) for k in np.unique(np.logspace(0.0, 3.0, 7, dtype=np.int32))]
+    problems = []
+    for k in sizes:
+        pts, wts = data(k, D, rs), rs.uniform(1.0, 50.0, k)
+        mu, cov = model_lr.laplace_fit(pts, wts)
+        problems.append(dict(pts=pts, wts=wts, center=mu, transform=np.linalg.cholesky(cov).T))
+    kw = dict(chains=chains, kernel="nuts", max_depth=8, adapt_metric=adapt_metric)
+    many = bc.DeviceHMC("logistic", D, seed=1, **kw)
+    many.sample_many(problems, 10, 10, seeds=[1] * len(sizes))                     # (first-use costs, both ways)
+    for q in problems:
+        bc.DeviceHMC("logistic", D, seed=1, **kw).sample(q["pts"], q["wts"], 10, 10, center=q["center"], transform=q["transform"])
+    rows = []
+    for rep in range(reps):
+        t0 = time.perf_counter()
+        singles = [bc.DeviceHMC("logistic", D, seed=1, **kw).sample(q["pts"], q["wts"], n, n, center=q["center"], transform=q["transform"])
+                   for q in problems]
+        t_seq = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        batch = many.sample_many(problems, n, n, seeds=[1] * len(sizes))
+        t_many = time.perf_counter() - t0
+        for a, b in zip(singles, batch):
+            for name in ("samples", "step_size", "accept_rate", "tree_depth", "n_leapfrog", "leapfrog_total"):
+                assert np.array_equal(getattr(a, name), getattr(b, name)), name
+        evals = float(singles[-1].leapfrog_total.max()) + 1.0                      # (the largest problem's slowest chain)
+        rows.append(dict(case="batch", adapt_metric=adapt_metric, rep=rep, sizes=sizes, D=D, chains=chains, transitions=2 * n,
+                         wall_sequence_s=t_seq, wall_batch_s=t_many, sequence_over_batch=t_seq / t_many,
+                         launches_sequence_s=[r.seconds_per_iteration * 2 * n for r in singles], launch_batch_s=batch[0].batch_seconds,
+                         largest_alone_s=singles[-1].seconds_per_iteration * 2 * n,
+                         largest_alone_us_per_leaf=singles[-1].seconds_per_iteration * 2 * n * 1e6 / evals,
+                         batch_us_per_leaf_of_largest=batch[0].batch_seconds * 1e6 / evals))
+    for row in rows:
+        print(json.dumps(row), flush=True)
+
+
 def host_baseline(pts, wts, center, transform, n=30):
     D = pts.shape[1]
     host = pts.cpu().numpy() if hasattr(pts, "cpu") else pts
@@ -160,6 +201,9 @@ def main():
             case_stream(bc, "N=%d" % N, Z, None, chains, 10 if quick else 50, mu, np.linalg.cholesky(cov).T)
         return
     adapt_metric, identity, scale = option("--adapt_metric"), "--identity" in sys.argv, float(option("--scale") or 1.0)
+    if nuts and "--batch" in sys.argv:
+        case_batch(bc, rs, D, 64, 100 if quick else 500, adapt_metric)
+        return
     for k in (30, 300, 1000):
         pts, wts = data(k, D, rs), rs.uniform(1.0, 50.0, k)
         pts[:, :D - 1] *= scale ** (np.arange(D - 1) / (D - 2.0))

@@ -1,4 +1,4 @@
-"""Dev tool: VGPRs / spills / scratch of every kernel of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
+"""Dev tool: VGPRs / spills / scratch / static LDS of every kernel of one HIP source (hipcc -Rpass-analysis=kernel-resource-usage).
 
     python tools/kernel_resources.py bayesian-coresets_amd/csrc/proj.hip [filter]
 """
@@ -31,6 +31,7 @@ for mangled, name in zip(rows, names):
     spill = r.get("VGPRs Spill", 0)
     scratch = r.get("ScratchSize [bytes/lane]", 0)
     bad += (spill > 0) + (scratch > 0)
-    print("%-64s VGPRs %3d AGPRs %3d spill %3d scratch %4d B  SGPRs %3d  occupancy %d" % (
-        name[:64], r.get("VGPRs", -1), r.get("AGPRs", 0), spill, scratch, r.get("SGPRs", -1), r.get("Occupancy [waves/SIMD]", -1)))
+    print("%-64s VGPRs %3d AGPRs %3d spill %3d scratch %4d B  SGPRs %3d  occupancy %d  static LDS %d B" % (
+        name[:64], r.get("VGPRs", -1), r.get("AGPRs", 0), spill, scratch, r.get("TotalSGPRs", r.get("SGPRs", -1)),
+        r.get("Occupancy [waves/SIMD]", -1), r.get("LDS Size [bytes/block]", -1)))
 print("kernels with spills or scratch: %d" % bad)
