@@ -13,6 +13,7 @@ from .linreg_sampler import LinregPosteriorSampler
 from .laplace_sampler import LaplacePosteriorSampler
 from .gaussian_sampler import GaussianPosteriorSampler
 from .mcmc import DeviceHMC, log_joint_grad
+from .predictive import log_predictive, PredictiveResult
 from . import snnls
 from . import util
 

@@ -52,6 +52,7 @@ SYMBOLS = (
     "bcx_nuts_adapt", "bcx_nuts_adapt_ok", "bcx_nuts_adapt_schedule",
     "bcx_nuts_batch", "bcx_nuts_batch_table_bytes",
     "bcx_nuts_stream", "bcx_nuts_stream_scratch_bytes",
+    "bcx_log_predictive", "bcx_log_predictive_scratch_bytes",
     "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
 )
 
@@ -241,6 +242,9 @@ def load():
                                vp, i64]
     lib.bcx_nuts_stream_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_nuts_stream_scratch_bytes.argtypes = [i64, i32, i32, i32]
+    sigs["bcx_log_predictive"] = [vp, i32, vp, i64, i64, i32, vp, i64, i64, i32, vp, vp, vp, i64]
+    lib.bcx_log_predictive_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_log_predictive_scratch_bytes.argtypes = [i64, i32, i64, i32]
     lib.bcx_hmc_stream_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_hmc_stream_scratch_bytes.argtypes = [i64, i32, i32]
     lib.bcx_psvi_gradient_scratch_bytes.restype = ctypes.c_int64

@@ -239,6 +239,8 @@ int bcx_launch_screen(bcx_solver* s);
 int bcx_launch_resume_store(bcx_solver* s);
 // proj.hip: sets the message bcx_project_last_error() returns (the entry points outside the solver report through it)
 void bcx_project_set_error(const std::string& msg);
+// proj.hip: the likelihood tables of proj_math.h (PJT_DOUBLES doubles) in the current device's memory; nullptr: no memory
+const double* proj_tables();
 
 #ifdef BCX_TIMING
 #define BCX_STAMP(st, i) do { if (threadIdx.x == 0) (st)->dbg_t[i] = wall_clock64(); } while (0)

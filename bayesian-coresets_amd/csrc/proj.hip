@@ -1247,7 +1247,8 @@ static int proj_grid(int64_t N) {
 }
 
 // The likelihood tables of proj_math.h in device memory: built once per device (from long double, on the host), never freed.
-static const double* proj_tables() {
+// (Also csrc/predict.hip's: declared in bcx_internal.h.)
+const double* proj_tables() {
   static std::mutex mu;
   static double* tabs[64];
   int dev = 0;

@@ -25,7 +25,11 @@ streamed NUTS (bc.DeviceHMC(kernel="nuts", stream=True)); the full-data cache fi
 that fits the adapting LDS-resident NUTS learns a metric in its windowed warm-up; the others run as without it.
 `--mcmc_kernel nuts --mcmc_batch`: the coresets of all sizes are kept during the build and scored after it by one
 mcmc.run_many -- ONE launch for all that fit the LDS-resident NUTS; every column is the unbatched run's but
-`mcmc_time_per_itr`, which is the launch's time over the coresets in it."""
+`mcmc_time_per_itr`, which is the launch's time over the coresets in it.
+`--eval mcmc --mcmc_test_rows K`: the last K rows of the loaded data are held out before anything is fitted or built, and two
+columns score the draws on them by bc.log_predictive: `test_ll`, the mean over the held-out rows of the log
+predictive density under the draws of every coreset size (the prior draws for an empty coreset), and `full_test_ll`, the same
+under the full-data draws."""
 import argparse
 import os
 import sys
@@ -62,12 +66,13 @@ def load(a, rs):
     return model_poiss.synthetic_rows(a.data_num, a.data_dim, rs)
 
 
-def full_data_samples(a, Z, nuts_stream=False):
+def full_data_samples(a, Z, nuts_stream=False, held_out=0):
     """The full-data draws and the sampler's time per iteration, cached per model / data set / trial (main.py:107-127) -- and per
-    kernel when the full-data chain is the streamed NUTS: a cached HMC run is never read as a NUTS one, nor the reverse."""
+    kernel when the full-data chain is the streamed NUTS: a cached HMC run is never read as a NUTS one, nor the reverse -- and per
+    number of held-out rows (--mcmc_test_rows), which are not part of the full data."""
     folder = os.path.join(a.results_folder, "mcmc_cache")
     name = "full_samples_%s_%s_%d_%d_%d_%d%s.npz" % (a.model, os.path.basename(a.dataset), a.data_num, a.data_dim, a.trial, a.mcmc_samples_full,
-                                                     "_nuts" if nuts_stream else "")
+                                                     ("_nuts" if nuts_stream else "") + ("_t%d" % held_out if held_out else ""))
     path = os.path.join(folder, name)
     if os.path.exists(path):
         d = np.load(path)
@@ -99,6 +104,11 @@ def run(a):
     batch = bool(getattr(a, "mcmc_batch", False))                  # (absent unless given: the parser suppresses its default)
     if batch and not (use_mcmc and mcmc_kernel == "nuts"):
         raise ValueError("--mcmc_batch goes with --eval mcmc --mcmc_kernel nuts")
+    test_rows = getattr(a, "mcmc_test_rows", None)                 # (absent unless given: the parser suppresses its default)
+    if test_rows is not None and not use_mcmc:
+        raise ValueError("--mcmc_test_rows goes with --eval mcmc")
+    if test_rows is not None and test_rows < 1:
+        raise ValueError("--mcmc_test_rows: at least one row")
     stream = bool(getattr(a, "laplace_stream", False))     # (absent unless given: the parser suppresses its default)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
@@ -112,6 +122,11 @@ def run(a):
     else:
         Ms = np.unique(np.linspace(1, a.coreset_size_max, a.coreset_num_sizes, dtype=np.int32))
     Z = load(a, np.random)
+    Zt = None
+    if test_rows is not None:                                                  # held out before anything is fitted or built
+        if test_rows >= Z.shape[0]:
+            raise ValueError("--mcmc_test_rows: %d rows to hold out of %d" % (test_rows, Z.shape[0]))
+        Z, Zt = Z[:-test_rows], Z[-test_rows:]
     D = Z.shape[1] if a.model == "lr" else Z.shape[1] - 1
     family = "logistic" if a.model == "lr" else "poisson"
     print("dataset %s: %d rows, %d parameters, model %s, trial %d" % (a.dataset, Z.shape[0], D, a.model, a.trial))
@@ -170,11 +185,13 @@ def run(a):
     n = Ms.shape[0]
     extra = {}
     if use_mcmc:
-        full_samples, full_t = full_data_samples(a, Z, nuts_stream)
+        full_samples, full_t = full_data_samples(a, Z, nuts_stream, test_rows or 0)
         mup, Sigp = full_samples.mean(axis=0), np.cov(full_samples, rowvar=False)     # main.py:137-138
         SigpInv = np.linalg.inv(Sigp)
         _, gfs = bc.log_joint_grad(family, Z, None, full_samples)
         extra = dict(Fs=np.zeros(n), full_mcmc_time_per_itr=np.full(n, full_t), mcmc_time_per_itr=np.zeros(n))
+        if Zt is not None:
+            extra.update(test_ll=np.zeros(n), full_test_ll=np.full(n, bc.log_predictive(family, Zt, full_samples).lppd.mean()))
     cputs, walls, csizes = np.zeros(n), np.zeros(n), np.zeros(n)
     rklw, fklw, mu_errs, Sig_errs = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
 
@@ -188,6 +205,8 @@ def run(a):
         _, gcs = bc.log_joint_grad(family, cpts, cwts, full_samples)
         extra["Fs"][m] = ((gcs - gfs) ** 2).sum(axis=1).mean()                  # main.py:226-228
         extra["mcmc_time_per_itr"][m] = t_cst / (a.mcmc_samples_coreset * 2)
+        if Zt is not None:
+            extra["test_ll"][m] = bc.log_predictive(family, Zt, cst).lppd.mean()
         score(m, cst.mean(axis=0), np.cov(cst, rowvar=False))
 
     kept = []                               # --mcmc_batch: (m, points, weights) of every size, scored behind the loop
@@ -248,6 +267,10 @@ def parser():
     ap.add_argument("--mcmc_batch", action="store_true", default=argparse.SUPPRESS,         # (result files keep their argument set)
                     help="with --mcmc_kernel nuts: keep every size's coreset and score them behind the build in one launch "
                          "(bc.DeviceHMC.sample_many); mcmc_time_per_itr is then the launch's time over the coresets in it")
+    ap.add_argument("--mcmc_test_rows", type=int, default=argparse.SUPPRESS,                 # (result files keep their argument set)
+                    help="with --eval mcmc: hold out the last K rows of the data before anything is fitted or built and add the columns "
+                         "test_ll / full_test_ll, their mean log predictive density under each coreset's / the full data's draws "
+                         "(bc.log_predictive)")
     ap.add_argument("--proj_dim", type=int, default=500)
     ap.add_argument("--coreset_size_max", type=int, default=1000)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)

@@ -655,6 +655,22 @@ int bcx_nuts_stream(void* stream, int32_t family, int64_t N, int32_t D, const vo
                     int32_t max_depth, double eps0, double fixed_eps, const void* noise_dev, int64_t noise_ld, int32_t ld,
                     void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev,
                     void* status_dev, void* scratch_dev, int64_t scratch_bytes);
+/* The log predictive density of N held-out rows under S posterior draws of the logistic / Poisson regression models
+ * (csrc/predict.hip), with ll the reference's full log-likelihood (examples/common/model_lr.py:25-32;
+ * model_poiss.py:25-38, the Poisson -log y! included):
+ *     lppd_dev[n] = logsumexp_s ll(z_n, theta_s) - log S,      mean_dev[n] = 1/S sum_s ll(z_n, theta_s)   (mean_dev may be NULL).
+ * Z_dev: N x ldz rows as bcx_log_joint_grad reads them (logistic y x, Poisson [x, y]); Theta_dev: S x ldt draws.  N >= 0, S >= 1,
+ * 1 <= D <= 32.  One pass over the rows: the products on the fp64 matrix pipe, the likelihood and an online log-sum-exp (running
+ * maximum, rescaled sum, sum of ll) per row in registers; the N x S table is never written.  `splits` cuts the draws into that many
+ * contiguous ranges [S i / splits, S (i + 1) / splits) on different workgroups (a range may be empty), whose records are combined
+ * per row in range order by a second kernel; 0: the library chooses from N, S and the device's CU count; 1 .. 4096: honoured
+ * exactly.  No floating-point atomics: the same inputs, splits and device give the same bits.  A non-finite value in a row or a draw
+ * makes the affected rows' outputs NaN (a row: its own; a draw: every row's); ll = -inf for some draws contributes exact zeros.
+ * work_dev: bcx_log_predictive_scratch_bytes(N, D, S, splits) bytes (-1: out of range), work_bytes its size.  BCX_ERR_ARG for
+ * anything else.  Asynchronous on `stream`. */
+int64_t bcx_log_predictive_scratch_bytes(int64_t N, int32_t D, int64_t S, int32_t splits);
+int bcx_log_predictive(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D, const void* Theta_dev,
+                       int64_t S, int64_t ldt, int32_t splits, void* lppd_dev, void* mean_dev, void* work_dev, int64_t work_bytes);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 
