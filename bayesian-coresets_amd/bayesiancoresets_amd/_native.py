@@ -27,7 +27,7 @@ SYMBOLS = (
     "bcx_finalize", "bcx_build_begin", "bcx_step_scan", "bcx_step_apply", "bcx_build_enqueue", "bcx_build_poll",
     "bcx_step_scan_exact", "bcx_build_trace", "bcx_active_count", "bcx_get_weights", "bcx_error", "bcx_optimize",
     "bcx_reset", "bcx_reached_numeric_limit", "bcx_get_vector", "bcx_get_norms", "bcx_get_stored_rows", "bcx_argmax_correlation", "bcx_time_scan",
-    "bcx_stats", "bcx_screen_stats", "bcx_screen_read", "bcx_profile_scan", "bcx_profile_read", "bcx_version",
+    "bcx_stats", "bcx_screen_stats", "bcx_screen4_stats", "bcx_screen_read", "bcx_profile_scan", "bcx_profile_read", "bcx_version",
     "bcx_project_write", "bcx_project_colsum", "bcx_project_select", "bcx_project_last_error",
     "bcx_build_enqueue_exact", "bcx_exchange_export", "bcx_exchange_attach", "bcx_exchange_probe", "bcx_exchange_disable", "bcx_exchange_set_timeout",
     "bcx_set_check_monotone", "bcx_project_profile", "bcx_project_profile_read", "bcx_exchange_stats", "bcx_load_rows_flags", "bcx_project_write_raw", "bcx_omp_stats", "bcx_project_select_ws", "bcx_project_select_scratch_bytes",
@@ -160,6 +160,7 @@ def load():
         "bcx_stats": [vp, P(i64), P(i64), P(i64)],
         "bcx_omp_stats": [vp, vp],
         "bcx_screen_stats": [vp, vp],
+        "bcx_screen4_stats": [vp, vp],
         "bcx_screen_read": [vp, i64, i64, vp, vp, vp, P(i32)],
         "bcx_profile_scan": [vp, i32],
         "bcx_profile_read": [vp, P(dbl), P(i64)],
@@ -556,13 +557,23 @@ class Engine(object):
     SCREEN_DROP = {0: "in use", 1: "dropped by the overflow rule until reset()", 2: "no device memory for the shadow",
                    3: "switched off or not applicable"}
 
+    SCREEN4_STATE = {0: "in use", 1: "dropped to 8-bit", 2: "no device memory for the second shadow",
+                     3: "switched off or not applicable"}
+
     def screen_stats(self):
         """The 8-bit screening tier: iterations screened, rows that survived it (re-scored from the stored rows), capture
-        overflows and iterations redone with the storage-precision scan (not exact fallbacks), its state and footprint."""
+        overflows and iterations redone with the storage-precision scan (not exact fallbacks; 8-bit and 4-bit iterations
+        alike, the 4-bit ones alone are front4_redos), its state and footprint."""
         out = (ctypes.c_int64 * 8)()
         self._check(self.lib.bcx_screen_stats(self.h, out))
+        o4 = (ctypes.c_int64 * 8)()
+        self._check(self.lib.bcx_screen4_stats(self.h, o4))
         return {"active": bool(out[0]), "screened": out[1], "survivors": out[2], "overflows": out[3], "storage_redos": out[4],
-                "state": self.SCREEN_DROP.get(int(out[5]), "?"), "device_bytes": out[6], "build_us": out[7]}
+                "state": self.SCREEN_DROP.get(int(out[5]), "?"), "device_bytes": out[6], "build_us": out[7],
+                # the 4-bit front pass in front of the tier (csrc/screen4.hip)
+                "front4_active": bool(o4[0]), "front4_iterations": o4[1], "front4_listed": o4[2], "front4_overflows": o4[3],
+                "front4_redos": o4[4], "front4_state": self.SCREEN4_STATE.get(int(o4[5]), "?"), "front4_device_bytes": o4[6],
+                "front4_drops": o4[7]}
 
     def screen_read(self, begin=0, count=None):
         """(codes uint8 [count, ld8], scales fp32 [count], bounds fp32 [count]) of the tier's shadow rows."""

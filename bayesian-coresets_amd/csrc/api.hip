@@ -37,7 +37,7 @@ static void free_all(bcx_solver* s) {
   for (size_t w = 0; w < s->peer_mbox.size(); ++w)
     if (s->peer_mbox[w] && s->peer_mbox[w] != s->mbox) (void)hipIpcCloseMemHandle(s->peer_mbox[w]);
   void* xptrs[] = {s->mbox, s->peer_tab, s->xseq, s->xprobe, s->rec_gather, s->grid_counter, s->fin_part, s->gram_work, s->warm_buf,
-                   s->Aq, s->scr_sb, s->scr_partials, s->scr_stat};
+                   s->Aq, s->scr_sb, s->scr_partials, s->scr_stat, s->A4, s->s4_sb, s->s4_list, s->s4_counts, s->s4_head};
   for (void* p : xptrs)
     if (p) (void)hipFree(p);
   for (auto& ev : s->prof_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -63,6 +63,8 @@ extern "C" int bcx_create(const bcx_config* cfg, bcx_solver** out) {
   s->cfg = *cfg;
   if (s->cfg.refresh_every == 0) s->cfg.refresh_every = 64;
   if (const char* e = bcx_dev_env("BCX_SCREEN8")) s->scr_enabled = atoi(e) != 0;   // dev: 0 = the parent's path (storage-precision scan only)
+  if (const char* e = bcx_dev_env("BCX_SCREEN4_SEGCAP")) { const int v = atoi(e); if (v >= 1 && v <= BCX_S4_SEG_CAP) s->s4_seg_cap = v; }   // dev: a small list segment, so that small inputs fill it
+  if (const char* e = bcx_dev_env("BCX_SCREEN4")) s->s4_enabled = atoi(e) != 0;   // dev: 0 = the 8-bit tier alone, as before the 4-bit front pass
   hipError_t e = hipSetDevice(cfg->device);
   if (e != hipSuccess) { g_create_err = std::string("hipSetDevice: ") + hipGetErrorString(e); delete s; return BCX_ERR_HIP; }
   const int d = cfg->d;
@@ -290,7 +292,8 @@ static int load_rows(bcx_solver* s, const void* src, int32_t src_is_device, int3
     }
   }
   s->rows_loaded += rows;
-  s->scr_valid = false;      // the shadow (screen8.hip) is rebuilt from the new rows before the next enqueued iteration
+  s->scr_valid = false;      // the shadows (screen8.hip, screen4.hip) are rebuilt from the new rows before the next enqueued iteration
+  s->s4_valid = false;
   return BCX_OK;
 }
 
@@ -460,12 +463,13 @@ static int step_scan(bcx_solver* s, void* send_dev, int exact, bool with_tail) {
   return bcx_launch_resolve(s, send, exact);
 }
 
-// the scan of one enqueued iteration: the 8-bit screen + refine (screen8.hip) or the storage-precision / exact scan
-static int front_scan(bcx_solver* s, int exact, bool tier) {
+// the scan of one enqueued iteration: the 4-bit front pass + second stage + refine (screen4.hip), the 8-bit screen + refine
+// (screen8.hip) or the storage-precision / exact scan
+static int front_scan(bcx_solver* s, int exact, bool tier, bool four) {
   int rc;
   if (exact && (rc = bcx_launch_resume_exact(s))) return rc;
   if ((rc = prof_begin(s))) return rc;
-  if ((rc = (tier && !exact) ? bcx_launch_screen(s) : bcx_launch_scan(s, exact))) return rc;
+  if ((rc = (tier && !exact) ? (four ? bcx_launch_screen4(s) : bcx_launch_screen(s)) : bcx_launch_scan(s, exact))) return rc;
   return prof_end(s);
 }
 
@@ -479,7 +483,7 @@ extern "C" int bcx_step_apply(bcx_solver* s, const void* recv_dev) {
 }
 
 // one whole iteration without the host: single shard, or row shards with an attached peer mailbox
-static int enqueue_one(bcx_solver* s, int exact, bool tier) {
+static int enqueue_one(bcx_solver* s, int exact, bool tier, bool four = false) {
   if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
   int rc;
   if (s->cfg.world_size != 1) {
@@ -487,10 +491,10 @@ static int enqueue_one(bcx_solver* s, int exact, bool tier) {
       s->err = "bcx_build_enqueue on a row shard needs bcx_exchange_attach (or drive bcx_step_scan / bcx_step_apply)";
       return BCX_ERR_ARG;
     }
-    if ((rc = front_scan(s, exact, tier))) return rc;
+    if ((rc = front_scan(s, exact, tier, false))) return rc;
     return bcx_launch_tail_exchange(s, exact);
   }
-  if ((rc = front_scan(s, exact, tier))) return rc;
+  if ((rc = front_scan(s, exact, tier, four))) return rc;
   if (s->cfg.alg == BCX_ALG_OMP) {
     // scan, then the fused resolve + OMP step (omp_lh.hip); where that does not apply: resolve_kernel + the multi-kernel step
     rc = bcx_launch_omp_fused(s, exact);
@@ -506,11 +510,18 @@ static int enqueue_many(bcx_solver* s, int64_t itrs) {
   int rc = bcx_screen_build(s);
   if (rc != BCX_OK) return rc;
   const bool tier = bcx_screen_on(s) && s->scr_valid;
+  if (tier && (rc = bcx_screen4_build(s))) return rc;
+  const bool tier4 = tier && bcx_screen4_on(s) && s->s4_valid;
   s->scr_batch = false;
   for (int64_t i = 0; i < itrs; ++i) {
     s->scr_batch = tier;
-    rc = enqueue_one(s, 0, tier);
+    // The 4-bit front pass needs sentinel rows: the partials of the tier iteration enqueued just before.  s4_warm counts the
+    // plain 8-bit iterations still due: two after finalize / reset / a reload (the second query after a fresh start is still
+    // far from the first), one after a redone iteration.  Decided here, without a device round trip.
+    const bool four = tier4 && s->s4_warm == 0;
+    rc = enqueue_one(s, 0, tier, four);
     if (rc != BCX_OK) return rc;
+    if (tier && s->s4_warm > 0) s->s4_warm -= 1;
   }
   return BCX_OK;
 }
@@ -661,10 +672,21 @@ extern "C" int bcx_build_poll(bcx_solver* s, int64_t* n_done, int32_t* need_exac
     unsigned long long st8[SCR_WORDS];
     BCX_HIP(hipMemcpy(st8, s->scr_stat, sizeof st8, hipMemcpyDeviceToHost));
     if (!st8[SCR_ARMED]) break;                       // the storage-precision redo itself halted
-    s->scr_halts += 1;
-    for (int i = 3; i > 0; --i) s->scr_ovf_at[i] = s->scr_ovf_at[i - 1];
-    s->scr_ovf_at[0] = st8[SCR_ITERS];
-    if (s->scr_halts >= 4 && s->scr_ovf_at[0] - s->scr_ovf_at[3] < 256) s->scr_dropped = 1;
+    if (st8[SCR4_LAST] != 0 && st8[SCR4_LAST] == st8[SCR_ITERS]) {
+      // the halted iteration went through the 4-bit front pass (a full list segment, or a capture overflow behind it): the
+      // same rule on the 4-bit tier's own count drops the solver to the 8-bit tier, never straight to the storage scan
+      s->s4_halts += 1;
+      for (int i = 3; i > 0; --i) s->s4_ovf_at[i] = s->s4_ovf_at[i - 1];
+      s->s4_ovf_at[0] = st8[SCR4_ITERS];
+      s->s4_redos += 1;
+      if (s->s4_halts >= 4 && s->s4_ovf_at[0] - s->s4_ovf_at[3] < 256 && !s->s4_dropped) { s->s4_dropped = 1; s->s4_drops += 1; }
+    } else {
+      s->scr_halts += 1;
+      for (int i = 3; i > 0; --i) s->scr_ovf_at[i] = s->scr_ovf_at[i - 1];
+      s->scr_ovf_at[0] = st8[SCR_ITERS];
+      if (s->scr_halts >= 4 && s->scr_ovf_at[0] - s->scr_ovf_at[3] < 256) s->scr_dropped = 1;
+    }
+    if (s->s4_warm < 1) s->s4_warm = 1;                // the redo writes no tier partials: one plain 8-bit iteration first
     if ((rc = bcx_launch_resume_store(s))) return rc;
     if ((rc = enqueue_one(s, 0, false))) return rc;
     const int64_t rest = h.itrs - h.it - 1;
@@ -694,7 +716,9 @@ extern "C" int bcx_build_poll(bcx_solver* s, int64_t* n_done, int32_t* need_exac
     // did the scan -- one that "read" the shard faster than 1.5x the HBM peak cannot have (a whole batch may consist
     // of such launches, e.g. everything enqueued after a latch, so the test is absolute, not relative to the batch)
     // (with the 8-bit tier on, a launch reads one byte per element)
-    const double min_ms = (double)s->cfg.n_local * s->cfg.d * ((bcx_screen_on(s) && s->scr_valid) ? 1 : s->elem) / 12.0e9;
+    // (half a byte with the 4-bit front pass)
+    const bool on8 = bcx_screen_on(s) && s->scr_valid;
+    const double min_ms = (double)s->cfg.n_local * s->cfg.d * (on8 ? ((bcx_screen4_on(s) && s->s4_valid) ? 0.5 : 1.0) : (double)s->elem) / 12.0e9;
     for (size_t i = 0; i < s->prof_used; ++i) {
       float ms = 0.f;
       if (hipEventElapsedTime(&ms, s->prof_events[i].first, s->prof_events[i].second) != hipSuccess) continue;
@@ -778,6 +802,10 @@ extern "C" int bcx_reset(bcx_solver* s) {
   if (s->scr_dropped == 1) s->scr_dropped = 0;      // the overflow rule's drop lasts until here
   s->scr_halts = 0;
   for (int i = 0; i < 4; ++i) s->scr_ovf_at[i] = 0;
+  if (s->s4_dropped == 1) s->s4_dropped = 0;
+  s->s4_halts = 0;
+  for (int i = 0; i < 4; ++i) s->s4_ovf_at[i] = 0;
+  s->s4_warm = 2;                                   // a fresh start: the first queries are far from the last ones
   // error() with an empty list must give ||b|| computed the same way as after finalize
   return bcx_launch_error_refresh(s);
 }
@@ -969,6 +997,37 @@ extern "C" int bcx_screen_stats(bcx_solver* s, int64_t* out8) {
   out8[5] = !possible ? 3 : s->scr_dropped;
   out8[6] = s->Aq ? (int64_t)s->scr_cap_rows * (s->ld8 + 8) + (int64_t)BCX_MAX_PARTIALS * BCX_PARTIAL_BYTES + SCR_WORDS * 8 : 0;
   out8[7] = (int64_t)(s->scr_build_ms * 1e3f);
+  return BCX_OK;
+}
+
+// The 4-bit front pass (screen4.hip) since construction: out8 = {1 if iterations enqueued next go through it once sentinel
+// rows exist, 4-bit iterations, rows listed for the second stage, list segments that were full, halted 4-bit iterations
+// that were redone, state (0 in use, 1 dropped to the 8-bit tier until bcx_reset, 2 no device memory for the second shadow,
+// 3 switched off or not applicable), device bytes of the second shadow and its list, times the drop rule fired}.
+extern "C" int bcx_screen4_stats(bcx_solver* s, int64_t* out8) {
+  if (!s || !out8) return BCX_ERR_ARG;
+  unsigned long long st8[SCR_WORDS];
+  for (auto& w : st8) w = 0;
+  if (s->scr_stat) {
+    BCX_HIP(hipSetDevice(s->cfg.device));
+    BCX_HIP(hipStreamSynchronize(s->stream));
+    BCX_HIP(hipMemcpy(st8, s->scr_stat, sizeof st8, hipMemcpyDeviceToHost));
+  }
+  const bool possible = s->s4_enabled && s->scr_enabled && s->cfg.store_dtype != BCX_F64 && s->cfg.d <= 4096 && s->cfg.n_local > 0 &&
+                        s->cfg.alg != BCX_ALG_GIGA && s->cfg.world_size == 1;
+  if (st8[SCR4_PENDING] && s->s4_counts && s->s4_n_seg > 0) {   // the last 4-bit iteration: booked on the device by the next one
+    std::vector<int32_t> cnt((size_t)s->s4_n_seg);
+    BCX_HIP(hipMemcpy(cnt.data(), s->s4_counts, cnt.size() * 4, hipMemcpyDeviceToHost));
+    for (int32_t c : cnt) { st8[SCR4_LISTED] += (unsigned long long)std::min<int32_t>(c, s->s4_seg_cap); st8[SCR4_OVERFLOWS] += c > s->s4_seg_cap; }
+  }
+  out8[0] = bcx_screen4_on(s) ? 1 : 0;
+  out8[1] = (int64_t)st8[SCR4_ITERS];
+  out8[2] = (int64_t)st8[SCR4_LISTED];
+  out8[3] = (int64_t)st8[SCR4_OVERFLOWS];
+  out8[4] = s->s4_redos;
+  out8[5] = !possible ? 3 : s->s4_dropped;
+  out8[6] = s->A4 ? (int64_t)s->s4_cap_rows * (s->ld4 + 8) + (int64_t)BCX_MAX_PARTIALS * (BCX_S4_SEG_CAP + 1) * 4 : 0;
+  out8[7] = s->s4_drops;
   return BCX_OK;
 }
 

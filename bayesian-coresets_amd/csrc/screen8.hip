@@ -41,13 +41,13 @@
 // BCX_SCREEN_MAX_SURV survivors, is an overflow: the refine kernel hands resolve_core a partial that makes it report
 // BCX_REC_OVERFLOW, the state machine halts as for a candidate-window overflow, and bcx_build_poll redoes that iteration with
 // the storage-precision scan (api.hip).  tools/screen8_model.py emulates this capture; DESIGN.md 4.1 has its numbers.
+//
+// The scoring and interval code (Q16, dot16, load_q16, screen_interval) lives in screen_core.h: the second stage of the 4-bit
+// front pass (screen4.hip) scores its listed rows with the same text and hands its partials to refine_kernel here.
 #include <float.h>
-#include "scan_core.h"
+#include "screen_core.h"
 
-#define BCX_SCREEN_WAVES (BCX_SCAN_THREADS / 64)
 #define BCX_REFINE_THREADS 1024
-
-struct Q16 { float4 a, b, c, d; };   // the 16 fp32 query values matching one 16-byte piece of codes
 
 struct ScreenArgs {
   const uint4* Aq;     // n x ldv pieces of 16 codes
@@ -62,36 +62,6 @@ struct ScreenArgs {
   float kacc;          // accumulation term per unit of scale and qscale (see the head of this file)
   float err_coef;      // the storage tier's own term
 };
-
-__device__ __forceinline__ float dot16(const uint4& x, const Q16& q, float acc) {
-  // (float)(byte k of a word): v_cvt_f32_ubyte0..3, one instruction per element, exact
-  acc = fmaf((float)(x.x & 0xffu), q.a.x, acc); acc = fmaf((float)((x.x >> 8) & 0xffu), q.a.y, acc);
-  acc = fmaf((float)((x.x >> 16) & 0xffu), q.a.z, acc); acc = fmaf((float)(x.x >> 24), q.a.w, acc);
-  acc = fmaf((float)(x.y & 0xffu), q.b.x, acc); acc = fmaf((float)((x.y >> 8) & 0xffu), q.b.y, acc);
-  acc = fmaf((float)((x.y >> 16) & 0xffu), q.b.z, acc); acc = fmaf((float)(x.y >> 24), q.b.w, acc);
-  acc = fmaf((float)(x.z & 0xffu), q.c.x, acc); acc = fmaf((float)((x.z >> 8) & 0xffu), q.c.y, acc);
-  acc = fmaf((float)((x.z >> 16) & 0xffu), q.c.z, acc); acc = fmaf((float)(x.z >> 24), q.c.w, acc);
-  acc = fmaf((float)(x.w & 0xffu), q.d.x, acc); acc = fmaf((float)((x.w >> 8) & 0xffu), q.d.y, acc);
-  acc = fmaf((float)((x.w >> 16) & 0xffu), q.d.z, acc); acc = fmaf((float)(x.w >> 24), q.d.w, acc);
-  return acc;
-}
-
-// the 16 query values of piece v (columns 16 v .. 16 v + 15; beyond d: zero), and their sum
-__device__ __forceinline__ Q16 load_q16(const float* q, int v, int d, bool ok, float& sum) {
-  float t[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) {
-    const int j = 16 * v + k;
-    const bool in = ok && j < d;
-    const float val = q[in ? j : 0];
-    t[k] = in ? val : 0.0f;
-    sum += t[k];
-  }
-  Q16 r;
-  r.a = make_float4(t[0], t[1], t[2], t[3]); r.b = make_float4(t[4], t[5], t[6], t[7]);
-  r.c = make_float4(t[8], t[9], t[10], t[11]); r.d = make_float4(t[12], t[13], t[14], t[15]);
-  return r;
-}
 
 template <bool DUAL, int G, int CH, int UR>
 __global__ __launch_bounds__(BCX_SCAN_THREADS) void screen_kernel(ScreenArgs a) {
@@ -177,10 +147,9 @@ __global__ __launch_bounds__(BCX_SCAN_THREADS) void screen_kernel(ScreenArgs a) 
       const int64_t myrow = tracked(r0, t);
       const float scale = sbv[t].x, bound = sbv[t].y;
       s0 *= scale; s1 *= scale;
-      const float e = (fmaf(scale, a.kacc, bound) * 1.000002f + a.err_coef) * qscale;
       float U, L;
-      if (DUAL) giga_interval(s0, s1, e, U, L);
-      else { const float ee = e + fabsf(s0) * 2e-7f; U = s0 + ee; L = s0 - ee; }
+      if (DUAL) giga_interval(s0, s1, (fmaf(scale, a.kacc, bound) * 1.000002f + a.err_coef) * qscale, U, L);
+      else screen_interval(s0, scale, bound, a.kacc, a.err_coef, qscale, U, L);
       if (!(myrow < n)) { U = -INFINITY; L = -INFINITY; }
       track_update<float>(tr, U, L, (int)myrow);
     }
@@ -396,12 +365,6 @@ int bcx_screen_build(bcx_solver* s) {
   return BCX_OK;
 }
 
-static int pick_group8(int nvec) {
-  int g = 1;
-  while (g < 64 && g < nvec) g <<= 1;
-  return g;
-}
-
 template <bool DUAL> static int launch_screen_t(bcx_solver* s, const ScreenArgs& a, int G, int CH, int UR, int grid) {
   dim3 g(grid), b(BCX_SCAN_THREADS);
 #define L(GG, CC, UU)                                                                            \
@@ -420,7 +383,6 @@ template <bool DUAL> static int launch_screen_t(bcx_solver* s, const ScreenArgs&
 // BCX_SCREEN_MAX_SURV storage-precision partials, exactly what the tail kernels read after bcx_launch_scan.
 int bcx_launch_screen(bcx_solver* s) {
   const int d = s->cfg.d;
-  const bool f16 = s->cfg.store_dtype == BCX_F16;
   ScreenArgs a;
   a.Aq = (const uint4*)s->Aq;
   a.sb = (const float2*)s->scr_sb;
@@ -430,14 +392,9 @@ int bcx_launch_screen(bcx_solver* s) {
   a.n = s->cfg.n_local;
   a.ldv = s->ld8 / 16;
   a.d = d;
-  const int G = pick_group8(a.ldv);
-  int CH = (a.ldv + G - 1) / G, chp = 1;
-  while (chp < CH) chp <<= 1;
-  CH = chp;
-  int lg = 0;
-  while ((1 << lg) < G) ++lg;
-  const double u = 5.9604644775390625e-08;
-  a.kacc = (float)(1.3 * u * (511.0 * (16.0 * CH + 1.0) + 127.0 * lg) * sqrt((double)d));
+  const int G = screen_group(a.ldv);
+  const int CH = screen_chunks(a.ldv, G);
+  a.kacc = screen_kacc(G, CH, d);
   // the storage tier's own term, as bcx_scan_plan states it for the stored rows
   ScanArgs sa;
   ScanPlan sp;
@@ -459,12 +416,22 @@ int bcx_launch_screen(bcx_solver* s) {
   const bool dual = s->cfg.alg == BCX_ALG_GIGA;
   rc = dual ? launch_screen_t<true>(s, a, G, CH, ur, grid) : launch_screen_t<false>(s, a, G, CH, ur, grid);
   if (rc != BCX_OK) return rc;
+  s->scr_n_in = n_in;     // (these partials also name the next 4-bit iteration's sentinel rows, screen4.hip)
+  return bcx_launch_refine(s, n_in);
+}
+
+// The refine kernel over the n_in per-wave partials in s->scr_partials (written by screen_kernel, or by the second stage of
+// the 4-bit tier in the same format).
+int bcx_launch_refine(bcx_solver* s, int n_in) {
+  const int d = s->cfg.d;
+  const bool f16 = s->cfg.store_dtype == BCX_F16;
+  const double u = 5.9604644775390625e-08;
   RefineArgs r;
-  r.in = a.out; r.n_in = n_in;
+  r.in = partial_view(s->scr_partials, n_in); r.n_in = n_in;
   r.out = partial_view(s->partials, BCX_SCREEN_MAX_SURV);
   r.st = s->st; r.stat = s->scr_stat;
   r.An = s->An; r.q = (const float*)s->qst;
-  r.store_f16 = f16; r.ld = s->ld; r.ldq = s->ld; r.d = d; r.dual = dual;
+  r.store_f16 = f16; r.ld = s->ld; r.ldq = s->ld; r.d = d; r.dual = s->cfg.alg == BCX_ALG_GIGA;
   // stored row and fp32 query multiplied and summed in fp64: what is left is their own rounding (2 u, fp16: its storage term)
   // and d 2^-53; 30 % head room as in bcx_scan_plan
   r.coef_mid = 1.3 * u * 3.0;

@@ -202,8 +202,18 @@ int bcx_stats(bcx_solver* s, int64_t* exact_fallbacks, int64_t* candidates, int6
  * rows, capture overflows, iterations redone with the storage-precision scan (these are NOT exact fallbacks), drop state
  * (0 in use, 1 dropped until bcx_reset after 4 redone iterations within 256 screened ones, 2 no device memory for the
  * shadow, 3 switched off or not applicable), device bytes held by the tier, microseconds the last shadow build took}.
- * bcx_stats keeps its meaning: `candidates` counts rows re-scored in fp64. */
+ * bcx_stats keeps its meaning: `candidates` counts rows re-scored in fp64.  With the 4-bit front pass (below) the redone
+ * iterations count every tier iteration redone with the storage-precision scan, 8-bit and 4-bit alike; bcx_screen4_stats
+ * gives the 4-bit ones on their own. */
 int bcx_screen_stats(bcx_solver* s, int64_t* out8);
+/* The 4-bit front pass in front of that tier (FW / OMP on one shard, wherever the 8-bit tier runs): an iteration streams a
+ * half-byte-per-element second shadow against a threshold taken, in 8 bits, from the rows that led the previous iteration,
+ * and reads the 8-bit shadow only for the rows it lists; selections do not change.
+ * out8 = {1 if the iterations enqueued next go through it (after the one or two plain 8-bit iterations that give it its
+ * first threshold), 4-bit iterations, rows listed, list segments that were full, halted 4-bit iterations that were redone,
+ * state (0 in use, 1 dropped to the 8-bit tier until bcx_reset after 4 redone iterations within 256 4-bit ones, 2 no device
+ * memory for the second shadow, 3 switched off or not applicable), device bytes of the second shadow, times it dropped}. */
+int bcx_screen4_stats(bcx_solver* s, int64_t* out8);
 /* Read back rows [begin, begin + count) of the shadow: codes (count x ld8 bytes, ld8 = d rounded up to 16, returned in
  * *ld8_out; value = (code - 128) * scale), per-row scales and per-row upper bounds of ||stored row - dequantised row||_2.
  * Builds the shadow if it is due (it is built before the first enqueued iteration after bcx_finalize). */

@@ -25,12 +25,14 @@ def fetch_bytes(db, key):
     c = sqlite3.connect(db)
     # fp32 / fp16 rows: the default path streams the 8-bit shadow (csrc/screen8.hip).  The line's traffic is that of the kernel
     # that moved the most bytes in the run: screen_kernel where the tier stayed on, scan_kernel where the overflow rule
-    # dropped it (c3) -- the survivors' re-score and the rare storage-precision redo are not in it.
+    # dropped it (c3), front4_kernel where the 4-bit front pass runs in front of the tier (FW / OMP on one shard) -- the
+    # listed rows' second stage, the survivors' re-score and the rare storage-precision redo are not in it.
     if key.rsplit("_", 1)[1] in ("float32", "float16") and not key.startswith("proj_colsum_linreg_"):
         tot = lambda pat: c.execute("select coalesce(sum(counter_value), 0) from pmc_events where name like ? and counter_name = "
                                     "'FETCH_SIZE'", ("%" + pat + "%",)).fetchone()[0]
-        if tot("screen_kernel<") > tot(inst):
-            inst = "screen_kernel<"
+        for other in ("screen_kernel<", "front4_kernel<"):
+            if tot(other) > tot(inst):
+                inst = other
     # rocpd stores one row per (dispatch, counter instance): sum the instances of a dispatch first
     per = c.execute("select dispatch_id, sum(counter_value) from pmc_events where name like ? and counter_name = 'FETCH_SIZE' "
                     "group by dispatch_id", ("%" + inst + "%",)).fetchall()

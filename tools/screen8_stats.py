@@ -59,6 +59,12 @@ def main():
         "timed_screened": after["screened"] - before["screened"], "timed_survivors": after["survivors"] - before["survivors"],
         "timed_capture_overflows": after["overflows"] - before["overflows"],
         "timed_storage_redos": after["storage_redos"] - before["storage_redos"],
+        # the 4-bit front pass (csrc/screen4.hip)
+        "front4_state": after["front4_state"], "front4_device_bytes": after["front4_device_bytes"],
+        "timed_front4_iterations": after["front4_iterations"] - before["front4_iterations"],
+        "timed_front4_listed": after["front4_listed"] - before["front4_listed"],
+        "timed_front4_overflows": after["front4_overflows"] - before["front4_overflows"],
+        "timed_front4_redos": after["front4_redos"] - before["front4_redos"],
         "exact_fallbacks": st["exact_fallbacks"], "fp64_candidates": st["candidates"], "resolves": st["resolves"]}))
 
 
