@@ -37,7 +37,7 @@ static void free_all(bcx_solver* s) {
   for (size_t w = 0; w < s->peer_mbox.size(); ++w)
     if (s->peer_mbox[w] && s->peer_mbox[w] != s->mbox) (void)hipIpcCloseMemHandle(s->peer_mbox[w]);
   void* xptrs[] = {s->mbox, s->peer_tab, s->xseq, s->xprobe, s->rec_gather, s->grid_counter, s->fin_part, s->gram_work, s->warm_buf,
-                   s->Aq, s->scr_sb, s->scr_partials, s->scr_stat, s->A4, s->s4_sb, s->s4_list, s->s4_counts, s->s4_head};
+                   s->Aq, s->scr_sb, s->scr_partials, s->scr_stat, s->A4, s->s4_sb, s->s4_list, s->s4_counts, s->s4_sent};
   for (void* p : xptrs)
     if (p) (void)hipFree(p);
   for (auto& ev : s->prof_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -463,7 +463,7 @@ static int step_scan(bcx_solver* s, void* send_dev, int exact, bool with_tail) {
   return bcx_launch_resolve(s, send, exact);
 }
 
-// the scan of one enqueued iteration: the 4-bit front pass + second stage + refine (screen4.hip), the 8-bit screen + refine
+// the scan of one enqueued iteration: the 4-bit front pass with its second stage + refine (screen4.hip), the 8-bit screen + refine
 // (screen8.hip) or the storage-precision / exact scan
 static int front_scan(bcx_solver* s, int exact, bool tier, bool four) {
   int rc;
@@ -515,7 +515,7 @@ static int enqueue_many(bcx_solver* s, int64_t itrs) {
   s->scr_batch = false;
   for (int64_t i = 0; i < itrs; ++i) {
     s->scr_batch = tier;
-    // The 4-bit front pass needs sentinel rows: the partials of the tier iteration enqueued just before.  s4_warm counts the
+    // The 4-bit front pass needs sentinel rows: those the refine kernel of the tier iteration enqueued just before left.  s4_warm counts the
     // plain 8-bit iterations still due: two after finalize / reset / a reload (the second query after a fresh start is still
     // far from the first), one after a redone iteration.  Decided here, without a device round trip.
     const bool four = tier4 && s->s4_warm == 0;
@@ -672,7 +672,7 @@ extern "C" int bcx_build_poll(bcx_solver* s, int64_t* n_done, int32_t* need_exac
     unsigned long long st8[SCR_WORDS];
     BCX_HIP(hipMemcpy(st8, s->scr_stat, sizeof st8, hipMemcpyDeviceToHost));
     if (!st8[SCR_ARMED]) break;                       // the storage-precision redo itself halted
-    if (st8[SCR4_LAST] != 0 && st8[SCR4_LAST] == st8[SCR_ITERS]) {
+    if (st8[SCR4_LAST] != 0) {
       // the halted iteration went through the 4-bit front pass (a full list segment, or a capture overflow behind it): the
       // same rule on the 4-bit tier's own count drops the solver to the 8-bit tier, never straight to the storage scan
       s->s4_halts += 1;
@@ -1015,11 +1015,6 @@ extern "C" int bcx_screen4_stats(bcx_solver* s, int64_t* out8) {
   }
   const bool possible = s->s4_enabled && s->scr_enabled && s->cfg.store_dtype != BCX_F64 && s->cfg.d <= 4096 && s->cfg.n_local > 0 &&
                         s->cfg.alg != BCX_ALG_GIGA && s->cfg.world_size == 1;
-  if (st8[SCR4_PENDING] && s->s4_counts && s->s4_n_seg > 0) {   // the last 4-bit iteration: booked on the device by the next one
-    std::vector<int32_t> cnt((size_t)s->s4_n_seg);
-    BCX_HIP(hipMemcpy(cnt.data(), s->s4_counts, cnt.size() * 4, hipMemcpyDeviceToHost));
-    for (int32_t c : cnt) { st8[SCR4_LISTED] += (unsigned long long)std::min<int32_t>(c, s->s4_seg_cap); st8[SCR4_OVERFLOWS] += c > s->s4_seg_cap; }
-  }
   out8[0] = bcx_screen4_on(s) ? 1 : 0;
   out8[1] = (int64_t)st8[SCR4_ITERS];
   out8[2] = (int64_t)st8[SCR4_LISTED];

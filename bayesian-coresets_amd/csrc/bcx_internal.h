@@ -40,12 +40,10 @@ enum { SCR_ARMED = 0,       // the iteration in flight (or the one that halted) 
        SCR_REDOS = 4,       // halted tier iterations redone with the storage-precision scan
        SCR4_ITERS = 5,      // iterations that went through the 4-bit front pass (screen4.hip)
        SCR4_LISTED = 6,     // rows the front pass listed for the second stage, summed over those iterations
-       SCR4_OVERFLOWS = 7,  // list segments that were full
-       SCR4_LAST = 8,       // the value SCR_ITERS takes at the end of the last 4-bit iteration: equal to SCR_ITERS at a halt
-                            // means the halted iteration was a 4-bit one
-       SCR4_PENDING = 9,    // the last 4-bit iteration's list counts are not in words 6 and 7 yet: the next threshold
-                            // kernel books them (one workgroup, no atomics in the pass), bcx_screen4_stats adds them itself
-       SCR_WORDS = 10 };
+       SCR4_OVERFLOWS = 7,  // list segments that were full (words 5 to 8 are booked by refine_kernel, in the same iteration)
+       SCR4_LAST = 8,       // 1 when the last iteration refine_kernel saw went through the 4-bit front pass: at a halt, that the
+                            // halted iteration was a 4-bit one (the kernels of later iterations return at once)
+       SCR_WORDS = 9 };
 // 4-bit front tier: entries per wave in the list buffer (tools/screen4_model.py), sentinel rows
 #define BCX_S4_SEG_CAP 1024
 #define BCX_S4_SENTINELS 64
@@ -214,15 +212,14 @@ struct bcx_solver {
   void* s4_sb = nullptr;         // n_local x (fp32 scale4, fp32 bound4)
   void* s4_list = nullptr;       // BCX_MAX_PARTIALS segments of BCX_S4_SEG_CAP row indices
   void* s4_counts = nullptr;     // BCX_MAX_PARTIALS entries: rows a wave wanted to list
-  void* s4_head = nullptr;       // the threshold kernel's output: Front4Head + the query's three nibble planes
+  void* s4_sent = nullptr;       // BCX_S4_SENTINELS row indices (-1: none) the last refine_kernel left for the next front pass
   int ld4 = 0;
-  int s4_n_seg = 0;              // list segments (waves) of the last front pass
   int s4_seg_cap = BCX_S4_SEG_CAP;   // entries of a segment in use; dev switch BCX_SCREEN4_SEGCAP=<n> lowers it (tests of the overflow path)
   int64_t s4_cap_rows = 0;
   bool s4_enabled = true;        // off: BCX_SCREEN4=0 (dev switch)
   int s4_dropped = 0;            // 1: dropped to the 8-bit tier by the redo rule until bcx_reset, 2: no memory for the second shadow
   bool s4_valid = false;         // the 4-bit shadow matches the stored rows
-  int s4_warm = 2;               // plain 8-bit iterations still to run before scr_partials name usable sentinel rows
+  int s4_warm = 2;               // plain 8-bit iterations still to run before the last refine has left usable sentinel rows
   uint64_t s4_ovf_at[4] = {0, 0, 0, 0};   // SCR4_ITERS stamps of the last four halted 4-bit iterations (drop rule, api.hip)
   int64_t s4_halts = 0;         // since bcx_reset
   int64_t s4_redos = 0, s4_drops = 0;   // since construction (bcx_screen4_stats)
@@ -265,7 +262,7 @@ bool bcx_screen_on(const bcx_solver* s);
 int bcx_screen_build(bcx_solver* s);
 int bcx_launch_screen(bcx_solver* s);
 int bcx_launch_resume_store(bcx_solver* s);
-int bcx_launch_refine(bcx_solver* s, int n_in);
+int bcx_launch_refine(bcx_solver* s, int n_in, bool four);   // four: the partials come from the 4-bit front pass
 // screen4.hip
 bool bcx_screen4_on(const bcx_solver* s);
 int bcx_screen4_build(bcx_solver* s);

@@ -19,6 +19,8 @@
 //                     re-scored from the STORED rows with an interval no wider than the storage-precision scan's, and leave
 //                     as one partial each in the format resolve_core reads.  resolve_core, the fp64 re-score and the state
 //                     update are untouched: they see fewer, tighter partials than scan_kernel would have given them.
+//                     For the 4-bit front tier (screen4.hip) it also leaves the next front pass's 64 sentinel rows, picked
+//                     from the partials it holds anyway, and books that tier's counters from the list counts.
 //
 // The enclosure.  Exact score s* = a* . q* (a*: the exact normalised row, q*: the fp64 query); a~, q~: their stored / fp32
 // roundings; deq: the dequantised row.  With qs = |q| (DevState::qscale):
@@ -42,8 +44,8 @@
 // BCX_REC_OVERFLOW, the state machine halts as for a candidate-window overflow, and bcx_build_poll redoes that iteration with
 // the storage-precision scan (api.hip).  tools/screen8_model.py emulates this capture; DESIGN.md 4.1 has its numbers.
 //
-// The scoring and interval code (Q16, dot16, load_q16, screen_interval) lives in screen_core.h: the second stage of the 4-bit
-// front pass (screen4.hip) scores its listed rows with the same text and hands its partials to refine_kernel here.
+// The scoring and interval code (Q16, dot16, load_q16, screen_interval) lives in screen_core.h: the 4-bit front pass
+// (screen4.hip) scores its listed rows with the same text, inside its own launch, and hands its partials to refine_kernel here.
 #include <float.h>
 #include "screen_core.h"
 
@@ -175,17 +177,24 @@ struct RefineArgs {
   const float* q;
   int store_f16, ld, ldq, d, dual;
   double coef_mid;      // |fp64-accumulated stored score - exact score| <= coef_mid * qscale
+  // the 4-bit front tier (screen4.hip); sent is null when the solver has no 4-bit shadow
+  int* sent;            // out: BCX_S4_SENTINELS row indices for the next front pass, -1: none
+  const int* counts;    // the list counts the front pass of THIS iteration wrote, one per partial; null: a plain 8-bit iteration
+  int seg_cap;          // entries of a list segment in use
+  int64_t n;
 };
+
+#define BCX_REFINE_PF 8   // elements per lane of a wave's first survivor row that are loaded ahead of the sentinel selection
 
 __global__ __launch_bounds__(BCX_REFINE_THREADS) void refine_kernel(RefineArgs a) {
   if (!a.st->active) return;
   __shared__ double scratch[BCX_SCRATCH];
   __shared__ int surv[BCX_SCREEN_MAX_SURV];
-  __shared__ int nsurv, overflow;
+  __shared__ int nsurv, overflow, listed, full;
   constexpr int PP = BCX_MAX_PARTIALS / BCX_REFINE_THREADS;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, nwaves = BCX_REFINE_THREADS / 64;
   double u1[PP], u2[PP], u3[PP], lo[PP];
-  int r1[PP], r2[PP];
+  int r1[PP], r2[PP], cn[PP];
 #pragma unroll
   for (int t = 0; t < PP; ++t) {
     const int p = tid + t * BCX_REFINE_THREADS;
@@ -193,8 +202,9 @@ __global__ __launch_bounds__(BCX_REFINE_THREADS) void refine_kernel(RefineArgs a
     u1[t] = ok ? a.in.U1[p] : -INFINITY; u2[t] = ok ? a.in.U2[p] : -INFINITY;
     u3[t] = ok ? a.in.U3[p] : -INFINITY; lo[t] = ok ? a.in.L[p] : -INFINITY;
     r1[t] = ok ? a.in.i1[p] : 0; r2[t] = ok ? a.in.i2[p] : 0;
+    cn[t] = (ok && a.counts) ? a.counts[p] : 0;
   }
-  if (tid == 0) { nsurv = 0; overflow = 0; }
+  if (tid == 0) { nsurv = 0; overflow = 0; listed = 0; full = 0; }
   double lmax = -INFINITY;
 #pragma unroll
   for (int t = 0; t < PP; ++t) lmax = fmax(lmax, lo[t]);
@@ -204,6 +214,13 @@ __global__ __launch_bounds__(BCX_REFINE_THREADS) void refine_kernel(RefineArgs a
     if (u1[t] > -INFINITY && u1[t] >= Lstar) { const int s = atomicAdd(&nsurv, 1); if (s < BCX_SCREEN_MAX_SURV) surv[s] = r1[t]; }
     if (u2[t] > -INFINITY && u2[t] >= Lstar) { const int s = atomicAdd(&nsurv, 1); if (s < BCX_SCREEN_MAX_SURV) surv[s] = r2[t]; }
     if (u3[t] > -INFINITY && u3[t] >= Lstar) overflow = 1;
+  }
+  if (a.counts) {   // (kernel-uniform) rows listed and full segments of this iteration's front pass: exact in a double
+    double li = 0.0, fu = 0.0;
+#pragma unroll
+    for (int t = 0; t < PP; ++t) { li += (double)(cn[t] > a.seg_cap ? a.seg_cap : cn[t]); fu += cn[t] > a.seg_cap ? 1.0 : 0.0; }
+    li = wave_allsum(li); fu = wave_allsum(fu);
+    if (lane == 0) { atomicAdd(&listed, (int)li); atomicAdd(&full, (int)fu); }
   }
   __syncthreads();
   const int ns = nsurv;
@@ -221,6 +238,61 @@ __global__ __launch_bounds__(BCX_REFINE_THREADS) void refine_kernel(RefineArgs a
     a.stat[SCR_ARMED] = 1ull;
     atomicAdd(&a.stat[SCR_ITERS], 1ull);
     if (ovf) atomicAdd(&a.stat[SCR_OVERFLOWS], 1ull); else atomicAdd(&a.stat[SCR_SURVIVORS], (unsigned long long)ns);
+    a.stat[SCR4_LAST] = a.counts ? 1ull : 0ull;
+    if (a.counts) {
+      atomicAdd(&a.stat[SCR4_ITERS], 1ull);
+      atomicAdd(&a.stat[SCR4_LISTED], (unsigned long long)listed);
+      atomicAdd(&a.stat[SCR4_OVERFLOWS], (unsigned long long)full);
+    }
+  }
+  auto stored = [&](int64_t i, int j) -> double {
+    return a.store_f16 ? (double)__half2float(((const __half*)a.An)[i * (int64_t)a.ld + j])
+                       : (double)((const float*)a.An)[i * (int64_t)a.ld + j];
+  };
+  // the head of this wave's first survivor row (and the query beside it) is requested before the sentinel selection, which
+  // needs no memory: unconditional loads at clamped addresses, so that all of them are in flight together.  (Without a 4-bit
+  // tier there is no selection to hide, and the rows are read by the loop below as before.)
+  double pv[BCX_REFINE_PF];
+  float pq0[BCX_REFINE_PF];
+  const bool ahead = a.sent && !a.dual && !ovf && wave < ns;   // (kernel-uniform but for the wave; the path sums one query only)
+#pragma unroll
+  for (int k = 0; k < BCX_REFINE_PF; ++k) { pv[k] = 0.0; pq0[k] = 0.0f; }
+  if (ahead) {
+    const int64_t row0 = surv[wave];
+#pragma unroll
+    for (int k = 0; k < BCX_REFINE_PF; ++k) {
+      const int j = lane + 64 * k, jc = j < a.d ? j : 0;
+      pv[k] = stored(row0, jc); pq0[k] = a.q[jc];
+    }
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  // The next front pass's sentinels (screen4.hip): this wave's SPW largest upper bounds among the 2 PP x 64 candidates it holds
+  // -- 16 x 4 rows, the 4 largest of all among them.  Written on every path that leaves tier partials, overflow included.
+  if (a.sent) {
+    constexpr int SPW = BCX_S4_SENTINELS / (BCX_REFINE_THREADS / 64);
+    double cu[2 * PP];
+    int ci[2 * PP];
+#pragma unroll
+    for (int t = 0; t < 2 * PP; ++t) {
+      const double u = (t & 1) ? u2[t >> 1] : u1[t >> 1];
+      const int i = (t & 1) ? r2[t >> 1] : r1[t >> 1];
+      const bool use = u > -INFINITY && u < INFINITY && i >= 0 && (int64_t)i < a.n;   // (false for NaN)
+      cu[t] = use ? u : -INFINITY; ci[t] = use ? i : -1;
+    }
+#pragma unroll
+    for (int r = 0; r < SPW; ++r) {
+      double best = -INFINITY;
+      int bt = -1, bi = -1;
+#pragma unroll
+      for (int t = 0; t < 2 * PP; ++t) if (cu[t] > best) { best = cu[t]; bt = t; bi = ci[t]; }
+      const double wm = wave_allmax(best);
+      const unsigned long long bal = __ballot(bt >= 0 && best == wm);
+      const int src = bal ? __ffsll((long long)bal) - 1 : 0;
+      const int row = __shfl(bi, src, BCX_WAVE);
+      if (lane == 0) a.sent[wave * SPW + r] = bal ? row : -1;   // -1: no candidates left
+#pragma unroll
+      for (int t = 0; t < 2 * PP; ++t) if (bal && lane == src && t == bt) cu[t] = -INFINITY;
+    }
   }
   if (ovf) return;
   const double qs = a.st->qscale;
@@ -228,9 +300,16 @@ __global__ __launch_bounds__(BCX_REFINE_THREADS) void refine_kernel(RefineArgs a
   for (int c = wave; c < ns; c += nwaves) {
     const int64_t i = surv[c];
     double s0 = 0.0, s1 = 0.0;
-    for (int j = lane; j < a.d; j += 64) {
-      const double v = a.store_f16 ? (double)__half2float(((const __half*)a.An)[i * (int64_t)a.ld + j])
-                                   : (double)((const float*)a.An)[i * (int64_t)a.ld + j];
+    int j = lane;
+    if (ahead && c == wave) {   // (same order of the sum as the loop below)
+#pragma unroll
+      for (int k = 0; k < BCX_REFINE_PF; ++k, j += 64) {
+        const double t0 = fma(pv[k], (double)pq0[k], s0);
+        s0 = j < a.d ? t0 : s0;
+      }
+    }
+    for (; j < a.d; j += 64) {
+      const double v = stored(i, j);
       s0 = fma(v, (double)a.q[j], s0);
       if (a.dual) s1 = fma(v, (double)a.q[a.ldq + j], s1);
     }
@@ -416,13 +495,13 @@ int bcx_launch_screen(bcx_solver* s) {
   const bool dual = s->cfg.alg == BCX_ALG_GIGA;
   rc = dual ? launch_screen_t<true>(s, a, G, CH, ur, grid) : launch_screen_t<false>(s, a, G, CH, ur, grid);
   if (rc != BCX_OK) return rc;
-  s->scr_n_in = n_in;     // (these partials also name the next 4-bit iteration's sentinel rows, screen4.hip)
-  return bcx_launch_refine(s, n_in);
+  s->scr_n_in = n_in;
+  return bcx_launch_refine(s, n_in, false);
 }
 
 // The refine kernel over the n_in per-wave partials in s->scr_partials (written by screen_kernel, or by the second stage of
-// the 4-bit tier in the same format).
-int bcx_launch_refine(bcx_solver* s, int n_in) {
+// the 4-bit tier in the same format; four: the latter, whose list counts the kernel then books).
+int bcx_launch_refine(bcx_solver* s, int n_in, bool four) {
   const int d = s->cfg.d;
   const bool f16 = s->cfg.store_dtype == BCX_F16;
   const double u = 5.9604644775390625e-08;
@@ -432,6 +511,8 @@ int bcx_launch_refine(bcx_solver* s, int n_in) {
   r.st = s->st; r.stat = s->scr_stat;
   r.An = s->An; r.q = (const float*)s->qst;
   r.store_f16 = f16; r.ld = s->ld; r.ldq = s->ld; r.d = d; r.dual = s->cfg.alg == BCX_ALG_GIGA;
+  r.sent = bcx_screen4_on(s) ? (int*)s->s4_sent : nullptr;   // (dropped to the 8-bit tier: nobody reads sentinels until reset)
+  r.counts = four ? (const int*)s->s4_counts : nullptr; r.seg_cap = s->s4_seg_cap; r.n = s->cfg.n_local;
   // stored row and fp32 query multiplied and summed in fp64: what is left is their own rounding (2 u, fp16: its storage term)
   // and d 2^-53; 30 % head room as in bcx_scan_plan
   r.coef_mid = 1.3 * u * 3.0;

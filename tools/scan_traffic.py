@@ -26,7 +26,8 @@ def fetch_bytes(db, key):
     # fp32 / fp16 rows: the default path streams the 8-bit shadow (csrc/screen8.hip).  The line's traffic is that of the kernel
     # that moved the most bytes in the run: screen_kernel where the tier stayed on, scan_kernel where the overflow rule
     # dropped it (c3), front4_kernel where the 4-bit front pass runs in front of the tier (FW / OMP on one shard) -- the
-    # listed rows' second stage, the survivors' re-score and the rare storage-precision redo are not in it.
+    # listed rows' second stage is inside that launch and its bytes; the survivors' re-score and the rare storage-precision
+    # redo are not in it.
     if key.rsplit("_", 1)[1] in ("float32", "float16") and not key.startswith("proj_colsum_linreg_"):
         tot = lambda pat: c.execute("select coalesce(sum(counter_value), 0) from pmc_events where name like ? and counter_name = "
                                     "'FETCH_SIZE'", ("%" + pat + "%",)).fetchone()[0]

@@ -65,7 +65,7 @@ def pack4(codes):
 
 
 def quantise_query(q32):
-    """thresh4_kernel (a): integers x in [-1911, 1911], step = fp32(max|q| / 1911), qerr >= ||q - x step||_2 (fp32 round-up),
+    """front4_head (a): integers x in [-1911, 1911], step = fp32(max|q| / 1911), qerr >= ||q - x step||_2 (fp32 round-up),
     and the three digit planes x = 256 h2 + 16 h1 + l, every digit in [-8, 7]."""
     q = np.asarray(q32, dtype=np.float32).astype(np.float64)
     m = np.abs(q).max() if q.size else 0.0
@@ -85,7 +85,7 @@ def quantise_query(q32):
 
 
 def e4_coefficients(qscale32, qerr32, err_coef):
-    """(eA, eB) of the head thresh4_kernel writes: e4 = bound4 eA + eB + 5e-7 |score4| (derivation: head of screen4.hip)."""
+    """(eA, eB) of the head front4_head computes: e4 = bound4 eA + eB + 5e-7 |score4| (derivation: head of screen4.hip)."""
     qs, qe = float(np.float32(qscale32)), float(qerr32)
     eA = _round_up_f32((qs * 1.000002 + qe) * 1.000004)
     eB = _round_up_f32((err_coef * qs + 1.001 * qe) * 1.000004 + 1e-37)
@@ -147,8 +147,9 @@ def wave_of_row4(n, d):
 
 
 def pick_sentinels(U, rows, bins, nbins):
-    """thresh4_kernel (b) on the partials a tier iteration leaves: per segment the two largest upper bounds among `rows`
-    (candidate 2 p + k of partial p), then the 4 largest of each of 16 interleaved sixteenths of the candidates."""
+    """refine_kernel's selection on the partials a tier iteration leaves: per segment the two largest upper bounds among `rows`
+    (two candidates of partial p), then the 4 largest of each sixteenth of the candidates, partial p being held by wave
+    (p mod 1024) // 64 of the refine kernel."""
     order = rows[np.lexsort((rows, -U[rows]))]               # by U descending, row ascending
     b = bins[order]
     first = np.zeros(len(order), dtype=bool)
@@ -160,8 +161,9 @@ def pick_sentinels(U, rows, bins, nbins):
     cand_row[2 * bins[order[i1]]] = order[i1]
     cand_row[2 * bins[rest[i2]] + 1] = rest[i2]
     out = []
+    holder = (np.arange(nbins) % 1024) // 64
     for w in range(16):
-        c = cand_row[w::16]
+        c = cand_row.reshape(nbins, 2)[holder == w].ravel()
         c = c[c >= 0]
         out.extend(c[np.argsort(-U[c], kind="stable")[: SENTINELS // 16]].tolist())
     return np.array(out, dtype=np.int64)
