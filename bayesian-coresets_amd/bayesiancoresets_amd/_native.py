@@ -27,7 +27,7 @@ SYMBOLS = (
     "bcx_finalize", "bcx_build_begin", "bcx_step_scan", "bcx_step_apply", "bcx_build_enqueue", "bcx_build_poll",
     "bcx_step_scan_exact", "bcx_build_trace", "bcx_active_count", "bcx_get_weights", "bcx_error", "bcx_optimize",
     "bcx_reset", "bcx_reached_numeric_limit", "bcx_get_vector", "bcx_get_norms", "bcx_get_stored_rows", "bcx_argmax_correlation", "bcx_time_scan",
-    "bcx_stats", "bcx_screen_stats", "bcx_screen4_stats", "bcx_screen_read", "bcx_profile_scan", "bcx_profile_read", "bcx_version",
+    "bcx_stats", "bcx_screen_stats", "bcx_screen4_stats", "bcx_screen_read", "bcx_screen4_read", "bcx_screen4_probe", "bcx_profile_scan", "bcx_profile_read", "bcx_version",
     "bcx_project_write", "bcx_project_colsum", "bcx_project_select", "bcx_project_last_error",
     "bcx_build_enqueue_exact", "bcx_exchange_export", "bcx_exchange_attach", "bcx_exchange_probe", "bcx_exchange_disable", "bcx_exchange_set_timeout",
     "bcx_set_check_monotone", "bcx_project_profile", "bcx_project_profile_read", "bcx_exchange_stats", "bcx_load_rows_flags", "bcx_project_write_raw", "bcx_omp_stats", "bcx_project_select_ws", "bcx_project_select_scratch_bytes",
@@ -162,6 +162,8 @@ def load():
         "bcx_screen_stats": [vp, vp],
         "bcx_screen4_stats": [vp, vp],
         "bcx_screen_read": [vp, i64, i64, vp, vp, vp, P(i32)],
+        "bcx_screen4_read": [vp, i64, i64, vp, vp, vp, P(i32)],
+        "bcx_screen4_probe": [vp, vp, vp, P(i32), vp, vp, i32, vp],
         "bcx_profile_scan": [vp, i32],
         "bcx_profile_read": [vp, P(dbl), P(i64)],
         "bcx_build_enqueue_exact": [vp],
@@ -587,6 +589,42 @@ class Engine(object):
                                              ctypes.byref(got)))
         assert got.value == ld8
         return codes, sc, bd
+
+    def screen4_read(self, begin=0, count=None):
+        """(codes uint8 [count, ld4], scale4 fp32 [count], bound4 fp32 [count]) of the 4-bit front pass's shadow rows: two codes
+        per byte as code + 8, the element with the even index in the low nibble, padding nibbles 8."""
+        count = self.n_local - begin if count is None else count
+        ld4 = (self.d + 31) // 32 * 16
+        codes = np.empty((count, ld4), dtype=np.uint8)
+        sc = np.empty(count, dtype=np.float32)
+        bd = np.empty(count, dtype=np.float32)
+        got = ctypes.c_int32()
+        self._check(self.lib.bcx_screen4_read(self.h, begin, count, codes.ctypes.data, sc.ctypes.data, bd.ctypes.data,
+                                              ctypes.byref(got)))
+        assert got.value == ld4
+        return codes, sc, bd
+
+    SCREEN4_MAX_WAVES = 2048      # BCX_SCREEN4_MAX_WAVES of include/bcx.h
+
+    def screen4_probe(self, query, sentinels, list_stride=1024):
+        """One launch of the front pass kernel alone against `query` ([d]) and 64 sentinel rows (-1: none).  Returns a dict:
+        counts int32 [n_waves] (rows each wave wanted to list), list int32 [n_waves, list_stride] (the listed rows of a wave first,
+        -1 behind them), and the partials its second stage wrote: U1, U2, U3, L float64 [n_waves], i1, i2 int32 [n_waves]."""
+        q = np.ascontiguousarray(query, dtype=np.float64)
+        sent = np.ascontiguousarray(sentinels, dtype=np.int32)
+        assert q.shape == (self.d,) and sent.shape == (64,)
+        cap = self.SCREEN4_MAX_WAVES
+        nw = ctypes.c_int32()
+        counts = np.zeros(cap, dtype=np.int32)
+        lst = np.full((cap, list_stride), -1, dtype=np.int32)
+        raw = np.zeros(cap * 40, dtype=np.uint8)
+        self._check(self.lib.bcx_screen4_probe(self.h, q.ctypes.data, sent.ctypes.data, ctypes.byref(nw), counts.ctypes.data,
+                                               lst.ctypes.data, list_stride, raw.ctypes.data))
+        n = nw.value
+        dbl = raw[:32 * n].view(np.float64).reshape(4, n)
+        idx = raw[32 * n:40 * n].view(np.int32).reshape(2, n)
+        return {"counts": counts[:n].copy(), "list": lst[:n].copy(), "U1": dbl[0].copy(), "U2": dbl[1].copy(), "U3": dbl[2].copy(),
+                "L": dbl[3].copy(), "i1": idx[0].copy(), "i2": idx[1].copy()}
 
     def omp_stats(self):
         out = (ctypes.c_int64 * 4)()

@@ -483,7 +483,7 @@ extern "C" int bcx_step_apply(bcx_solver* s, const void* recv_dev) {
 }
 
 // one whole iteration without the host: single shard, or row shards with an attached peer mailbox
-static int enqueue_one(bcx_solver* s, int exact, bool tier, bool four = false) {
+static int enqueue_one_launch(bcx_solver* s, int exact, bool tier, bool four) {
   if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
   int rc;
   if (s->cfg.world_size != 1) {
@@ -503,6 +503,12 @@ static int enqueue_one(bcx_solver* s, int exact, bool tier, bool four = false) {
     return bcx_launch_apply(s, s->rec_local);
   }
   return bcx_launch_tail(s, exact);   // resolve + apply in one launch (single shard, GIGA/FW)
+}
+
+static int enqueue_one(bcx_solver* s, int exact, bool tier, bool four = false) {
+  const int rc = enqueue_one_launch(s, exact, tier, four);
+  if (rc == BCX_OK) s->enq_unpolled = true;   // until bcx_build_poll (or bcx_reset): bcx_screen4_probe refuses meanwhile
+  return rc;
 }
 
 // `itrs` iterations through the 8-bit tier when it is on (default), else as the parent did
@@ -694,6 +700,7 @@ extern "C" int bcx_build_poll(bcx_solver* s, int64_t* n_done, int32_t* need_exac
     else if (rest <= 0) s->scr_batch = false;
     if ((rc = read_state(s, &h))) return rc;
   }
+  s->enq_unpolled = false;
   if (h.halt == HALT_GRID_TIMEOUT) { s->err = "OMP step: grid barrier timed out"; return BCX_ERR_STATE; }
   if (h.halt == HALT_EXCHANGE_TIMEOUT) {
     // which peers' flags never arrived (recorded by the waiting lanes, csrc/resolve.hip mailbox_exchange)
@@ -806,6 +813,7 @@ extern "C" int bcx_reset(bcx_solver* s) {
   s->s4_halts = 0;
   for (int i = 0; i < 4; ++i) s->s4_ovf_at[i] = 0;
   s->s4_warm = 2;                                   // a fresh start: the first queries are far from the last ones
+  s->enq_unpolled = false;                          // (read_state above waited for whatever was enqueued)
   // error() with an empty list must give ||b|| computed the same way as after finalize
   return bcx_launch_error_refresh(s);
 }
@@ -908,18 +916,10 @@ extern "C" int bcx_time_scan(bcx_solver* s, int32_t reps, int32_t exact, double*
   return BCX_OK;
 }
 
-// One N-way correlation scan with a caller-supplied query: arg-max_n An[n] . q (first maximum) and the
-// exact fp64 score.  This is the select step of SparseVI on already projected vectors
-// (sparsevi.py:49-56: corrs = vecs.dot(resid)/||vecs||/S, argmax).  Single-query algorithms only.
-extern "C" int bcx_argmax_correlation(bcx_solver* s, const double* query_host, int64_t* idx, double* score) {
-  if (!s || !query_host || !idx || !score) return BCX_ERR_ARG;
-  if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
-  if (s->cfg.alg == BCX_ALG_GIGA) { s->err = "bcx_argmax_correlation needs a single-query solver (FW/OMP)"; return BCX_ERR_ARG; }
-  BCX_HIP(hipSetDevice(s->cfg.device));
+// A caller's query for one scan (bcx_argmax_correlation, bcx_screen4_probe): the storage-precision query of the scan, with the
+// fp64 query of the re-score when `with64`; *qn_out / *E_out are DevState's qscale / qexp for it.
+static int upload_query(bcx_solver* s, const double* query_host, bool with64, double* qn_out, int* E_out) {
   const int d = s->cfg.d;
-  DevState h;
-  int rc = read_state(s, &h);
-  if (rc != BCX_OK) return rc;
   std::vector<double> q64((size_t)s->ld64, 0.0);
   // |q| without leaving fp64's range at any scale of q: the squares are taken of q * 2^-E0, E0 the exponent of the largest
   // element; the fp32 query then holds q * 2^-E with E the exponent of |q| (apply_common.h store_query: same rule)
@@ -931,7 +931,7 @@ extern "C" int bcx_argmax_correlation(bcx_solver* s, const double* query_host, i
   for (int j = 0; j < d; ++j) { const double t = std::ldexp(query_host[j], -E0); qn += t * t; }
   qn = std::sqrt(qn);                                      // |q| * 2^-E0, in [1, 2 sqrt(d))
   int E = 0;
-  BCX_HIP(hipMemcpy(s->q64, q64.data(), (size_t)s->ld64 * 8, hipMemcpyHostToDevice));
+  if (with64) BCX_HIP(hipMemcpy(s->q64, q64.data(), (size_t)s->ld64 * 8, hipMemcpyHostToDevice));
   if (s->cfg.store_dtype == BCX_F64) {
     std::vector<double> qs((size_t)s->ld, 0.0);
     for (int j = 0; j < d; ++j) qs[j] = query_host[j];
@@ -945,6 +945,24 @@ extern "C" int bcx_argmax_correlation(bcx_solver* s, const double* query_host, i
     BCX_HIP(hipMemcpy(s->qst, qs.data(), (size_t)s->ld * 4, hipMemcpyHostToDevice));
     qn = std::ldexp(qn, -E1);
   }
+  *qn_out = qn; *E_out = E;
+  return BCX_OK;
+}
+
+// One N-way correlation scan with a caller-supplied query: arg-max_n An[n] . q (first maximum) and the
+// exact fp64 score.  This is the select step of SparseVI on already projected vectors
+// (sparsevi.py:49-56: corrs = vecs.dot(resid)/||vecs||/S, argmax).  Single-query algorithms only.
+extern "C" int bcx_argmax_correlation(bcx_solver* s, const double* query_host, int64_t* idx, double* score) {
+  if (!s || !query_host || !idx || !score) return BCX_ERR_ARG;
+  if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
+  if (s->cfg.alg == BCX_ALG_GIGA) { s->err = "bcx_argmax_correlation needs a single-query solver (FW/OMP)"; return BCX_ERR_ARG; }
+  BCX_HIP(hipSetDevice(s->cfg.device));
+  DevState h;
+  int rc = read_state(s, &h);
+  if (rc != BCX_OK) return rc;
+  double qn = 0.0;
+  int E = 0;
+  if ((rc = upload_query(s, query_host, true, &qn, &E))) return rc;
   DevState forced = h;
   forced.active = 1; forced.exact_mode = 0; forced.qscale = qn; forced.qexp = E;
   double rec[BCX_REC_HDR];
@@ -1045,6 +1063,94 @@ extern "C" int bcx_screen_read(bcx_solver* s, int64_t begin, int64_t count, void
     if (scales) scales[i] = sb[2 * i];
     if (bounds) bounds[i] = sb[2 * i + 1];
   }
+  return BCX_OK;
+}
+
+// Both shadows, built if they are due; BCX_ERR_STATE where the 4-bit front pass does not apply (GIGA, fp64 storage, row shards,
+// switched off, no memory).
+static int screen4_ready(bcx_solver* s, const char* who) {
+  if (!s->finalized) { s->err = "solver not finalized"; return BCX_ERR_STATE; }
+  BCX_HIP(hipSetDevice(s->cfg.device));
+  int rc = bcx_screen_build(s);
+  if (rc != BCX_OK) return rc;
+  if (bcx_screen_on(s) && s->scr_valid && (rc = bcx_screen4_build(s))) return rc;
+  if (!bcx_screen_on(s) || !s->scr_valid || !bcx_screen4_on(s) || !s->s4_valid) {
+    s->err = std::string(who) + ": the 4-bit front pass is not in use";
+    return BCX_ERR_STATE;
+  }
+  return BCX_OK;
+}
+
+// The twin of bcx_screen_read for the 4-bit shadow: codes (count x ld4 bytes, ld4 = ceil(d / 32) * 16; returned in *ld4_out),
+// scale4 and bound4 (count floats each).
+extern "C" int bcx_screen4_read(bcx_solver* s, int64_t begin, int64_t count, void* codes, float* scales, float* bounds, int32_t* ld4_out) {
+  if (!s || begin < 0 || count < 0 || begin + count > s->cfg.n_local) return BCX_ERR_ARG;
+  int rc = screen4_ready(s, "bcx_screen4_read");
+  if (rc != BCX_OK) return rc;
+  BCX_HIP(hipStreamSynchronize(s->stream));
+  if (ld4_out) *ld4_out = s->ld4;
+  if (count == 0) return BCX_OK;
+  if (codes) BCX_HIP(hipMemcpy(codes, (const char*)s->A4 + (size_t)begin * s->ld4, (size_t)count * s->ld4, hipMemcpyDeviceToHost));
+  std::vector<float> sb((size_t)count * 2);
+  BCX_HIP(hipMemcpy(sb.data(), (const char*)s->s4_sb + (size_t)begin * 8, (size_t)count * 8, hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < count; ++i) {
+    if (scales) scales[i] = sb[2 * i];
+    if (bounds) bounds[i] = sb[2 * i + 1];
+  }
+  return BCX_OK;
+}
+
+// One launch of front4_kernel, and only that, against a caller's query and a caller's sentinel rows (no refine, no resolve, no
+// tail, no counters): what it listed and what its second stage settled.  The query and DevState (active, qscale, qexp) are set
+// as bcx_argmax_correlation sets them; afterwards DevState, the query and the sentinel rows are what they were.
+extern "C" int bcx_screen4_probe(bcx_solver* s, const double* query_host, const int32_t* sentinels, int32_t* n_waves_out,
+                                 int32_t* counts, int32_t* list, int32_t list_stride, void* partials) {
+  if (!s || !query_host || !sentinels || !n_waves_out || list_stride < 0) return BCX_ERR_ARG;
+  for (int i = 0; i < BCX_S4_SENTINELS; ++i)       // every index the kernel is handed is checked here
+    if (!(sentinels[i] == -1 || (sentinels[i] >= 0 && (int64_t)sentinels[i] < s->cfg.n_local))) {
+      s->err = "bcx_screen4_probe: sentinel " + std::to_string(i) + " is neither -1 nor a local row";
+      return BCX_ERR_ARG;
+    }
+  if (s->enq_unpolled) { s->err = "bcx_screen4_probe: iterations are enqueued; call bcx_build_poll first"; return BCX_ERR_STATE; }
+  int rc = screen4_ready(s, "bcx_screen4_probe");
+  if (rc != BCX_OK) return rc;
+  DevState h;
+  if ((rc = read_state(s, &h))) return rc;
+  BCX_HIP(hipStreamSynchronize(s->stream));
+  int32_t sent_was[BCX_S4_SENTINELS];
+  std::vector<char> q_was((size_t)s->ld * 4);
+  BCX_HIP(hipMemcpy(sent_was, s->s4_sent, sizeof sent_was, hipMemcpyDeviceToHost));
+  BCX_HIP(hipMemcpy(q_was.data(), s->qst, q_was.size(), hipMemcpyDeviceToHost));
+  double qn = 0.0;
+  int E = 0;
+  if ((rc = upload_query(s, query_host, false, &qn, &E))) return rc;
+  DevState forced = h;
+  forced.active = 1; forced.exact_mode = 0; forced.qscale = qn; forced.qexp = E;
+  BCX_HIP(hipMemcpy(s->st, &forced, sizeof forced, hipMemcpyHostToDevice));
+  BCX_HIP(hipMemcpy(s->s4_sent, sentinels, sizeof sent_was, hipMemcpyHostToDevice));
+  int nw = 0;
+  rc = bcx_launch_front4_probe(s, &nw);
+  hipError_t e = hipStreamSynchronize(s->stream);
+  // (put everything back whatever the launch said)
+  BCX_HIP(hipMemcpy(s->st, &h, sizeof h, hipMemcpyHostToDevice));
+  BCX_HIP(hipMemcpy(s->s4_sent, sent_was, sizeof sent_was, hipMemcpyHostToDevice));
+  BCX_HIP(hipMemcpy(s->qst, q_was.data(), q_was.size(), hipMemcpyHostToDevice));
+  if (rc != BCX_OK) return rc;
+  BCX_HIP(e);
+  *n_waves_out = nw;
+  std::vector<int32_t> cnt((size_t)nw);
+  BCX_HIP(hipMemcpy(cnt.data(), s->s4_counts, (size_t)nw * 4, hipMemcpyDeviceToHost));
+  if (counts) memcpy(counts, cnt.data(), (size_t)nw * 4);
+  if (list && list_stride > 0) {
+    std::vector<int32_t> all((size_t)nw * BCX_S4_SEG_CAP);
+    BCX_HIP(hipMemcpy(all.data(), s->s4_list, all.size() * 4, hipMemcpyDeviceToHost));
+    for (int b = 0; b < nw; ++b) {
+      int m = cnt[b] < s->s4_seg_cap ? cnt[b] : s->s4_seg_cap;
+      if (m > list_stride) m = list_stride;
+      if (m > 0) memcpy(list + (size_t)b * list_stride, all.data() + (size_t)b * BCX_S4_SEG_CAP, (size_t)m * 4);
+    }
+  }
+  if (partials) BCX_HIP(hipMemcpy(partials, s->scr_partials, (size_t)nw * BCX_PARTIAL_BYTES, hipMemcpyDeviceToHost));
   return BCX_OK;
 }
 

@@ -223,6 +223,7 @@ struct bcx_solver {
   uint64_t s4_ovf_at[4] = {0, 0, 0, 0};   // SCR4_ITERS stamps of the last four halted 4-bit iterations (drop rule, api.hip)
   int64_t s4_halts = 0;         // since bcx_reset
   int64_t s4_redos = 0, s4_drops = 0;   // since construction (bcx_screen4_stats)
+  bool enq_unpolled = false;     // iterations were enqueued and bcx_build_poll has not been called since (bcx_screen4_probe refuses)
   // measurement
   bool profile = false;
   bool prof_now = false;
@@ -267,6 +268,7 @@ int bcx_launch_refine(bcx_solver* s, int n_in, bool four);   // four: the partia
 bool bcx_screen4_on(const bcx_solver* s);
 int bcx_screen4_build(bcx_solver* s);
 int bcx_launch_screen4(bcx_solver* s);
+int bcx_launch_front4_probe(bcx_solver* s, int* n_waves);   // front4_kernel alone, the plan of bcx_launch_screen4 (bcx_screen4_probe)
 // proj.hip: sets the message bcx_project_last_error() returns (the entry points outside the solver report through it)
 void bcx_project_set_error(const std::string& msg);
 // proj.hip: the likelihood tables of proj_math.h (PJT_DOUBLES doubles) in the current device's memory; nullptr: no memory

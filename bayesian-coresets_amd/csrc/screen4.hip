@@ -486,10 +486,11 @@ static int launch_front4(bcx_solver* s, const Front4Args& a, int G, int CH, int 
   return BCX_ERR_ARG;
 }
 
-// One 4-bit iteration's front: the front pass (which computes its own threshold and settles its list), then refine.  Afterwards s->partials /
-// s->n_partials are what bcx_launch_screen leaves.  The caller (api.hip) has made sure that the refine kernel of the tier
-// iteration enqueued just before has left sentinel rows.
-int bcx_launch_screen4(bcx_solver* s) {
+// The launch plan of one front pass: the kernel's arguments, the pair of lane geometries and the grid.  One text for the
+// iteration (bcx_launch_screen4) and for the diagnostic probe (bcx_launch_front4_probe).
+struct Front4Plan { Front4Args f; int G, CH, G8, CH8, grid, n_in; };
+
+static int front4_plan(bcx_solver* s, Front4Plan* p) {
   const int d = s->cfg.d;
   const int64_t n = s->cfg.n_local;
   const int nw4 = s->ld4 / 4;
@@ -502,7 +503,7 @@ int bcx_launch_screen4(bcx_solver* s) {
   const int G8 = screen_group(ldv8), CH8 = screen_chunks(ldv8, G8);
   const float kacc = screen_kacc(G8, CH8, d);
 
-  Front4Args f;
+  Front4Args& f = p->f;
   f.A4 = (const uint4*)s->A4; f.sb = (const float2*)s->s4_sb; f.q = (const float*)s->qst; f.sent = (const int*)s->s4_sent;
   f.Aq = (const unsigned char*)s->Aq; f.sb8 = (const float2*)s->scr_sb; f.st = s->st;
   f.list = (int*)s->s4_list; f.counts = (int*)s->s4_counts;
@@ -521,8 +522,31 @@ int bcx_launch_screen4(bcx_solver* s) {
 
   const int n_in = grid * BCX_SCREEN_WAVES;
   f.out = partial_view(s->scr_partials, n_in); f.ldv8 = ldv8;
-  if ((rc = launch_front4(s, f, G, CH, G8, CH8, grid))) return rc;
+  p->G = G; p->CH = CH; p->G8 = G8; p->CH8 = CH8; p->grid = grid; p->n_in = n_in;
+  return BCX_OK;
+}
+
+// One 4-bit iteration's front: the front pass (which computes its own threshold and settles its list), then refine.  Afterwards s->partials /
+// s->n_partials are what bcx_launch_screen leaves.  The caller (api.hip) has made sure that the refine kernel of the tier
+// iteration enqueued just before has left sentinel rows.
+int bcx_launch_screen4(bcx_solver* s) {
+  Front4Plan p;
+  int rc = front4_plan(s, &p);
+  if (rc != BCX_OK) return rc;
+  if ((rc = launch_front4(s, p.f, p.G, p.CH, p.G8, p.CH8, p.grid))) return rc;
   BCX_HIP(hipGetLastError());
-  s->scr_n_in = n_in;
-  return bcx_launch_refine(s, n_in, true);
+  s->scr_n_in = p.n_in;
+  return bcx_launch_refine(s, p.n_in, true);
+}
+
+// One launch of front4_kernel and nothing else (bcx_screen4_probe, api.hip): the same plan, no refine, no counters.  The
+// caller has set the query, the state and the sentinels; *n_waves is the number of list segments / partials it wrote.
+int bcx_launch_front4_probe(bcx_solver* s, int* n_waves) {
+  Front4Plan p;
+  int rc = front4_plan(s, &p);
+  if (rc != BCX_OK) return rc;
+  if ((rc = launch_front4(s, p.f, p.G, p.CH, p.G8, p.CH8, p.grid))) return rc;
+  BCX_HIP(hipGetLastError());
+  *n_waves = p.n_in;
+  return BCX_OK;
 }

@@ -218,6 +218,25 @@ int bcx_screen4_stats(bcx_solver* s, int64_t* out8);
  * *ld8_out; value = (code - 128) * scale), per-row scales and per-row upper bounds of ||stored row - dequantised row||_2.
  * Builds the shadow if it is due (it is built before the first enqueued iteration after bcx_finalize). */
 int bcx_screen_read(bcx_solver* s, int64_t begin, int64_t count, void* codes, float* scales, float* bounds, int32_t* ld8_out);
+/* Diagnostics of the 4-bit front pass (tests hold the kernel to exact arithmetic with them; no solver path calls them).
+ * Both build the two shadows if they are due and return BCX_ERR_STATE where the front pass does not apply (GIGA, fp64
+ * storage, row shards, switched off, no device memory for the second shadow).
+ * The read is the twin of the one above for the second shadow: codes (count x ld4 bytes, ld4 = ceil(d / 32) * 16, returned
+ * in *ld4_out; element 8 w + k of a row in bits 4k..4k+3 of its dword w as code + 8, code in [-7, 7], padding nibbles 8;
+ * value = code * scale4), per-row scale4 and per-row upper bounds bound4 of ||stored row - dequantised row||_2. */
+int bcx_screen4_read(bcx_solver* s, int64_t begin, int64_t count, void* codes, float* scales, float* bounds, int32_t* ld4_out);
+/* The probe runs ONE launch of the front pass kernel, and only that, with the launch plan of an iteration, against the
+ * caller's query (d doubles, scaled and stored as by the argmax entry above) and the caller's 64 sentinel rows (each -1 = none
+ * or a local row index; anything else: BCX_ERR_ARG, nothing is launched).  After synchronising it returns the number of waves
+ * (= list segments = partials, at most BCX_SCREEN4_MAX_WAVES) in *n_waves_out, the rows every wave wanted to list in
+ * counts[w], the first min(counts[w], segment capacity, list_stride) listed rows of wave w at list + w * list_stride, and in
+ * `partials` what the second stage settled, as n_waves doubles each of U1, U2, U3, L followed by n_waves int32 each of i1, i2
+ * (40 bytes per wave).  counts, list and partials may be NULL; otherwise they hold BCX_SCREEN4_MAX_WAVES waves.  The solver's
+ * state, its query and its sentinel rows are restored: a build after a probe gives what it gives without one.
+ * BCX_ERR_STATE when iterations are enqueued and bcx_build_poll has not been called since. */
+#define BCX_SCREEN4_MAX_WAVES 2048
+int bcx_screen4_probe(bcx_solver* s, const double* query_host, const int32_t* sentinels, int32_t* n_waves_out,
+                      int32_t* counts, int32_t* list, int32_t list_stride, void* partials);
 /* Sum of scan-kernel time recorded by hipEvents during bcx_build_enqueue: on = 1 times every scan launch,
  * on = N > 1 every N-th one (an event pair costs several microseconds of stream time), on = 0 stops. */
 /* OMP step diagnostics since construction: out4 = {steps taken, columns that left the passive set, from-scratch re-solves
