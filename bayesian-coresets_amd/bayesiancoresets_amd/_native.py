@@ -54,6 +54,7 @@ SYMBOLS = (
     "bcx_nuts_stream", "bcx_nuts_stream_scratch_bytes",
     "bcx_log_predictive", "bcx_log_predictive_scratch_bytes",
     "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
+    "bcx_quasi_newton_step", "bcx_quasi_newton_scratch_bytes",
 )
 
 
@@ -256,6 +257,9 @@ def load():
     sigs["bcx_sparsevi_adam_step_ws"] = [vp, i32, i32, vp, dbl, vp, i64, vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, i32, vp, i64]
     lib.bcx_linreg_posterior_factor_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_linreg_posterior_factor_scratch_bytes.argtypes = [i32]
+    sigs["bcx_quasi_newton_step"] = [vp, i32, i32, vp, dbl, vp, i64, i32, vp, vp, i32, dbl, vp, vp, vp, vp, i64]
+    lib.bcx_quasi_newton_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_quasi_newton_scratch_bytes.argtypes = [i32, i32]
     lib.bcx_sparsevi_adam_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_sparsevi_adam_scratch_bytes.argtypes = [i32, i32]
     lib.bcx_gram_scratch_bytes.restype = ctypes.c_int64

@@ -5,6 +5,7 @@ from . import hilbert as _hilbert
 from . import sampling as _sampling
 from . import sparsevi as _sparsevi
 from . import bpsvi as _bpsvi
+from . import quasinewton as _quasinewton
 from . import sharded_hilbert as _sharded
 
 Coreset = _base.Coreset
@@ -12,7 +13,8 @@ HilbertCoreset = _hilbert.HilbertCoreset
 UniformSamplingCoreset = _sampling.UniformSamplingCoreset
 SparseVICoreset = _sparsevi.SparseVICoreset
 BatchPSVICoreset = _bpsvi.BatchPSVICoreset
+QuasiNewtonCoreset = _quasinewton.QuasiNewtonCoreset
 ShardedHilbertCoreset = _sharded.ShardedHilbertCoreset
 
 
-__all__ = ["Coreset", "HilbertCoreset", "UniformSamplingCoreset", "SparseVICoreset", "BatchPSVICoreset", "ShardedHilbertCoreset"]
+__all__ = ["Coreset", "HilbertCoreset", "UniformSamplingCoreset", "SparseVICoreset", "BatchPSVICoreset", "QuasiNewtonCoreset", "ShardedHilbertCoreset"]

@@ -363,15 +363,22 @@ static void gram_plan(int k, int d, int* nblk, int* nslices, int64_t* len_per_sl
 }
 int64_t bcx_gram_sk_scratch_bytes(int k, int d);      // gram.hip: the chip-balanced kernel (16-byte aligned rows, k >= 192)
 int bcx_gram_sk(hipStream_t st, const double* rows, int k, int d, int64_t ld, double* G, int64_t ldg, double* work);
-int64_t bcx_gram_rows_scratch_bytes(int k, int d) {
+// The tiled kernel alone: whole blocks per workgroup, slices added in slice order by a second launch -- no workgroup waits for
+// another one's stores, so a caller that may not wait inside a launch (csrc/qn.hip) asks for this path by name.
+int64_t bcx_gram_tiled_scratch_bytes(int k, int d) {
   int nblk, nslices, ps; int64_t lps;
   gram_plan(k, d, &nblk, &nslices, &lps, &ps);
-  const int64_t tiled = nslices == 1 ? 8 : (int64_t)nslices * (nblk * (nblk + 1) / 2) * MOM_BLK * MOM_BLK * (int64_t)sizeof(double);
-  return std::max<int64_t>(tiled, bcx_gram_sk_scratch_bytes(k, d));     // (which kernel runs depends on the rows' alignment)
+  return nslices == 1 ? 8 : (int64_t)nslices * (nblk * (nblk + 1) / 2) * MOM_BLK * MOM_BLK * (int64_t)sizeof(double);
+}
+int64_t bcx_gram_rows_scratch_bytes(int k, int d) {
+  return std::max<int64_t>(bcx_gram_tiled_scratch_bytes(k, d), bcx_gram_sk_scratch_bytes(k, d));     // (which kernel runs depends on the rows' alignment)
 }
 int bcx_gram_rows(hipStream_t st, const double* rows, int k, int d, int64_t ld, double* G, int64_t ldg, double* work) {
   const int sk = bcx_gram_sk(st, rows, k, d, ld, G, ldg, work);
   if (sk <= 0) return sk;
+  return bcx_gram_rows_tiled(st, rows, k, d, ld, G, ldg, work);
+}
+int bcx_gram_rows_tiled(hipStream_t st, const double* rows, int k, int d, int64_t ld, double* G, int64_t ldg, double* work) {
   int nblk, nslices, ps; int64_t lps;
   gram_plan(k, d, &nblk, &nslices, &lps, &ps);
   const int npairs = nblk * (nblk + 1) / 2;

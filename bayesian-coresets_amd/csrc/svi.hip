@@ -29,6 +29,7 @@
 #include "bcx_internal.h"
 #include "dev_util.h"
 #include "launch_host.h"
+#include "slab_rows.h"
 
 typedef double sv4d __attribute__((ext_vector_type(4)));
 
@@ -490,15 +491,7 @@ __global__ __launch_bounds__(256) void svi_adam_a_kernel(SvbArgs a) {
   // row means: the four rows of a wave are requested together
   {
     double t[SVB_ROWS / 4];
-#pragma unroll
-    for (int u = 0; u < SVB_ROWS / 4; ++u) {
-      const int q = wave + 4 * u;
-      t[u] = 0.0;
-      if (a.raw_core && q < nj) {
-        const double* row = a.core + (size_t)(j0 + q) * a.ldc;
-        for (int s = lane; s < a.S; s += 64) t[u] += row[s];
-      }
-    }
+    slab_row_sums<SVB_ROWS>(a.core, a.ldc, j0, nj, a.S, a.raw_core != 0, t);
 #pragma unroll
     for (int u = 0; u < SVB_ROWS / 4; ++u) {
       const int q = wave + 4 * u;
@@ -522,26 +515,8 @@ __global__ __launch_bounds__(256) void svi_adam_b_kernel(SvbArgs a) {
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int j0 = blockIdx.x * SVB_ROWS, nj = min(SVB_ROWS, a.k - j0);
   const int nslab = (a.k + SVB_ROWS - 1) / SVB_ROWS;
-  for (int s = tid; s < a.S; s += 256) {
-    double t = 0.0;
-    int b = 0;
-    for (; b + 32 <= nslab; b += 32) {              // (thirty-two shares in flight -- 300 weights: ONE round trip; added in slab order)
-      double v[32];
-#pragma unroll
-      for (int q = 0; q < 32; ++q) v[q] = a.part[(size_t)(b + q) * a.S + s];
-#pragma unroll
-      for (int q = 0; q < 32; ++q) t += v[q];
-    }
-    for (; b + 8 <= nslab; b += 8) {
-      double v[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) v[q] = a.part[(size_t)(b + q) * a.S + s];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) t += v[q];
-    }
-    for (; b < nslab; ++b) t += a.part[(size_t)b * a.S + s];
-    resid[s] = a.scaling * a.colsum[s] - t;         // sparsevi.py:72
-  }
+  for (int s = tid; s < a.S; s += 256)
+    resid[s] = a.scaling * a.colsum[s] - slab_share_sum(a.part, nslab, a.S, s);      // sparsevi.py:72 (shares added in slab order)
   __syncthreads();
   double g[SVB_ROWS / 4];
 #pragma unroll

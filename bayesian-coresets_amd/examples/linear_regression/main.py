@@ -79,6 +79,9 @@ def run(a):
     build = {
         "SVI": lambda: bc.SparseVICoreset(Z, dev(sampler_w), opt_itrs=a.opt_itrs, step_sched=eval(a.step_sched)),
         "SVI-EXACT": lambda: bc.SparseVICoreset(Z, exact(), opt_itrs=a.opt_itrs, step_sched=eval(a.step_sched)),
+        # (the quasi-Newton coreset: M uniformly drawn points, opt_itrs Newton steps on all weights; every size is built afresh)
+        "QNC": lambda: bc.QuasiNewtonCoreset(Z, dev(sampler_w), opt_itrs=a.opt_itrs, step_sched=eval(a.step_sched),
+                                             tau=getattr(a, "qn_tau", 1e-2)),
         "GIGA-OPT": lambda: bc.HilbertCoreset(Z, dev(fixed(mup, Up))),
         "GIGA-OPT-EXACT": lambda: bc.HilbertCoreset(Z, exact(Z)),
         "GIGA-REAL": lambda: bc.HilbertCoreset(Z, dev(fixed(muh, Uh))),
@@ -91,7 +94,11 @@ def run(a):
     for m in range(Ms.shape[0]):
         print("M = %d: coreset construction, %s %d" % (Ms[m], a.alg, a.trial))
         c0, t0 = time.process_time(), time.perf_counter()
-        alg.build(int(Ms[m] if m == 0 else Ms[m] - Ms[m - 1]))
+        if a.alg == "QNC":
+            alg.reset()
+            alg.build(int(Ms[m]))
+        else:
+            alg.build(int(Ms[m] if m == 0 else Ms[m] - Ms[m - 1]))
         cputs[m] = time.process_time() - c0 + (cputs[m - 1] if m else 0.0)
         walls[m] = time.perf_counter() - t0 + (walls[m - 1] if m else 0.0)
         wts, pts, idcs = alg.get()
@@ -118,7 +125,7 @@ def parser():
     rp = sub.add_parser("run", help="Runs the main computational code")
     rp.set_defaults(func=run)
     ap.add_argument("--data_num", type=int, default=10000)
-    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "SVI-EXACT", "GIGA-OPT", "GIGA-OPT-EXACT", "GIGA-REAL", "GIGA-REAL-EXACT", "US"])
+    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "SVI-EXACT", "GIGA-OPT", "GIGA-OPT-EXACT", "GIGA-REAL", "GIGA-REAL-EXACT", "US", "QNC"])
     ap.add_argument("--proj_dim", type=int, default=100)
     ap.add_argument("--coreset_size_max", type=int, default=300)
     ap.add_argument("--coreset_num_sizes", type=int, default=6)
@@ -126,6 +133,8 @@ def parser():
     ap.add_argument("--n_bases_per_scale", type=int, default=50)
     ap.add_argument("--opt_itrs", type=int, default=100)
     ap.add_argument("--step_sched", type=str, default="lambda i : 1./(1+i)")
+    ap.add_argument("--qn_tau", type=float, default=argparse.SUPPRESS,                      # (absent = 1e-2: result files keep their argument set)
+                    help="QNC: the regularisation tau of (G + tau I) d = b")
     ap.add_argument("--host-sampler", action="store_true")
     ap.add_argument("--trial", type=int, default=1)
     ap.add_argument("--results_folder", type=str, default="results/")

@@ -177,6 +177,9 @@ def run(a):
         # (--subsample_select / --subsample_opt: the drawn rows are projected where the data is resident, never gathered on the host)
         "SVI": lambda: bc.SparseVICoreset(Z, dev(sampler_w), n_subsample_select=a.subsample_select, n_subsample_opt=a.subsample_opt,
                                           opt_itrs=a.opt_itrs, step_sched=eval(a.step_sched), subsample="device"),
+        # (the quasi-Newton coreset: M uniformly drawn points, opt_itrs Newton steps on all weights; every size is built afresh)
+        "QNC": lambda: bc.QuasiNewtonCoreset(Z, dev(sampler_w), n_subsample_opt=a.subsample_opt, opt_itrs=a.opt_itrs,
+                                             step_sched=eval(a.step_sched), tau=getattr(a, "qn_tau", 1e-2), subsample="device"),
         "GIGA-OPT": lambda: bc.HilbertCoreset(Z, dev(gauss(mup, Sigp))),
         "GIGA-REAL": lambda: bc.HilbertCoreset(Z, dev(gauss(muh, Sigh))),
         "US": lambda: bc.UniformSamplingCoreset(Z),
@@ -213,7 +216,11 @@ def run(a):
     for m in range(n):
         print("M = %d: coreset construction, %s %s %d" % (Ms[m], a.alg, a.dataset, a.trial))
         c0, t0 = time.process_time(), time.perf_counter()
-        alg.build(int(Ms[m] if m == 0 else Ms[m] - Ms[m - 1]))
+        if a.alg == "QNC":
+            alg.reset()
+            alg.build(int(Ms[m]))
+        else:
+            alg.build(int(Ms[m] if m == 0 else Ms[m] - Ms[m - 1]))
         cputs[m] = time.process_time() - c0 + (cputs[m - 1] if m else 0.0)
         walls[m] = time.perf_counter() - t0 + (walls[m - 1] if m else 0.0)
         wts, pts, idcs = alg.get()
@@ -250,7 +257,7 @@ def parser():
     ap.add_argument("--dataset", type=str, default="synth_lr")
     ap.add_argument("--data_num", type=int, default=10000)
     ap.add_argument("--data_dim", type=int, default=3)
-    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "GIGA-OPT", "GIGA-REAL", "US"])
+    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "GIGA-OPT", "GIGA-REAL", "US", "QNC"])
     ap.add_argument("--mcmc_samples_full", type=int, default=10000, help="--eval mcmc: draws from the full-data posterior")
     ap.add_argument("--mcmc_samples_coreset", type=int, default=10000, help="--eval mcmc: draws from every coreset's posterior")
     ap.add_argument("--eval", type=str, choices=["laplace", "mcmc"], default="laplace",
@@ -277,6 +284,8 @@ def parser():
     ap.add_argument("--coreset_size_spacing", type=str, choices=["log", "linear"], default="log")
     ap.add_argument("--opt_itrs", type=int, default=100)
     ap.add_argument("--step_sched", type=str, default="lambda i : 1./(1+i)")
+    ap.add_argument("--qn_tau", type=float, default=argparse.SUPPRESS,                       # (absent = 1e-2: result files keep their argument set)
+                    help="QNC: the regularisation tau of (G + tau I) d = b")
     ap.add_argument("--subsample_select", type=int, default=None, help="SVI: rows drawn for every selection step (default: all)")
     ap.add_argument("--subsample_opt", type=int, default=None, help="SVI: rows drawn for every ADAM step (default: all)")
     ap.add_argument("--trial", type=int, default=1)

@@ -392,6 +392,29 @@ int bcx_sparsevi_adam_step_ws(void* stream, int32_t k, int32_t S, const void* co
                               int64_t ldc, void* w_dev, void* mom1_dev, void* mom2_dev, const void* sched_dev, int32_t step,
                               double b1, double b2, double eps, void* trace_dev, int32_t core_is_raw, void* work_dev,
                               int64_t work_bytes);
+/* One step of the quasi-Newton coreset (Naik, Rousseau and Campbell, 2022) on k device-resident weights (csrc/qn.hip).  With
+ * V (k x S) the rows of core_dev centred over the S draws (core_is_raw != 0: the row means of projector.py:21 are taken here,
+ * into a centred copy in scratch; 0: the rows arrive centred) and c = scaling x colsum_dev (S):
+ *     resid = c - V^T w                                  (sparsevi.py:47 / :72)
+ *     b     = V resid / S                                (minus SparseVI's gradient, sparsevi.py:74)
+ *     G     = V V^T / S
+ *     d     : (G + tau I) d = b                          (tau >= 0, absolute, in squared log-likelihood units)
+ *     w     <- max(w + gamma d, 0)                       (NumPy's maximum: a NaN stays a NaN),  gamma = sched_dev[step]
+ * The system is solved multiplied through by S, (V V^T + S tau I) d = V resid: V V^T on the fp64 matrix cores (the tiled
+ * Gram kernel), a Cholesky factorisation -- one workgroup with the matrix in LDS up to 128 weights, beyond it panels of 32
+ * columns ordered by launch boundaries (diagonal tile in one wave, panel solve, trailing update on the matrix cores) -- and
+ * the two triangular solves.  No grid barrier, no wait between workgroups, no floating-point atomics, every sum in a fixed
+ * order: the same inputs on the same device give the same bits.  1 <= k <= 4096, 1 <= S <= 8192, ldc >= S.
+ * sched_dev: one double per step (gamma_i, evaluated by the host); dir_dev: NULL or k doubles receiving d; trace_dev: NULL or
+ * steps x k doubles, row `step` receiving the weights after this step; status_dev: one int32 the caller zeroes when a loop of
+ * steps starts and reads once after it -- a step raises it to 1 (max: it is never cleared here) when a pivot is not positive
+ * or NaN, and while it is non-zero, in that step and every later one, w_dev and dir_dev are left untouched.  work_dev:
+ * bcx_quasi_newton_scratch_bytes(k, S) bytes (-1: k or S out of range), 16-byte aligned, owned by the call until it has
+ * completed.  Asynchronous on `stream`; errors: bcx_project_last_error(). */
+int64_t bcx_quasi_newton_scratch_bytes(int32_t k, int32_t S);
+int bcx_quasi_newton_step(void* stream, int32_t k, int32_t S, const void* colsum_dev, double scaling, const void* core_dev,
+                          int64_t ldc, int32_t core_is_raw, void* w_dev, const void* sched_dev, int32_t step, double tau,
+                          void* dir_dev, void* trace_dev, void* status_dev, void* work_dev, int64_t work_bytes);
 /* The weighted conjugate posterior of Gaussian linear regression for ANY number of weighted points, in the reference's own
  * arithmetic (examples/common/model_linreg.py:26-41 weighted_post returns mup, USigp, LSigpInv; the sampler of
  * examples/linear_regression/main.py:141-147 draws muw + randn . USigw^T):
