@@ -7,7 +7,7 @@
 Namespace mirrors bayesiancoresets/__init__.py:1-2.  ``BatchPSVICoreset`` (the batch pseudocoreset)
 runs with a ``DeviceProjector`` only: its pseudo-point gradients are device kernels (csrc/psvi.hip), and any other
 projector raises NotImplementedError."""
-from .coreset import Coreset, HilbertCoreset, UniformSamplingCoreset, SparseVICoreset, BatchPSVICoreset, QuasiNewtonCoreset, ShardedHilbertCoreset
+from .coreset import Coreset, HilbertCoreset, UniformSamplingCoreset, SparseVICoreset, BatchPSVICoreset, QuasiNewtonCoreset, CoresetMCMC, ShardedHilbertCoreset
 from .projector import BlackBoxProjector, Projector, DeviceProjector
 from .linreg_sampler import LinregPosteriorSampler
 from .laplace_sampler import LaplacePosteriorSampler

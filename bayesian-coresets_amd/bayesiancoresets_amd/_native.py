@@ -55,6 +55,7 @@ SYMBOLS = (
     "bcx_log_predictive", "bcx_log_predictive_scratch_bytes",
     "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
     "bcx_quasi_newton_step", "bcx_quasi_newton_scratch_bytes",
+    "bcx_cmc_advance", "bcx_cmc_advance_ok", "bcx_cmc_advance_lds_bytes", "bcx_cmc_state_bytes",
 )
 
 
@@ -231,6 +232,13 @@ def load():
     sigs["bcx_hmc_coreset_ok"] = [i32, i32]
     lib.bcx_hmc_coreset_lds_bytes.restype = ctypes.c_int64
     lib.bcx_hmc_coreset_lds_bytes.argtypes = [i32, i32]
+    sigs["bcx_cmc_advance"] = [vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, dbl, i32, i32, i32, vp, vp, vp, i64, i64, vp, i64,
+                               vp, i64, vp, i32, vp, vp, vp, vp, vp]
+    sigs["bcx_cmc_advance_ok"] = [i32, i32]
+    lib.bcx_cmc_advance_lds_bytes.restype = ctypes.c_int64
+    lib.bcx_cmc_advance_lds_bytes.argtypes = [i32, i32]
+    lib.bcx_cmc_state_bytes.restype = ctypes.c_int64
+    lib.bcx_cmc_state_bytes.argtypes = [i32]
     sigs["bcx_nuts_coreset"] = [vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
     sigs["bcx_nuts_coreset_ok"] = [i32, i32]
     lib.bcx_nuts_coreset_lds_bytes.restype = ctypes.c_int64

@@ -6,6 +6,7 @@ from . import sampling as _sampling
 from . import sparsevi as _sparsevi
 from . import bpsvi as _bpsvi
 from . import quasinewton as _quasinewton
+from . import coresetmcmc as _coresetmcmc
 from . import sharded_hilbert as _sharded
 
 Coreset = _base.Coreset
@@ -14,7 +15,8 @@ UniformSamplingCoreset = _sampling.UniformSamplingCoreset
 SparseVICoreset = _sparsevi.SparseVICoreset
 BatchPSVICoreset = _bpsvi.BatchPSVICoreset
 QuasiNewtonCoreset = _quasinewton.QuasiNewtonCoreset
+CoresetMCMC = _coresetmcmc.CoresetMCMC
 ShardedHilbertCoreset = _sharded.ShardedHilbertCoreset
 
 
-__all__ = ["Coreset", "HilbertCoreset", "UniformSamplingCoreset", "SparseVICoreset", "BatchPSVICoreset", "QuasiNewtonCoreset", "ShardedHilbertCoreset"]
+__all__ = ["Coreset", "HilbertCoreset", "UniformSamplingCoreset", "SparseVICoreset", "BatchPSVICoreset", "QuasiNewtonCoreset", "CoresetMCMC", "ShardedHilbertCoreset"]

@@ -13,6 +13,8 @@
 //  * bcx_hmc_stream: the same transition for points that do not fit (the full data set): every leapfrog step is one
 //    log-joint pass over the resident rows for all chains and one small kernel per chain behind it that adds the partials in
 //    a fixed order and runs the SAME transition text (hmc_consume) -- enqueued on the stream, no host synchronisation.
+//  * bcx_cmc_advance: the chains of Coreset MCMC -- the coreset kernel's transition from a state carried in global memory, at
+//    weights that move between launches, emitting what the weight step reads (cmc_advance_kernel, cmc_centre_kernel).
 //
 // The chain moves in the whitened variable xi, theta = mu + W^T xi (unit mass matrix; mu, W: the Laplace mode and covariance
 // factor by default, W = I: plain HMC).  Transition t of a chain reads D + 3 standard normals (bcx_standard_normal): D momenta,
@@ -228,18 +230,19 @@ static __device__ void hmc_consume(HmcLds& S, const HmcPar& a, int chain, int ph
     a.samples[o * a.ld + tid] = tid < D ? S.s.thcur[tid] : 0.0;
     if (a.xis) a.xis[o * a.ld + tid] = tid < D ? S.s.xi[tid] : 0.0;
   }
-  if (!(a.fixed_eps > 0.0) && t < a.nwarm) {
+  const int life = a.t0 + t;                   // (the transition's index in the chain's life: t but for cmc_advance_kernel)
+  if (!(a.fixed_eps > 0.0) && life < a.nwarm) {
     const double alpha = fin ? fmin(1.0, exp(-dH)) : 0.0;
-    base = hmc_dual_average(t, a.nwarm, a.eps0, alpha, hbar, lebar);
+    base = hmc_dual_average(life, a.nwarm, a.eps0, alpha, hbar, lebar);
   }
-  if (t >= a.nwarm || a.nwarm >= a.T) nacc += acc ? 1.0 : 0.0;
+  if (life >= a.nwarm || a.nwarm >= a.T) nacc += acc ? 1.0 : 0.0;
   if (tid == 0) {
     if (acc) S.s.sc[SC_LOGP] = logp;
     S.s.sc[SC_BASE] = base; S.s.sc[SC_HBAR] = hbar; S.s.sc[SC_LEBAR] = lebar; S.s.sc[SC_NACC] = nacc;
     double* dg = a.diag + o * HMC_DIAG;
     dg[0] = dH; dg[1] = acc ? 1.0 : 0.0; dg[2] = eps_t; dg[3] = base; dg[4] = hbar; dg[5] = lebar;
     if (!fin) { atomicMax(&a.status[0], 1); atomicMax(&a.status[1], 1); }
-    if (t + 1 == a.T) {
+    if (t + 1 == a.T && a.accept_rate) {       // (cmc_advance_kernel has neither: its caller reads diag)
       const int cnt = a.nwarm >= a.T ? a.T : a.T - a.nwarm;
       a.accept_rate[chain] = nacc / (double)cnt;
       a.eps_final[chain] = base;
@@ -315,6 +318,147 @@ extern "C" int bcx_hmc_coreset(void* stream, int32_t family, int32_t k, int32_t 
   if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_hmc_coreset: memset failed"); return BCX_ERR_HIP; }
   hipLaunchKernelGGL(hmc_coreset_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);
   if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_hmc_coreset: launch failed"); return BCX_ERR_HIP; }
+  return BCX_OK;
+}
+
+// ------------------------------------------------------------------- Coreset MCMC: the chains of a run whose weights move
+// (Chen & Campbell 2024; bayesiancoresets_amd/coreset/coresetmcmc.py)  One launch advances every chain by
+// `thin` transitions of the text above at the weights as they are NOW, and emits what the weight step behind it reads:
+//   * the chain's HmcChain is loaded from `state` (fresh: hmc_reset) and stored back, so a chain lives across launches;
+//   * the target and its gradient at the carried state are evaluated again (phase 0 of hmc_consume): what the previous launch
+//     cached belongs to the previous weights;
+//   * HmcPar::t0 makes the dual averaging count the transitions of the chain's life, not of the launch;
+//   * core[m ldc + chain] = ll(z_m, theta_chain) over the k points and colsum[chain] = sum_r ll(z_rows[r], theta_chain) over
+//     the gathered rows of the resident data (rows NULL: all N), at the state after the last transition.
+// Nothing waits on another workgroup: the order against the weight step is the launch boundary.  A NaN is kept.
+struct CmcArgs {
+  HmcPar par;           // T = thin, nwarm = the life-long adapting transitions; noise / samples / xis / props / diag: this launch's block
+  const double* w;      // k weights
+  const double* pts;    // k x ldp
+  HmcChain* state;      // chains
+  const double* Z;      // N x ldz: the resident data set
+  const int64_t* rows;  // n_rows indices into Z, or NULL (all N rows)
+  double* core;         // k x ldc
+  double* colsum;       // chains
+  int64_t ldp, N, ldz, n_rows, ldc;
+  int family, k, fresh;
+};
+
+__global__ __launch_bounds__(HMC_THREADS) void cmc_advance_kernel(CmcArgs a) {
+  extern __shared__ __attribute__((aligned(16))) double hmc_dyn[];
+  __shared__ HmcLds S;
+  __shared__ double s_part[8 * 32];
+  __shared__ double scratch[BCX_SCRATCH];
+  const int tid = threadIdx.x, chain = blockIdx.x, D = a.par.D;
+  const HmcPoints P = hmc_load_points(hmc_dyn, a.family, a.k, D, a.w, a.pts, a.ldp);
+  hmc_load_frame(S, a.par);
+  if (a.fresh) {
+    hmc_reset(S, a.par);
+  } else {
+    double* dst = (double*)&S.s;
+    const double* src = (const double*)&a.state[chain];
+    for (int e = tid; e < (int)(sizeof(HmcChain) / sizeof(double)); e += HMC_THREADS) dst[e] = src[e];
+    if (tid < 32) S.gth[tid] = 0.0;
+  }
+  __syncthreads();
+  if (tid < 32) S.s.xp[tid] = S.s.xi[tid];           // (the stored xp is the last proposal, accepted or not)
+  __syncthreads();
+  hmc_theta(S, D);
+  __syncthreads();
+
+  auto eval = [&]() -> double { return hmc_eval_points(S, P, D, s_part, scratch); };
+
+  hmc_consume(S, a.par, chain, 0, 0, eval());
+  for (int t = 0; t < a.par.T; ++t)
+    for (int l = 1; l <= a.par.L; ++l) hmc_consume(S, a.par, chain, l, t, eval());
+  {
+    const double* src = (const double*)&S.s;
+    double* dst = (double*)&a.state[chain];
+    for (int e = tid; e < (int)(sizeof(HmcChain) / sizeof(double)); e += HMC_THREADS) dst[e] = src[e];
+  }
+  // what the weight step reads, at thcur
+  const int Dp = D + 1;
+  for (int j = tid; j < a.k; j += HMC_THREADS) {
+    double s = 0.0;
+    for (int c = 0; c < D; ++c) s = fma(P.sX[j * Dp + c], S.s.thcur[c], s);
+    double ll, g, h;
+    lap_point(a.family, s, P.sy[j], ll, g, h);
+    a.core[(size_t)j * a.ldc + chain] = ll;
+  }
+  const int64_t n = a.rows ? a.n_rows : a.N;
+  double part[1] = {0.0};
+  for (int64_t r = tid; r < n; r += HMC_THREADS) {
+    const int64_t i = a.rows ? a.rows[r] : r;
+    if ((uint64_t)i >= (uint64_t)a.N) { part[0] += NAN; continue; }      // (an index outside the data is not read: the sum says so)
+    const double* row = a.Z + (size_t)i * a.ldz;
+    double s = 0.0;
+    for (int c = 0; c < D; ++c) s = fma(row[c], S.s.thcur[c], s);
+    double ll, g, h;
+    lap_point(a.family, s, a.family == LAP_POISSON ? row[D] : 0.0, ll, g, h);
+    part[0] += ll;
+  }
+  block_allsum<1>(part, scratch);                    // (every thread's rows in their order, the lanes, then the waves in theirs)
+  if (tid == 0) a.colsum[chain] = part[0];
+}
+
+// s <- s - mean(s) over the chains, one workgroup: svi_adam_kernel takes the column sums as they arrive and centres only the points
+__global__ __launch_bounds__(256) void cmc_centre_kernel(double* __restrict__ s, int n) {
+  __shared__ double scratch[BCX_SCRATCH];
+  double part[1] = {0.0};
+  for (int c = threadIdx.x; c < n; c += 256) part[0] += s[c];
+  block_allsum<1>(part, scratch);
+  const double mean = part[0] / (double)n;
+  for (int c = threadIdx.x; c < n; c += 256) s[c] -= mean;
+}
+
+extern "C" int64_t bcx_cmc_advance_lds_bytes(int32_t k, int32_t D) {
+  if (k < 0 || D < 1 || D > HMC_DMAX) return -1;
+  return hmc_points_lds_bytes(k, D);
+}
+extern "C" int bcx_cmc_advance_ok(int32_t k, int32_t D) {
+  static PerDevice<int64_t> room;
+  const int64_t b = bcx_cmc_advance_lds_bytes(k, D);
+  return k >= 1 && k <= 4096 && b >= 0 && b <= lds_room((const void*)cmc_advance_kernel, room);
+}
+extern "C" int64_t bcx_cmc_state_bytes(int32_t chains) {
+  if (chains < 1 || chains > 8192) return -1;
+  return (int64_t)chains * (int64_t)sizeof(HmcChain);
+}
+extern "C" int bcx_cmc_advance(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                               const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t thin, int32_t leapfrog, double eps0,
+                               int32_t first_transition, int32_t n_adapt_transitions, int32_t fresh, const void* noise_dev, void* state_dev,
+                               const void* Z_dev, int64_t N, int64_t ldz, const void* rows_dev, int64_t n_rows, void* core_dev, int64_t ldc,
+                               void* colsum_dev, int32_t ld, void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev,
+                               void* status_dev) {
+  const int cols = D + (family == LAP_POISSON ? 1 : 0);
+  if ((family != LAP_LOGISTIC && family != LAP_POISSON) || D < 1 || D > HMC_DMAX || chains < 1 || chains > 8192 || thin < 1 || leapfrog < 1 ||
+      !(eps0 > 0.0) || first_transition < 0 || (int64_t)first_transition + thin > INT32_MAX || n_adapt_transitions < 0 || ld < D || ld > 32 ||
+      !bcx_cmc_advance_ok(k, D) || !w_dev || !pts_dev || ldp < cols || (W_dev && ldw < D) || !noise_dev || !state_dev || N < 1 || !Z_dev ||
+      ldz < cols || (rows_dev ? n_rows < 1 : n_rows != 0) || !core_dev || ldc < chains || !colsum_dev || !samples_dev || !diag_dev ||
+      !status_dev) {
+    bcx_project_set_error("bcx_cmc_advance: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, 1 <= k <= 4096 points within "
+                          "bcx_cmc_advance_ok, at most 8192 chains, ldc >= chains, at least one transition and leapfrog step, eps0 > 0, "
+                          "n_rows 0 without rows_dev)");
+    return BCX_ERR_ARG;
+  }
+  CmcArgs a;
+  a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_adapt_transitions, 0, leapfrog, eps0, 0.0, noise_dev, ld, samples_dev, xi_dev, prop_dev,
+                  diag_dev, nullptr, nullptr, status_dev);
+  a.par.T = thin; a.par.t0 = first_transition;
+  a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.state = (HmcChain*)state_dev; a.Z = (const double*)Z_dev;
+  a.rows = (const int64_t*)rows_dev; a.core = (double*)core_dev; a.colsum = (double*)colsum_dev;
+  a.ldp = ldp; a.N = N; a.ldz = ldz; a.n_rows = n_rows; a.ldc = ldc; a.family = family; a.k = k; a.fresh = fresh != 0;
+  hipStream_t st = (hipStream_t)stream;
+  const size_t lds = (size_t)bcx_cmc_advance_lds_bytes(k, D);
+  static PerDevice<size_t> lds_max;
+  if (raise_dynamic_lds((const void*)cmc_advance_kernel, lds, 16 * 1024, lds_max) != hipSuccess) {
+    bcx_project_set_error("bcx_cmc_advance: hipFuncSetAttribute failed");
+    return BCX_ERR_HIP;
+  }
+  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_cmc_advance: memset failed"); return BCX_ERR_HIP; }
+  hipLaunchKernelGGL(cmc_advance_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);
+  hipLaunchKernelGGL(cmc_centre_kernel, dim3(1), dim3(256), 0, st, (double*)colsum_dev, (int)chains);
+  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_cmc_advance: launch failed"); return BCX_ERR_HIP; }
   return BCX_OK;
 }
 

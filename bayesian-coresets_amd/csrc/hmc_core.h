@@ -27,6 +27,7 @@ struct HmcPar {
   double eps0, fixed_eps;
   int64_t ldw;
   int D, ld, L, T, nwarm, C;
+  int t0;                 // the launch's first transition in the chain's life (0 but for csrc/hmc.hip cmc_advance_kernel: the warm-up counts t0 + t)
 };
 enum { SC_LOGP = 0, SC_BASE, SC_HBAR, SC_LEBAR, SC_EPS_T, SC_H0, SC_E, SC_NACC, SC_COUNT = 16 };
 struct HmcChain {         // one chain's state (LDS; the streamed path keeps a copy in global memory between its kernels)
@@ -156,6 +157,6 @@ static inline HmcPar hmc_par(int32_t D, const void* mu, const void* W, int64_t l
   p.mu = (const double*)mu; p.W = (const double*)W; p.noise = (const double*)noise; p.samples = (double*)samples; p.xis = (double*)xi;
   p.props = (double*)prop; p.diag = (double*)diag; p.accept_rate = (double*)acc; p.eps_final = (double*)eps; p.status = (int*)status;
   p.eps0 = eps0; p.fixed_eps = fixed_eps; p.ldw = ldw; p.D = D; p.ld = ld; p.L = leapfrog; p.T = n_warmup + n_samples; p.nwarm = n_warmup;
-  p.C = chains;
+  p.C = chains; p.t0 = 0;
   return p;
 }

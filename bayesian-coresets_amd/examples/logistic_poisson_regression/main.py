@@ -180,6 +180,9 @@ def run(a):
         # (the quasi-Newton coreset: M uniformly drawn points, opt_itrs Newton steps on all weights; every size is built afresh)
         "QNC": lambda: bc.QuasiNewtonCoreset(Z, dev(sampler_w), n_subsample_opt=a.subsample_opt, opt_itrs=a.opt_itrs,
                                              step_sched=eval(a.step_sched), tau=getattr(a, "qn_tau", 1e-2), subsample="device"),
+        # (Coreset MCMC: M uniformly drawn points, the weights learned from chains on the coreset posterior while they run; its own
+        # step schedule -- --step_sched is tuned for SVI's gradients -- and, as QNC, every size built afresh)
+        "CMC": lambda: bc.CoresetMCMC(Z, family, opt_itrs=a.opt_itrs, n_subsample=a.subsample_opt, seed=a.trial),
         "GIGA-OPT": lambda: bc.HilbertCoreset(Z, dev(gauss(mup, Sigp))),
         "GIGA-REAL": lambda: bc.HilbertCoreset(Z, dev(gauss(muh, Sigh))),
         "US": lambda: bc.UniformSamplingCoreset(Z),
@@ -216,7 +219,7 @@ def run(a):
     for m in range(n):
         print("M = %d: coreset construction, %s %s %d" % (Ms[m], a.alg, a.dataset, a.trial))
         c0, t0 = time.process_time(), time.perf_counter()
-        if a.alg == "QNC":
+        if a.alg in ("QNC", "CMC"):
             alg.reset()
             alg.build(int(Ms[m]))
         else:
@@ -257,7 +260,7 @@ def parser():
     ap.add_argument("--dataset", type=str, default="synth_lr")
     ap.add_argument("--data_num", type=int, default=10000)
     ap.add_argument("--data_dim", type=int, default=3)
-    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "GIGA-OPT", "GIGA-REAL", "US", "QNC"])
+    ap.add_argument("--alg", type=str, default="SVI", choices=["SVI", "GIGA-OPT", "GIGA-REAL", "US", "QNC", "CMC"])
     ap.add_argument("--mcmc_samples_full", type=int, default=10000, help="--eval mcmc: draws from the full-data posterior")
     ap.add_argument("--mcmc_samples_coreset", type=int, default=10000, help="--eval mcmc: draws from every coreset's posterior")
     ap.add_argument("--eval", type=str, choices=["laplace", "mcmc"], default="laplace",
@@ -287,7 +290,7 @@ def parser():
     ap.add_argument("--qn_tau", type=float, default=argparse.SUPPRESS,                       # (absent = 1e-2: result files keep their argument set)
                     help="QNC: the regularisation tau of (G + tau I) d = b")
     ap.add_argument("--subsample_select", type=int, default=None, help="SVI: rows drawn for every selection step (default: all)")
-    ap.add_argument("--subsample_opt", type=int, default=None, help="SVI: rows drawn for every ADAM step (default: all)")
+    ap.add_argument("--subsample_opt", type=int, default=None, help="SVI / QNC / CMC: rows drawn for every weight step (default: all)")
     ap.add_argument("--trial", type=int, default=1)
     ap.add_argument("--results_folder", type=str, default="results/")
     ap.add_argument("--verbosity", type=str, default="error", choices=["error", "warning", "critical", "info", "debug"])

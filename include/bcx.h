@@ -620,6 +620,27 @@ int bcx_hmc_stream(void* stream, int32_t family, int64_t N, int32_t D, const voi
                    int32_t leapfrog, double eps0, double fixed_eps, const void* noise_dev, int32_t ld, void* samples_dev,
                    void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev, void* work_dev,
                    int64_t work_bytes);
+/* One iteration's chain half of Coreset MCMC (Chen & Campbell 2024; csrc/hmc.hip cmc_advance_kernel): `chains`
+ * chains (at most 8192) that live across calls in state_dev (bcx_cmc_state_bytes(chains) bytes; fresh != 0: they start from
+ * xi = 0, base step eps0) each take `thin` transitions of bcx_hmc_coreset at the weights w_dev holds NOW -- the target and its
+ * gradient at the carried state are evaluated again first -- with the k points in LDS (1 <= k <= 4096 within bcx_cmc_advance_ok).
+ * first_transition is the index of the call's first transition in the chains' life: the transitions with index below
+ * n_adapt_transitions adapt the step by the dual averaging with that index, the last of them hands over exp(log eps-bar), later
+ * ones keep it.  noise_dev, samples_dev, xi_dev, prop_dev (the last two may be NULL) and diag_dev are this call's chains x thin x
+ * (D + 3 | ld | ld | ld | 6) blocks, laid out and filled as bcx_hmc_coreset's.  Then, with theta_c the chains' states:
+ *     core_dev[m ldc + c] = log p(z_m | theta_c) of the k points (ldc >= chains; the Poisson -log y! dropped),
+ *     colsum_dev[c]       = sum_r log p(Z[rows[r]] | theta_c) - the mean of these sums over the chains (fixed order),
+ * rows_dev: n_rows int64 indices into the N x ldz rows of Z_dev, or NULL with n_rows = 0: all N rows; an index outside [0, N) is
+ * not read and makes its sum a NaN.  These are the core_dev (raw) / colsum_dev of bcx_sparsevi_adam_step_ws with S = chains.
+ * No workgroup waits on another; a NaN is kept.  status_dev as bcx_hmc_coreset ([0] is zeroed by every call).  Asynchronous. */
+int bcx_cmc_advance_ok(int32_t k, int32_t D);
+int64_t bcx_cmc_advance_lds_bytes(int32_t k, int32_t D);
+int64_t bcx_cmc_state_bytes(int32_t chains);
+int bcx_cmc_advance(void* stream, int32_t family, int32_t k, int32_t D, const void* w_dev, const void* pts_dev, int64_t ldp,
+                    const void* mu_dev, const void* W_dev, int64_t ldw, int32_t chains, int32_t thin, int32_t leapfrog, double eps0,
+                    int32_t first_transition, int32_t n_adapt_transitions, int32_t fresh, const void* noise_dev, void* state_dev,
+                    const void* Z_dev, int64_t N, int64_t ldz, const void* rows_dev, int64_t n_rows, void* core_dev, int64_t ldc,
+                    void* colsum_dev, int32_t ld, void* samples_dev, void* xi_dev, void* prop_dev, void* diag_dev, void* status_dev);
 /* The No-U-Turn sampler (Hoffman & Gelman 2014) on the same target, frame and start as bcx_hmc_coreset, for the (k, D) that fit one
  * workgroup's LDS (csrc/nuts.hip; any N: bcx_nuts_stream below): ONE launch, a workgroup per chain, no leapfrog count to choose.
  * With J = max_depth (1 .. 10), transition t of chain c reads R = D + 3 J + 2 (2^J - 1) standard normals at
