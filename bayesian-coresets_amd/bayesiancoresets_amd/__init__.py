@@ -14,6 +14,7 @@ from .laplace_sampler import LaplacePosteriorSampler
 from .gaussian_sampler import GaussianPosteriorSampler
 from .mcmc import DeviceHMC, log_joint_grad
 from .predictive import log_predictive, PredictiveResult
+from .discrepancy import energy_distance, stein_discrepancy, EnergyResult, SteinResult
 from . import snnls
 from . import util
 

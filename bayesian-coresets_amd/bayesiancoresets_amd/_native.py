@@ -56,6 +56,7 @@ SYMBOLS = (
     "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
     "bcx_quasi_newton_step", "bcx_quasi_newton_scratch_bytes",
     "bcx_cmc_advance", "bcx_cmc_advance_ok", "bcx_cmc_advance_lds_bytes", "bcx_cmc_state_bytes",
+    "bcx_pair_stat", "bcx_pair_stat_scratch_bytes",
 )
 
 
@@ -257,6 +258,9 @@ def load():
     sigs["bcx_log_predictive"] = [vp, i32, vp, i64, i64, i32, vp, i64, i64, i32, vp, vp, vp, i64]
     lib.bcx_log_predictive_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_log_predictive_scratch_bytes.argtypes = [i64, i32, i64, i32]
+    sigs["bcx_pair_stat"] = [vp, i32, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, i32, dbl, i32, vp, vp, i64]
+    lib.bcx_pair_stat_scratch_bytes.restype = ctypes.c_int64
+    lib.bcx_pair_stat_scratch_bytes.argtypes = [i64, i64, i32, i32]
     lib.bcx_hmc_stream_scratch_bytes.restype = ctypes.c_int64
     lib.bcx_hmc_stream_scratch_bytes.argtypes = [i64, i32, i32]
     lib.bcx_psvi_gradient_scratch_bytes.restype = ctypes.c_int64

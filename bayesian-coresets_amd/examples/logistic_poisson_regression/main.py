@@ -29,7 +29,12 @@ mcmc.run_many -- ONE launch for all that fit the LDS-resident NUTS (DESIGN.md 4.
 `--eval mcmc --mcmc_test_rows K`: the last K rows of the loaded data are held out before anything is fitted or built, and two
 columns score the draws on them by bc.log_predictive: `test_ll`, the mean over the held-out rows of the log
 predictive density under the draws of every coreset size (the prior draws for an empty coreset), and `full_test_ll`, the same
-under the full-data draws."""
+under the full-data draws.
+`--eval mcmc --mcmc_discrepancy K`: three columns that compare the draws themselves, not their moments, each side
+thinned evenly to at most K draws, in the frame of the full-data draws (mu their mean, W = L^T with L L^T their covariance):
+`energy`, the squared energy distance between every coreset's draws and the full-data draws (bc.energy_distance(...).value);
+`ksd`, the IMQ kernel Stein discrepancy of every coreset's draws under the FULL-data score (bc.stein_discrepancy with
+family / pts = the full data); `full_ksd`, the same of the full-data draws themselves."""
 import argparse
 import os
 import sys
@@ -109,6 +114,11 @@ def run(a):
         raise ValueError("--mcmc_test_rows goes with --eval mcmc")
     if test_rows is not None and test_rows < 1:
         raise ValueError("--mcmc_test_rows: at least one row")
+    disc = getattr(a, "mcmc_discrepancy", None)                    # (absent unless given: the parser suppresses its default)
+    if disc is not None and not use_mcmc:
+        raise ValueError("--mcmc_discrepancy goes with --eval mcmc")
+    if disc is not None and disc < 2:
+        raise ValueError("--mcmc_discrepancy: at least two draws a side")
     stream = bool(getattr(a, "laplace_stream", False))     # (absent unless given: the parser suppresses its default)
     if results.check_exists(a, a.results_folder):
         print("Results already exist for arguments " + str(a))
@@ -198,6 +208,10 @@ def run(a):
         extra = dict(Fs=np.zeros(n), full_mcmc_time_per_itr=np.full(n, full_t), mcmc_time_per_itr=np.zeros(n))
         if Zt is not None:
             extra.update(test_ll=np.zeros(n), full_test_ll=np.full(n, bc.log_predictive(family, Zt, full_samples).lppd.mean()))
+        if disc is not None:                                                   # the frame of the full-data draws: theta = mup + L xi
+            frame = dict(transform=np.linalg.cholesky(Sigp).T, center=mup, max_draws=disc)
+            full_ksd = bc.stein_discrepancy(full_samples, family=family, pts=Z, **frame).ksd
+            extra.update(energy=np.zeros(n), ksd=np.zeros(n), full_ksd=np.full(n, full_ksd))
     cputs, walls, csizes = np.zeros(n), np.zeros(n), np.zeros(n)
     rklw, fklw, mu_errs, Sig_errs = np.zeros(n), np.zeros(n), np.zeros(n), np.zeros(n)
 
@@ -213,6 +227,9 @@ def run(a):
         extra["mcmc_time_per_itr"][m] = t_cst / (a.mcmc_samples_coreset * 2)
         if Zt is not None:
             extra["test_ll"][m] = bc.log_predictive(family, Zt, cst).lppd.mean()
+        if disc is not None:
+            extra["energy"][m] = bc.energy_distance(cst, full_samples, **frame).value
+            extra["ksd"][m] = bc.stein_discrepancy(cst, family=family, pts=Z, **frame).ksd
         score(m, cst.mean(axis=0), np.cov(cst, rowvar=False))
 
     kept = []                               # --mcmc_batch: (m, points, weights) of every size, scored behind the loop
@@ -281,6 +298,10 @@ def parser():
                     help="with --eval mcmc: hold out the last K rows of the data before anything is fitted or built and add the columns "
                          "test_ll / full_test_ll, their mean log predictive density under each coreset's / the full data's draws "
                          "(bc.log_predictive)")
+    ap.add_argument("--mcmc_discrepancy", type=int, default=argparse.SUPPRESS,               # (result files keep their argument set)
+                    help="with --eval mcmc: add the columns energy / ksd / full_ksd -- the squared energy distance of each coreset's "
+                         "draws to the full-data draws and the IMQ kernel Stein discrepancy of each coreset's / the full data's draws "
+                         "under the full-data score, each side thinned to at most K draws (bc.energy_distance, bc.stein_discrepancy)")
     ap.add_argument("--proj_dim", type=int, default=500)
     ap.add_argument("--coreset_size_max", type=int, default=1000)
     ap.add_argument("--coreset_num_sizes", type=int, default=7)

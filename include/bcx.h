@@ -744,6 +744,23 @@ int bcx_nuts_stream(void* stream, int32_t family, int64_t N, int32_t D, const vo
 int64_t bcx_log_predictive_scratch_bytes(int64_t N, int32_t D, int64_t S, int32_t splits);
 int bcx_log_predictive(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D, const void* Theta_dev,
                        int64_t S, int64_t ldt, int32_t splits, void* lppd_dev, void* mean_dev, void* work_dev, int64_t work_bytes);
+/* Sums over all pairs of two sets of draws (csrc/pairstat.hip): A_dev nA x lda against B_dev nB x ldb, D coordinates.
+ *     kind 0: sum_{i,j} |a_i - b_j|_2.
+ *     kind 1: sum_{i,j} k_p(a_i, b_j), the Stein kernel of the IMQ base kernel (c^2 + |x - y|^2)^(-1/2) under the scores GA_dev (nA x
+ *             ldga) / GB_dev (nB x ldgb): with r = x - y and q = c^2 + |r|^2,
+ *             D q^(-3/2) - 3 |r|^2 q^(-5/2) - ((g_y - g_x) . r) q^(-3/2) + (g_x . g_y) q^(-1/2).
+ * B_dev = NULL: A against itself (nB, ldb, GB_dev, ldgb are not read); only the tiles on and above the diagonal are computed.
+ * out_dev: 2 doubles, the total and the total of the terms i = j (0 unless kind 1 and B_dev = NULL).  1 <= nA, nB <= 2^20,
+ * 1 <= D <= 32, row strides in elements >= D, c finite and > 0 for kind 1.  Differences are formed coordinate by coordinate, so equal
+ * rows are at distance exactly 0.  `splits`: contiguous ranges of B's 64-row tiles per 64-row tile of A, on different workgroups
+ * (0: the library chooses; 1 .. 1024: honoured exactly); one record per (tile, range) in work_dev, added in index order by a second
+ * launch.  No floating-point atomics: the same arguments on the same device give the same bits.  Non-finite input is not screened:
+ * it makes the total non-finite.  work_dev: bcx_pair_stat_scratch_bytes(nA, nB, D, splits) bytes (nB = 0: A against itself; -1: out
+ * of range), work_bytes its size.  BCX_ERR_ARG for anything else.  Asynchronous on `stream`. */
+int64_t bcx_pair_stat_scratch_bytes(int64_t nA, int64_t nB, int32_t D, int32_t splits);
+int bcx_pair_stat(void* stream, int32_t kind, const void* A_dev, int64_t nA, int64_t lda, const void* GA_dev, int64_t ldga,
+                  const void* B_dev, int64_t nB, int64_t ldb, const void* GB_dev, int64_t ldgb, int32_t D, double c, int32_t splits,
+                  void* out_dev, void* work_dev, int64_t work_bytes);
 /* Library/arch identification, e.g. "bcx 0.1 gfx950". */
 const char* bcx_version(void);
 
