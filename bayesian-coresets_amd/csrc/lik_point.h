@@ -10,7 +10,7 @@ static __device__ __forceinline__ void lap_point(int family, double s, double y,
   if (family == LAP_LOGISTIC) {
     // log p = -log(1 + exp(-s)), linear tail beyond -s >= 100 (model_lr.py:29-31)
     const double arg = -s;
-    if (arg < 100.0) {
+    if (!(arg >= 100.0)) {                                          // (a NaN predictor goes through exp: NaN in ll, g and h)
       const double e = exp(arg);
       ll = -log1p(e);
       g = e / (1.0 + e);
@@ -25,8 +25,12 @@ static __device__ __forceinline__ void lap_point(int family, double s, double y,
     const double sig = (s >= 0.0 ? 1.0 : e) / (1.0 + e);           // rate'
     const double dsig = e / ((1.0 + e) * (1.0 + e));                // rate''
     const double safe = rate > 0.0 ? rate : 1.0;
-    const double r1 = rate > 0.0 ? sig / safe : 1.0;                // rate' / rate
-    const double r2 = rate > 0.0 ? (dsig * safe - sig * sig) / (safe * safe) : 0.0;
+    // Below s = -300 the rate is e^s (1 - e^s / 2 + ..): rate' / rate = 1 and (rate'' rate - rate'^2) / rate^2 = -e^s / 2 to every
+    // bit, and neither quotient may be formed there.  e^s is subnormal below s = -708 (exp, log1p and the division then agree
+    // to one part in 2^37 at best: y times that in g), rate^2 leaves the normal range at s = -354 and is 0 from -372.5 on (0 / 0).
+    const bool body = rate > 0.0 && !(s < -300.0);
+    const double r1 = body ? sig / safe : 1.0;                      // rate' / rate
+    const double r2 = body ? (dsig * safe - sig * sig) / (safe * safe) : (rate > 0.0 ? -0.5 * e : 0.0);
     g = y * r1 - sig;
     h = y * r2 - dsig;
   }

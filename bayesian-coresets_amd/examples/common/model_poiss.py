@@ -37,10 +37,13 @@ def _derivs(s, y):
     sig = np.where(s >= 0.0, 1.0, e) / (1.0 + e)              # rate'(s) = sigmoid(s), relative accuracy in both tails
     dsig = e / ((1.0 + e) * (1.0 + e))                        # rate''(s)
     safe = np.where(rate > 0.0, rate, 1.0)
-    r1 = np.where(rate > 0.0, sig / safe, 1.0)                # rate' / rate  (-> 1 as s -> -inf)
-    g = y * r1 - sig
-    # (rate'' rate - rate'^2) / rate^2  (-> 0 as s -> -inf, where log rate = s)
-    r2 = np.where(rate > 0.0, (dsig * safe - sig * sig) / (safe * safe), 0.0)
+    # below s = -300 the rate is e^s (1 - e^s / 2 + ..): rate' / rate = 1 and (rate'' rate - rate'^2) / rate^2 = -e^s / 2 to every
+    # bit; the quotients are not used there (e^s is subnormal below -708, rate^2 underflows from -354 on: csrc/lik_point.h)
+    body = (rate > 0.0) & ~(s < -300.0)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        r1 = np.where(body, sig / safe, 1.0)                  # rate' / rate  (-> 1 as s -> -inf)
+        g = y * r1 - sig
+        r2 = np.where(body, (dsig * safe - sig * sig) / (safe * safe), np.where(rate > 0.0, -0.5 * e, 0.0))
     h = y * r2 - dsig
     return g, h
 

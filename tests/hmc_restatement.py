@@ -17,7 +17,7 @@ def point_terms(family, s, y):
     """(log-likelihood, its derivative in s) of every point, in the dtype of s (the branches of csrc/lik_point.h)."""
     if family == "logistic":
         arg = -s
-        small = arg < 100
+        small = np.logical_not(arg >= 100)                     # (NaN goes through exp)
         e = np.exp(np.where(small, arg, 0))
         return np.where(small, -np.log1p(e), -arg), np.where(small, e / (1 + e), 1)
     e = np.exp(-np.abs(s))
@@ -26,7 +26,7 @@ def point_terms(family, s, y):
     safe = np.where(pos, rate, 1)
     lr = np.where(s > -100, np.log(safe), s)
     sig = np.where(s >= 0, 1, e) / (1 + e)
-    return y * lr - rate, y * np.where(pos, sig / safe, 1) - sig
+    return y * lr - rate, y * np.where(pos & np.logical_not(s < -300), sig / safe, 1) - sig
 
 
 class Target(object):
