@@ -21,6 +21,10 @@
 //                     160 rows at a time, itself on the matrix cores.  The column means of R ride along as one more row: their
 //                     "draw" is the mean of the draws (thetabar: what the closed-form column sums are expanded around,
 //                     csrc/moments.hip).
+//                     What the ABI does NOT promise: bcx_linreg_posterior_draw takes k <= 64 at any D, but for k > D and heavy
+//                     weights I + C C^T is singular up to the added identity and the form loses what the D x D form keeps (float64
+//                     restatement at D = 40, k = 64, weights 1e4: e_cov 2e-8 where the reference's algorithm has 1e-15; DESIGN.md
+//                     4.24).  The sampler routes k <= 4 + 2 ceil(D / 32) here, which is <= D from D = 6 on; below, k <= 6.
 //   svi_adam_kernel   resid = scaling colsum - w corevecs, g = -corevecs resid / S, the ADAM moments, the step and the clamp at
 //                     zero, on the device-resident weights; the step-size schedule and the bias corrections arrive as data
 //                     (the caller evaluates step_sched(i), 1 - b1^(i+1), 1 - b2^(i+1) on the host once per greedy step).
@@ -366,10 +370,14 @@ __global__ __launch_bounds__(256) void lrs_apply_kernel(LraArgs a) {
   }
   __syncthreads();
   if (!row_ok) return;
-  // ---- this wave's row: theta = mu0 + (X Sig0)^T coef + g - sum_j (g . X_j) B2_j ----
-  double2 acc[LRA_NI];
+  // ---- this wave's row: theta = [mu0 + (X Sig0)^T coef] + [g - sum_j (g . X_j) B2_j], the two sums APART: with collinear points
+  // the mean's k terms are 1e4 times the mean they cancel to (D = 301, k = 24, weights that sum to N: terms of 4e5 for a mean of
+  // 70).  Accumulated into the row's own sum they are rounded against a different running value in every row, 1e-9 of
+  // difference between draws that share the mean -- 800 times the reference's own error of the covariance in the posterior's
+  // metric (measured: DESIGN.md 4.24).  Kept apart, the mean's sum is the same number in every row and every workgroup. ----
+  double2 acc[LRA_NI], accm[LRA_NI];
 #pragma unroll
-  for (int i = 0; i < LRA_NI; ++i) acc[i] = make_double2(m0[i].x + g[i].x, m0[i].y + g[i].y);
+  for (int i = 0; i < LRA_NI; ++i) { acc[i] = g[i]; accm[i] = m0[i]; }
   for (int j0 = 0; j0 < k; j0 += 4) {
     double2 xs[4][LRA_NI];                          // X Sig0, four points per round of loads (cached: every workgroup reads them)
 #pragma unroll
@@ -400,8 +408,10 @@ __global__ __launch_bounds__(256) void lrs_apply_kernel(LraArgs a) {
           const int c = 2 * lane + 128 * i;
           if (c < ld) {
             const double2 b = *(const double2*)(sB2 + (size_t)j * ld + c);
-            acc[i].x += cj * xs[q][i].x - pj * b.x;
-            acc[i].y += cj * xs[q][i].y - pj * b.y;
+            accm[i].x = fma(cj, xs[q][i].x, accm[i].x);
+            accm[i].y = fma(cj, xs[q][i].y, accm[i].y);
+            acc[i].x = fma(-pj, b.x, acc[i].x);
+            acc[i].y = fma(-pj, b.y, acc[i].y);
           }
         }
       }
@@ -411,6 +421,8 @@ __global__ __launch_bounds__(256) void lrs_apply_kernel(LraArgs a) {
   for (int i = 0; i < LRA_NI; ++i) {
     const int c = 2 * lane + 128 * i;
     if (c < ld) {
+      acc[i].x += accm[i].x;
+      acc[i].y += accm[i].y;
       if (c + 1 >= D) acc[i].y = 0.0;               // (the padding column)
       if (row < S) *(double2*)(a.theta + (size_t)row * ld + c) = acc[i];
       else { a.tbar[c] = acc[i].x; if (c + 1 < D) a.tbar[c + 1] = acc[i].y; }
