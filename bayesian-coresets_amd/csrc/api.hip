@@ -16,31 +16,12 @@ extern "C" const char* bcx_version(void) { return "bcx 0.1 gfx950"; }
 
 extern "C" const char* bcx_last_error(const bcx_solver* s) { return s ? s->err.c_str() : g_create_err.c_str(); }
 
-template <typename T> static hipError_t dev_alloc(T** p, size_t count, bool zero = true) {
-  *p = nullptr;
-  if (count == 0) count = 1;
-  hipError_t e = hipMalloc((void**)p, count * sizeof(T));
-  if (e != hipSuccess) return e;
-  if (zero) e = hipMemset(*p, 0, count * sizeof(T));
-  return e;
-}
-
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
-static void free_all(bcx_solver* s) {
-  void* ptrs[] = {s->An, s->A64, s->norms, s->chunk_sums, s->staging, s->st, s->b, s->bn, s->xw, s->q64, s->qst,
-                  s->tmp, s->partials, s->rec_local, s->act_idx, s->act_w, s->act_rows, s->act_norm, s->gram,
-                  s->hinv, s->hinv_lo, s->cvec, s->plist, s->ppos, s->nn_x, s->nn_z, s->nn_wv, s->nn_tmp, s->nn_flag, s->nn_wbak, s->nn_xr, s->tr_sel, s->tr_err,
-                  s->tr_status};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (size_t w = 0; w < s->peer_mbox.size(); ++w)
-    if (s->peer_mbox[w] && s->peer_mbox[w] != s->mbox) (void)hipIpcCloseMemHandle(s->peer_mbox[w]);
-  void* xptrs[] = {s->mbox, s->peer_tab, s->xseq, s->xprobe, s->rec_gather, s->grid_counter, s->fin_part, s->gram_work, s->warm_buf,
-                   s->Aq, s->scr_sb, s->scr_partials, s->scr_stat, s->A4, s->s4_sb, s->s4_list, s->s4_counts, s->s4_sent};
-  for (void* p : xptrs)
-    if (p) (void)hipFree(p);
-  for (auto& ev : s->prof_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+// a failed DevBuf call (its HIP status) as the solver's error, in BCX_HIP's form
+static int mem_fail(bcx_solver* s, const char* what, int e) {
+  s->err = std::string(what) + ": " + hipGetErrorString((hipError_t)e);
+  return BCX_ERR_HIP;
 }
 
 extern "C" int bcx_create(const bcx_config* cfg, bcx_solver** out) {
@@ -75,22 +56,22 @@ extern "C" int bcx_create(const bcx_config* cfg, bcx_solver** out) {
   s->ld64 = round_up(d, 2);
   s->n_chunks = (n + BCX_CHUNK_ROWS - 1) / BCX_CHUNK_ROWS;
   bool ok = true;
-  auto chk = [&](hipError_t r) { if (r != hipSuccess && ok) { ok = false; g_create_err = std::string("hipMalloc: ") + hipGetErrorString(r); } };
-  chk(dev_alloc((char**)&s->An, (size_t)n * s->ld * s->elem));
-  if (cfg->keep_exact_rows && cfg->store_dtype != BCX_F64) chk(dev_alloc(&s->A64, (size_t)n * s->ld64));
-  chk(dev_alloc(&s->norms, (size_t)n));
-  chk(dev_alloc(&s->chunk_sums, (size_t)s->n_chunks * (d + 1)));
-  chk(dev_alloc(&s->st, 1));
-  chk(dev_alloc(&s->b, (size_t)d));
-  chk(dev_alloc(&s->bn, (size_t)d));
-  chk(dev_alloc(&s->xw, (size_t)d));
-  chk(dev_alloc(&s->q64, (size_t)2 * s->ld64));
-  chk(dev_alloc((char**)&s->qst, (size_t)2 * s->ld * s->qelem));
-  chk(dev_alloc(&s->tmp, (size_t)20 * d));
+  auto chk = [&](int r) { if (r != 0 && ok) { ok = false; g_create_err = std::string("hipMalloc: ") + hipGetErrorString((hipError_t)r); } };
+  chk(s->An.alloc((size_t)n * s->ld * s->elem, true));
+  if (cfg->keep_exact_rows && cfg->store_dtype != BCX_F64) chk(s->A64.alloc((size_t)n * s->ld64, true));
+  chk(s->norms.alloc((size_t)n, true));
+  chk(s->chunk_sums.alloc((size_t)s->n_chunks * (d + 1), true));
+  chk(s->st.alloc(1, true));
+  chk(s->b.alloc((size_t)d, true));
+  chk(s->bn.alloc((size_t)d, true));
+  chk(s->xw.alloc((size_t)d, true));
+  chk(s->q64.alloc((size_t)2 * s->ld64, true));
+  chk(s->qst.alloc((size_t)2 * s->ld * s->qelem, true));
+  chk(s->tmp.alloc((size_t)20 * d, true));
   s->n_partials = 0;
-  chk(dev_alloc((char**)&s->partials, (size_t)bcx_scan_grid(s) * BCX_PARTIAL_BYTES));
-  chk(dev_alloc(&s->rec_local, (size_t)(d + BCX_REC_HDR)));
-  if (!ok) { free_all(s); delete s; return BCX_ERR_NOMEM; }
+  chk(s->partials.alloc((size_t)bcx_scan_grid(s) * BCX_PARTIAL_BYTES, true));
+  chk(s->rec_local.alloc((size_t)(d + BCX_REC_HDR), true));
+  if (!ok) { delete s; return BCX_ERR_NOMEM; }
   bounce_acquire(cfg->device);
   *out = s;
   return BCX_OK;
@@ -100,9 +81,9 @@ extern "C" int bcx_destroy(bcx_solver* s) {
   if (!s) return BCX_OK;
   (void)hipSetDevice(s->cfg.device);
   (void)hipDeviceSynchronize();
-  free_all(s);
-  bounce_release(s->cfg.device);
-  delete s;
+  const int device = s->cfg.device;
+  delete s;      // unmaps the peers' mailboxes, frees every device buffer, destroys the profiling events
+  bounce_release(device);
   return BCX_OK;
 }
 
@@ -275,18 +256,13 @@ static int load_rows(bcx_solver* s, const void* src, int32_t src_is_device, int3
     const int64_t piece = std::max<int64_t>(BCX_CHUNK_ROWS,
                                             ((int64_t)(256u << 20) / (int64_t)(d * esz)) / BCX_CHUNK_ROWS * BCX_CHUNK_ROWS);
     const size_t need = (size_t)std::min(piece, rows) * d * esz;
-    if (s->staging_bytes < need) {
-      if (s->staging) BCX_HIP(hipFree(s->staging));
-      s->staging = nullptr; s->staging_bytes = 0;
-      BCX_HIP(hipMalloc(&s->staging, need));
-      s->staging_bytes = need;
-    }
+    if (s->staging.count() < need) BCX_HIP((hipError_t)s->staging.alloc(need, false));
     for (int64_t r = 0; r < rows; r += piece) {
       const int64_t m = std::min(piece, rows - r);
-      int rc = upload_host_rows(s, s->staging, (size_t)d * esz, (const char*)src + (size_t)r * ld * esz, (size_t)ld * esz,
+      int rc = upload_host_rows(s, s->staging.get(), (size_t)d * esz, (const char*)src + (size_t)r * ld * esz, (size_t)ld * esz,
                                 (size_t)d * esz, m);
       if (rc != BCX_OK) return rc;
-      rc = bcx_launch_ingest(s, s->staging, src_dtype, d, row_begin + r, m, center);
+      rc = bcx_launch_ingest(s, s->staging.get(), src_dtype, d, row_begin + r, m, center);
       if (rc != BCX_OK) return rc;
       BCX_HIP(hipStreamSynchronize(s->stream));  // staging buffer is reused
     }
@@ -340,24 +316,20 @@ extern "C" int bcx_finalize(bcx_solver* s, const double* b_host, const void* gat
 }
 
 // ---- capacity management -----------------------------------------------------------------
-template <typename T> static int grow(bcx_solver* s, T** p, size_t old_count, size_t new_count) {
-  T* q = nullptr;
-  BCX_HIP(dev_alloc(&q, new_count));
-  if (*p && old_count) BCX_HIP(hipMemcpy(q, *p, old_count * sizeof(T), hipMemcpyDeviceToDevice));
-  if (*p) BCX_HIP(hipFree(*p));
-  *p = q;
-  return BCX_OK;
-}
-
+// A capacity change commits whole or not at all: every new buffer is built in a local (DevBuf::grown: zero-filled, with a
+// copy of what the kernels still read), and only when all of them exist are they moved into the solver and the capacity
+// set -- a block that cannot fail.  After a failure the solver is what it was and the locals have freed what they held.
 static int ensure_slots(bcx_solver* s, int64_t need) {
   if (need <= s->cap) return BCX_OK;
-  int64_t ncap = std::max<int64_t>(need, std::max<int64_t>(256, s->cap * 2));
-  const size_t d = (size_t)s->cfg.d;
-  int rc;
-  if ((rc = grow(s, &s->act_idx, (size_t)s->cap, (size_t)ncap))) return rc;
-  if ((rc = grow(s, &s->act_w, (size_t)s->cap, (size_t)ncap))) return rc;
-  if ((rc = grow(s, &s->act_norm, (size_t)s->cap, (size_t)ncap))) return rc;
-  if ((rc = grow(s, &s->act_rows, (size_t)s->cap * d, (size_t)ncap * d))) return rc;
+  const int64_t ncap = std::max<int64_t>(need, std::max<int64_t>(256, s->cap * 2));
+  const size_t d = (size_t)s->cfg.d, oc = (size_t)s->cap, nc = (size_t)ncap;
+  int e = 0;
+  auto idx = DevBuf<int64_t>::grown(s->act_idx, nc, oc, &e);
+  auto w = DevBuf<double>::grown(s->act_w, nc, oc, &e);
+  auto norm = DevBuf<double>::grown(s->act_norm, nc, oc, &e);
+  auto rows = DevBuf<double>::grown(s->act_rows, nc * d, oc * d, &e);
+  if (e) return mem_fail(s, "grow", e);
+  s->act_idx = std::move(idx); s->act_w = std::move(w); s->act_norm = std::move(norm); s->act_rows = std::move(rows);
   s->cap = ncap;
   return BCX_OK;
 }
@@ -366,43 +338,43 @@ int bcx_ensure_gram(bcx_solver* s, int64_t need) {
   if (need <= s->gram_cap) return BCX_OK;
   const int64_t ncap = std::max<int64_t>((need + 63) / 64 * 64, std::max<int64_t>(256, s->gram_cap * 2));
   const size_t oc = (size_t)s->gram_cap, nc = (size_t)ncap;
-  // gram / hinv change their leading dimension: copy row by row
-  double* g2 = nullptr; double* h2 = nullptr; double* l2 = nullptr;
-  BCX_HIP(dev_alloc(&g2, nc * nc));
-  BCX_HIP(dev_alloc(&h2, nc * nc));
-  BCX_HIP(dev_alloc(&l2, nc * nc));
-  if (oc) {
-    BCX_HIP(hipMemcpy2D(g2, nc * 8, s->gram, oc * 8, oc * 8, oc, hipMemcpyDeviceToDevice));
-    BCX_HIP(hipMemcpy2D(h2, nc * 8, s->hinv, oc * 8, oc * 8, oc, hipMemcpyDeviceToDevice));
-    BCX_HIP(hipMemcpy2D(l2, nc * 8, s->hinv_lo, oc * 8, oc * 8, oc, hipMemcpyDeviceToDevice));
-    BCX_HIP(hipFree(s->gram));
-    BCX_HIP(hipFree(s->hinv));
-    BCX_HIP(hipFree(s->hinv_lo));
-  }
-  s->gram = g2; s->hinv = h2; s->hinv_lo = l2;
-  int rc;
-  if ((rc = grow(s, &s->cvec, oc, nc))) return rc;
-  if ((rc = grow(s, &s->plist, oc, nc))) return rc;
-  if ((rc = grow(s, &s->ppos, oc, nc))) return rc;
-  if ((rc = grow(s, &s->nn_x, oc, nc))) return rc;
-  if ((rc = grow(s, &s->nn_z, 0, nc))) return rc;
-  if ((rc = grow(s, &s->nn_wv, 0, nc))) return rc;
-  if ((rc = grow(s, &s->nn_tmp, 0, 16 * nc))) return rc;   // t0..t3 + the exchange ring of grid_lh.h (GRID_RING = 16 buffers)
-  if ((rc = grow(s, &s->nn_flag, 0, nc))) return rc;
-  if ((rc = grow(s, &s->nn_wbak, 0, nc))) return rc;
-  if ((rc = grow(s, &s->nn_xr, 0, 2 * nc))) return rc;
+  int e = 0;
+  // gram / hinv change their leading dimension: copied row by row
+  auto mat = [&](const DevBuf<double>& m) { return DevBuf<double>::grown_rows(m, oc, nc, nc, oc, &e); };
+  auto gram = mat(s->gram), hinv = mat(s->hinv), hinv_lo = mat(s->hinv_lo);
+  auto cvec = DevBuf<double>::grown(s->cvec, nc, oc, &e);
+  auto plist = DevBuf<int32_t>::grown(s->plist, nc, oc, &e), ppos = DevBuf<int32_t>::grown(s->ppos, nc, oc, &e);
+  auto x = DevBuf<double>::grown(s->nn_x, nc, oc, &e);
+  // scratch of one step: nothing to keep
+  auto z = DevBuf<double>::grown(s->nn_z, nc, 0, &e), wv = DevBuf<double>::grown(s->nn_wv, nc, 0, &e);
+  auto tmp = DevBuf<double>::grown(s->nn_tmp, 16 * nc, 0, &e);   // t0..t3 + the exchange ring of grid_lh.h (GRID_RING = 16 buffers)
+  auto flag = DevBuf<int32_t>::grown(s->nn_flag, nc, 0, &e);
+  auto wbak = DevBuf<double>::grown(s->nn_wbak, nc, 0, &e), xr = DevBuf<double>::grown(s->nn_xr, 2 * nc, 0, &e);
+  if (e) return mem_fail(s, "grow", e);
+  s->gram = std::move(gram); s->hinv = std::move(hinv); s->hinv_lo = std::move(hinv_lo);
+  s->cvec = std::move(cvec); s->plist = std::move(plist); s->ppos = std::move(ppos); s->nn_x = std::move(x);
+  s->nn_z = std::move(z); s->nn_wv = std::move(wv); s->nn_tmp = std::move(tmp);
+  s->nn_flag = std::move(flag); s->nn_wbak = std::move(wbak); s->nn_xr = std::move(xr);
   s->gram_cap = ncap;
   return BCX_OK;
 }
 
 static int ensure_trace(bcx_solver* s, int64_t need) {
   if (need <= s->trace_cap) return BCX_OK;
-  int64_t ncap = std::max<int64_t>(need, 1024);
-  int rc;
-  if ((rc = grow(s, &s->tr_sel, 0, (size_t)ncap))) return rc;
-  if ((rc = grow(s, &s->tr_err, 0, (size_t)ncap))) return rc;
-  if ((rc = grow(s, &s->tr_status, 0, (size_t)ncap))) return rc;
-  s->trace_cap = ncap;
+  const size_t nc = (size_t)std::max<int64_t>(need, 1024);
+  int e = 0;
+  auto sel = DevBuf<int64_t>::grown(s->tr_sel, nc, 0, &e);
+  auto err = DevBuf<double>::grown(s->tr_err, nc, 0, &e);
+  auto status = DevBuf<int32_t>::grown(s->tr_status, nc, 0, &e);
+  if (e) return mem_fail(s, "grow", e);
+  s->tr_sel = std::move(sel); s->tr_err = std::move(err); s->tr_status = std::move(status);
+  s->trace_cap = (int64_t)nc;
+  return BCX_OK;
+}
+
+int bcx_ensure_grid_counter(bcx_solver* s) {
+  if (s->grid_counter) return BCX_OK;
+  if (s->grid_counter.alloc(BCX_GRID_WORDS, true) != 0) { s->err = "grid counter allocation failed"; return BCX_ERR_NOMEM; }
   return BCX_OK;
 }
 
@@ -420,7 +392,7 @@ extern "C" int bcx_build_begin(bcx_solver* s, int64_t itrs, double tol, int32_t*
   if ((rc = ensure_slots(s, (int64_t)h.k + itrs))) return rc;
   if (s->cfg.alg == BCX_ALG_OMP) {
     if ((rc = bcx_ensure_gram(s, (int64_t)h.k + itrs))) return rc;
-    if (!s->grid_counter && dev_alloc(&s->grid_counter, 32 /* = BCX_GRID_WORDS, nnls_common.h */) != hipSuccess) { s->err = "grid counter allocation failed"; return BCX_ERR_NOMEM; }
+    if ((rc = bcx_ensure_grid_counter(s))) return rc;
     BCX_HIP(hipMemsetAsync(s->grid_counter, 0, 2 * sizeof(unsigned long long), s->stream));
     s->grid_epoch = 0;
     s->grid_dirty = false;
@@ -551,14 +523,12 @@ static int mailbox_alloc(bcx_solver* s) {
   const int world = s->cfg.world_size;
   const size_t bytes = bcx_mailbox_slot_offset(world) + 2 * (size_t)world * (s->cfg.d + BCX_REC_HDR) * sizeof(double);
   // fine-grained: stores from peer GPUs become visible to a kernel that is already running here
-  hipError_t e = hipExtMallocWithFlags(&s->mbox, bytes, hipDeviceMallocFinegrained);
-  if (e != hipSuccess) {
+  const int e = s->mbox.alloc(bytes, false, true);
+  if (e != 0) {
     (void)hipGetLastError();
-    s->mbox = nullptr;
-    s->err = std::string("peer mailbox: fine-grained allocation failed: ") + hipGetErrorString(e);
+    s->err = std::string("peer mailbox: fine-grained allocation failed: ") + hipGetErrorString((hipError_t)e);
     return BCX_ERR_HIP;
   }
-  s->mbox_bytes = bytes;
   BCX_HIP(hipMemset(s->mbox, 0, bytes));
   BCX_HIP(hipDeviceSynchronize());
   return BCX_OK;
@@ -590,30 +560,46 @@ extern "C" int bcx_exchange_attach(bcx_solver* s, const void* handles, int32_t h
   BCX_HIP(hipSetDevice(s->cfg.device));
   const int world = s->cfg.world_size;
   if (world > BCX_APPLY_THREADS) { s->err = "peer mailbox supports at most 256 shards"; return BCX_ERR_ARG; }
-  s->peer_mbox.assign(world, nullptr);
+  if (!s->peer_mbox.empty()) {
+    // attached before and disabled since: the earlier attachment goes first (nothing enqueued may still be reading it)
+    BCX_HIP(hipStreamSynchronize(s->stream));
+    s->close_peers();
+    s->peer_tab.reset(); s->xseq.reset(); s->xprobe.reset(); s->rec_gather.reset();
+  }
+  // everything is built in locals and handed to the solver at the end: a failure on the way leaves nothing mapped
+  std::vector<void*> peers(world, nullptr);
+  auto unmap = [&]() {
+    for (int v = 0; v < world; ++v)
+      if (v != s->cfg.rank && peers[v]) (void)hipIpcCloseMemHandle(peers[v]);
+  };
   for (int w = 0; w < world; ++w) {
-    if (w == s->cfg.rank) { s->peer_mbox[w] = s->mbox; continue; }
+    if (w == s->cfg.rank) { peers[w] = s->mbox; continue; }
     hipIpcMemHandle_t h;
     memcpy(&h, (const char*)handles + (size_t)w * handle_bytes, sizeof(h));
-    hipError_t e = hipIpcOpenMemHandle(&s->peer_mbox[w], h, hipIpcMemLazyEnablePeerAccess);
+    hipError_t e = hipIpcOpenMemHandle(&peers[w], h, hipIpcMemLazyEnablePeerAccess);
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      s->peer_mbox[w] = nullptr;
+      peers[w] = nullptr;
       s->err = "peer mailbox: cannot map shard " + std::to_string(w) + ": " + hipGetErrorString(e);
-      for (int v = 0; v < w; ++v)
-        if (v != s->cfg.rank && s->peer_mbox[v]) { (void)hipIpcCloseMemHandle(s->peer_mbox[v]); s->peer_mbox[v] = nullptr; }
-      s->peer_mbox.clear();
+      unmap();
       return BCX_ERR_HIP;
     }
   }
-  hipError_t e;
-  if ((e = dev_alloc(&s->peer_tab, (size_t)world)) != hipSuccess || (e = dev_alloc(&s->xseq, 8)) != hipSuccess ||
-      (e = dev_alloc(&s->xprobe, 1)) != hipSuccess ||
-      (e = dev_alloc(&s->rec_gather, (size_t)world * (s->cfg.d + BCX_REC_HDR))) != hipSuccess) {
-    s->err = std::string("peer mailbox: ") + hipGetErrorString(e);
+  DevBuf<void*> tab;
+  DevBuf<unsigned long long> xseq;
+  DevBuf<int32_t> xprobe;
+  DevBuf<double> gather;
+  int e;
+  if ((e = tab.alloc((size_t)world, true)) || (e = xseq.alloc(8, true)) || (e = xprobe.alloc(1, true)) ||
+      (e = gather.alloc((size_t)world * (s->cfg.d + BCX_REC_HDR), true))) {
+    s->err = std::string("peer mailbox: ") + hipGetErrorString((hipError_t)e);
+    unmap();
     return BCX_ERR_NOMEM;
   }
-  BCX_HIP(hipMemcpy(s->peer_tab, s->peer_mbox.data(), (size_t)world * sizeof(void*), hipMemcpyHostToDevice));
+  const hipError_t ec = hipMemcpy(tab, peers.data(), (size_t)world * sizeof(void*), hipMemcpyHostToDevice);
+  if (ec != hipSuccess) { unmap(); return mem_fail(s, "peer mailbox: hipMemcpy", (int)ec); }
+  s->peer_mbox = std::move(peers);
+  s->peer_tab = std::move(tab); s->xseq = std::move(xseq); s->xprobe = std::move(xprobe); s->rec_gather = std::move(gather);
   if (timeout_s > 0.0) s->exchange_timeout_s = timeout_s;
   s->exchange_ready = true;
   return BCX_OK;
@@ -1013,7 +999,7 @@ extern "C" int bcx_screen_stats(bcx_solver* s, int64_t* out8) {
   out8[3] = (int64_t)st8[SCR_OVERFLOWS];
   out8[4] = (int64_t)st8[SCR_REDOS];
   out8[5] = !possible ? 3 : s->scr_dropped;
-  out8[6] = s->Aq ? (int64_t)s->scr_cap_rows * (s->ld8 + 8) + (int64_t)BCX_MAX_PARTIALS * BCX_PARTIAL_BYTES + SCR_WORDS * 8 : 0;
+  out8[6] = s->Aq ? (int64_t)s->scr_sb.count() * (s->ld8 + 8) + (int64_t)BCX_MAX_PARTIALS * BCX_PARTIAL_BYTES + SCR_WORDS * 8 : 0;
   out8[7] = (int64_t)(s->scr_build_ms * 1e3f);
   return BCX_OK;
 }
@@ -1039,7 +1025,7 @@ extern "C" int bcx_screen4_stats(bcx_solver* s, int64_t* out8) {
   out8[3] = (int64_t)st8[SCR4_OVERFLOWS];
   out8[4] = s->s4_redos;
   out8[5] = !possible ? 3 : s->s4_dropped;
-  out8[6] = s->A4 ? (int64_t)s->s4_cap_rows * (s->ld4 + 8) + (int64_t)BCX_MAX_PARTIALS * (BCX_S4_SEG_CAP + 1) * 4 : 0;
+  out8[6] = s->A4 ? (int64_t)s->s4_sb.count() * (s->ld4 + 8) + (int64_t)BCX_MAX_PARTIALS * (BCX_S4_SEG_CAP + 1) * 4 : 0;
   out8[7] = s->s4_drops;
   return BCX_OK;
 }
@@ -1058,7 +1044,7 @@ extern "C" int bcx_screen_read(bcx_solver* s, int64_t begin, int64_t count, void
   if (count == 0) return BCX_OK;
   if (codes) BCX_HIP(hipMemcpy(codes, (const char*)s->Aq + (size_t)begin * s->ld8, (size_t)count * s->ld8, hipMemcpyDeviceToHost));
   std::vector<float> sb((size_t)count * 2);
-  BCX_HIP(hipMemcpy(sb.data(), (const char*)s->scr_sb + (size_t)begin * 8, (size_t)count * 8, hipMemcpyDeviceToHost));
+  BCX_HIP(hipMemcpy(sb.data(), s->scr_sb + begin, (size_t)count * 8, hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < count; ++i) {
     if (scales) scales[i] = sb[2 * i];
     if (bounds) bounds[i] = sb[2 * i + 1];
@@ -1092,7 +1078,7 @@ extern "C" int bcx_screen4_read(bcx_solver* s, int64_t begin, int64_t count, voi
   if (count == 0) return BCX_OK;
   if (codes) BCX_HIP(hipMemcpy(codes, (const char*)s->A4 + (size_t)begin * s->ld4, (size_t)count * s->ld4, hipMemcpyDeviceToHost));
   std::vector<float> sb((size_t)count * 2);
-  BCX_HIP(hipMemcpy(sb.data(), (const char*)s->s4_sb + (size_t)begin * 8, (size_t)count * 8, hipMemcpyDeviceToHost));
+  BCX_HIP(hipMemcpy(sb.data(), s->s4_sb + begin, (size_t)count * 8, hipMemcpyDeviceToHost));
   for (int64_t i = 0; i < count; ++i) {
     if (scales) scales[i] = sb[2 * i];
     if (bounds) bounds[i] = sb[2 * i + 1];

@@ -7,6 +7,7 @@
 #include <utility>
 #include <vector>
 #include "../../include/bcx.h"
+#include "dev_buf.h"
 
 #define BCX_CHUNK_ROWS 1024      // rows per column-sum chunk (fixed summation tree, shard-count independent)
 #define BCX_MAX_CAND 64          // candidate rows re-scored in fp64 per shard per iteration
@@ -123,82 +124,76 @@ struct bcx_solver {
   int elem = 4;             // bytes per stored element
   int qelem = 4;            // bytes per element of the storage-precision query
   int ld64 = 0;             // row stride (doubles) of A64 / q64 (d rounded up to even)
-  void* An = nullptr;       // n_local x ld, fp32 or fp64, rows normalised to unit norm
-  double* A64 = nullptr;    // n_local x ld64 raw rows (optional)
-  double* norms = nullptr;  // n_local
-  double* chunk_sums = nullptr;  // n_chunks x (d+1)
+  DevBuf<char> An;          // n_local x ld, fp32 or fp64, rows normalised to unit norm
+  DevBuf<double> A64;       // n_local x ld64 raw rows (optional)
+  DevBuf<double> norms;     // n_local
+  DevBuf<double> chunk_sums;     // n_chunks x (d+1)
   int64_t n_chunks = 0;
-  void* staging = nullptr;  // upload staging when raw rows are not kept
-  size_t staging_bytes = 0;
-  DevState* st = nullptr;
-  double* b = nullptr;      // d
-  double* bn = nullptr;     // d (GIGA)
-  double* xw = nullptr;     // d
-  double* q64 = nullptr;    // 2 x ld64 query vectors (fp64, used by the exact re-score)
-  void* qst = nullptr;      // 2 x ld query vectors in storage precision (read by the scan)
-  double* tmp = nullptr;    // 4 x d scratch
-  void* partials = nullptr;     // PartialView storage
+  DevBuf<char> staging;     // upload staging when raw rows are not kept
+  DevBuf<DevState> st;
+  DevBuf<double> b;         // d
+  DevBuf<double> bn;        // d (GIGA)
+  DevBuf<double> xw;        // d
+  DevBuf<double> q64;       // 2 x ld64 query vectors (fp64, used by the exact re-score)
+  DevBuf<char> qst;         // 2 x ld query vectors in storage precision (read by the scan)
+  DevBuf<double> tmp;       // 4 x d scratch
+  DevBuf<char> partials;        // PartialView storage
   int n_partials = 0;
-  double* rec_local = nullptr;   // (d+4) record produced by this shard when world_size == 1
-  double* fin_part = nullptr;    // finalize: sums of groups of chunk sums
-  int64_t fin_cap = 0;
+  DevBuf<double> rec_local;      // (d+4) record produced by this shard when world_size == 1
+  DevBuf<double> fin_part;       // finalize: sums of groups of chunk sums
   // peer mailbox (bcx_exchange_*): device-side record exchange for world_size > 1
-  void* mbox = nullptr;          // this shard's mailbox (fine-grained device memory, exported over hipIpc)
-  size_t mbox_bytes = 0;
+  DevBuf<char> mbox;             // this shard's mailbox (fine-grained device memory, exported over hipIpc)
   std::vector<void*> peer_mbox;  // mapped mailboxes by rank ([rank] == mbox)
-  void** peer_tab = nullptr;     // device copy of peer_mbox
-  unsigned long long* xseq = nullptr;   // [0] exchanges completed; [1..5] timing statistics, [6] late ranks (bit mask) and [7] the exchange
+  DevBuf<void*> peer_tab;        // device copy of peer_mbox
+  DevBuf<unsigned long long> xseq;      // [0] exchanges completed; [1..5] timing statistics, [6] late ranks (bit mask) and [7] the exchange
                                         // number of the last timeout (Mailbox::stat[0..6])
-  int32_t* xprobe = nullptr;
-  double* rec_gather = nullptr;  // world x (d+4): records of the last exchange (input of the OMP apply kernels)
+  DevBuf<int32_t> xprobe;
+  DevBuf<double> rec_gather;     // world x (d+4): records of the last exchange (input of the OMP apply kernels)
   bool exchange_ready = false;
   double exchange_timeout_s = 20.0;
   // sparse weight list (selection order), grown on demand
   int64_t cap = 0;
-  int64_t* act_idx = nullptr;    // global row index per slot
-  double* act_w = nullptr;       // weight per slot
-  double* act_rows = nullptr;    // cap x d raw rows of the slots (replicated)
-  double* act_norm = nullptr;    // norm per slot
+  DevBuf<int64_t> act_idx;       // global row index per slot
+  DevBuf<double> act_w;          // weight per slot
+  DevBuf<double> act_rows;       // cap x d raw rows of the slots (replicated)
+  DevBuf<double> act_norm;       // norm per slot
   // OMP / optimize(): Gram system over the slots
-  double* gram = nullptr;        // cap x cap
-  double* hinv = nullptr;        // cap x cap inverse of the passive block
-  double* hinv_lo = nullptr;     // its low words (double-double inverse of the OMP step, omp_lh.hip)
-  double* cvec = nullptr;        // cap : a_j . b
-  int32_t* plist = nullptr;      // passive list (slot ids)
-  int32_t* ppos = nullptr;       // slot -> position in plist or -1
-  double* nn_x = nullptr;        // cap
-  double* nn_z = nullptr;        // cap
-  double* nn_wv = nullptr;       // cap
-  double* nn_tmp = nullptr;      // 16*cap: position scratch t0..t3 = the first quarter of the exchange ring (grid_lh.h)
-  int32_t* nn_flag = nullptr;    // cap: bit0 in problem set S, bit1 rejected, bit2 remove
-  double* nn_wbak = nullptr;     // cap: weights before the step (revert on monotone failure)
-  double* nn_xr = nullptr;       // 2*cap: row-phase exchange of the OMP step (omp_lh.hip)
+  DevBuf<double> gram;           // cap x cap
+  DevBuf<double> hinv;           // cap x cap inverse of the passive block
+  DevBuf<double> hinv_lo;        // its low words (double-double inverse of the OMP step, omp_lh.hip)
+  DevBuf<double> cvec;           // cap : a_j . b
+  DevBuf<int32_t> plist;         // passive list (slot ids)
+  DevBuf<int32_t> ppos;          // slot -> position in plist or -1
+  DevBuf<double> nn_x;           // cap
+  DevBuf<double> nn_z;           // cap
+  DevBuf<double> nn_wv;          // cap
+  DevBuf<double> nn_tmp;         // 16*cap: position scratch t0..t3 = the first quarter of the exchange ring (grid_lh.h)
+  DevBuf<int32_t> nn_flag;       // cap: bit0 in problem set S, bit1 rejected, bit2 remove
+  DevBuf<double> nn_wbak;        // cap: weights before the step (revert on monotone failure)
+  DevBuf<double> nn_xr;          // 2*cap: row-phase exchange of the OMP step (omp_lh.hip)
   int64_t gram_cap = 0;
-  double* gram_work = nullptr;   // optimize(): slice partials of the Gram kernel (moments.hip), grown on demand
-  size_t gram_work_bytes = 0;
-  void* warm_buf = nullptr;      // optimize(): buffers of the warm start (csrc/warm.hip), grown on demand
-  size_t warm_bytes = 0;
+  DevBuf<double> gram_work;      // optimize(): slice partials of the Gram kernel (moments.hip), grown on demand
+  DevBuf<char> warm_buf;         // optimize(): buffers of the warm start (csrc/warm.hip), grown on demand
   int64_t opt_warm = 0, opt_warm_failed = 0;   // optimize() calls that started warm / whose warm start was rejected by the closing check
   int64_t k_ub = 0;              // host upper bound of the slot count (grid sizing of the multi-kernel OMP step)
-  unsigned long long* grid_counter = nullptr;   // [0] arrival counter of the grid barriers, [1] barrier base of the next OMP step
+  DevBuf<unsigned long long> grid_counter;      // [0] arrival counter of the grid barriers, [1] barrier base of the next OMP step
   uint64_t grid_epoch = 0;       // fused OMP launches since the counter was reset (bcx_build_begin)
   int64_t opt_fallbacks = 0;     // optimize() calls that took the refined solve after the incremental one's check failed (bcx_omp_stats)
   bool grid_dirty = false;       // optimize() advanced grid_counter[0] past the OMP step's base [1]: re-zero both before the next OMP step
   size_t omp_lds_allowed = 0;
   // trace of the current build() call
   int64_t trace_cap = 0;
-  int64_t* tr_sel = nullptr;
-  double* tr_err = nullptr;
-  int32_t* tr_status = nullptr;
+  DevBuf<int64_t> tr_sel;
+  DevBuf<double> tr_err;
+  DevBuf<int32_t> tr_status;
   bool finalized = false;
   int64_t rows_loaded = 0;
   // 8-bit screening tier (screen8.hip)
-  void* Aq = nullptr;            // n_local x ld8 codes
-  void* scr_sb = nullptr;        // n_local x (fp32 scale, fp32 bound)
-  void* scr_partials = nullptr;  // per-wave partials of the screen kernel
-  unsigned long long* scr_stat = nullptr;   // SCR_* words
+  DevBuf<char> Aq;               // n_local x ld8 codes
+  DevBuf<float2> scr_sb;         // n_local x (fp32 scale, fp32 bound)
+  DevBuf<char> scr_partials;     // per-wave partials of the screen kernel
+  DevBuf<unsigned long long> scr_stat;      // SCR_* words
   int ld8 = 0;
-  int64_t scr_cap_rows = 0;
   bool scr_enabled = true;       // off: BCX_SCREEN8=0 (dev switch)
   int scr_dropped = 0;           // 1: dropped by the overflow rule until bcx_reset, 2: no memory for the shadow
   bool scr_valid = false;        // the shadow matches the stored rows
@@ -208,14 +203,13 @@ struct bcx_solver {
   int64_t scr_halts = 0;
   int scr_n_in = 0;              // partials in scr_partials after the last tier iteration that was enqueued
   // 4-bit front tier (screen4.hip): in front of the 8-bit tier for the single-query algorithms on one shard
-  void* A4 = nullptr;            // n_local x ld4 bytes of 4-bit codes
-  void* s4_sb = nullptr;         // n_local x (fp32 scale4, fp32 bound4)
-  void* s4_list = nullptr;       // BCX_MAX_PARTIALS segments of BCX_S4_SEG_CAP row indices
-  void* s4_counts = nullptr;     // BCX_MAX_PARTIALS entries: rows a wave wanted to list
-  void* s4_sent = nullptr;       // BCX_S4_SENTINELS row indices (-1: none) the last refine_kernel left for the next front pass
+  DevBuf<char> A4;               // n_local x ld4 bytes of 4-bit codes
+  DevBuf<float2> s4_sb;          // n_local x (fp32 scale4, fp32 bound4)
+  DevBuf<int32_t> s4_list;       // BCX_MAX_PARTIALS segments of BCX_S4_SEG_CAP row indices
+  DevBuf<int32_t> s4_counts;     // BCX_MAX_PARTIALS entries: rows a wave wanted to list
+  DevBuf<int32_t> s4_sent;       // BCX_S4_SENTINELS row indices (-1: none) the last refine_kernel left for the next front pass
   int ld4 = 0;
   int s4_seg_cap = BCX_S4_SEG_CAP;   // entries of a segment in use; dev switch BCX_SCREEN4_SEGCAP=<n> lowers it (tests of the overflow path)
-  int64_t s4_cap_rows = 0;
   bool s4_enabled = true;        // off: BCX_SCREEN4=0 (dev switch)
   int s4_dropped = 0;            // 1: dropped to the 8-bit tier by the redo rule until bcx_reset, 2: no memory for the second shadow
   bool s4_valid = false;         // the 4-bit shadow matches the stored rows
@@ -233,6 +227,17 @@ struct bcx_solver {
   int64_t prof_launches = 0;
   std::vector<std::pair<hipEvent_t, hipEvent_t>> prof_events;
   size_t prof_used = 0;
+
+  // The peers' mailboxes are unmapped here, before the members go: this shard's own mailbox (one of them) is freed after.
+  void close_peers() {
+    for (void* p : peer_mbox)
+      if (p && p != mbox.get()) (void)hipIpcCloseMemHandle(p);
+    peer_mbox.clear();
+  }
+  ~bcx_solver() {
+    close_peers();
+    for (auto& ev : prof_events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
+  }
 };
 
 // ---- kernel launchers (defined in the .hip files) ------------------------
@@ -261,6 +266,10 @@ int bcx_gram_rows_tiled(hipStream_t st, const double* rows, int k, int d, int64_
 unsigned long long bcx_gram_sk_epoch_now();
 int bcx_gram_sk_timed_out(hipStream_t st, const double* work, unsigned long long since);
 int bcx_scan_grid(const bcx_solver* s);
+// api.hip: the words behind bcx_solver::grid_counter, allocated zero-filled on first use; the callers reset what they use per call
+#define BCX_GRID_WORDS 32   // [0] arrivals, [1] barrier base of the next OMP step, [16] (its own 128-byte line) the barrier index
+                            // word of the split form (GridSync::gen)
+int bcx_ensure_grid_counter(bcx_solver* s);
 // screen8.hip
 bool bcx_screen_on(const bcx_solver* s);
 int bcx_screen_build(bcx_solver* s);

@@ -273,7 +273,7 @@ int bcx_launch_ingest(bcx_solver* s, const void* src, int src_dtype, int64_t ld_
     if (shmem > 48 * 1024)                                                                                    \
       BCX_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));  \
     hipLaunchKernelGGL(kfn, grid, block, shmem, s->stream, (const TS_*)src, ld_src, row_begin, rows, d,       \
-                       (TD_*)s->An, s->ld, s->ld64, s->A64, s->norms, s->chunk_sums, s->st, center, acc_global); \
+                       (TD_*)s->An.get(), s->ld, s->ld64, s->A64, s->norms, s->chunk_sums, s->st, center, acc_global); \
   } while (0)
 #define LAUNCH(TS, TD)                                                                                        \
   do {                                                                                                        \
@@ -370,12 +370,7 @@ int bcx_launch_finalize(bcx_solver* s, int have_b, const double* gathered, int64
   if (n > 2 * FIN_GROUP) {
     // two levels: groups of FIN_GROUP chunks in parallel, then the (few) group sums in order
     const int64_t ng = (n + FIN_GROUP - 1) / FIN_GROUP;
-    if (s->fin_cap < ng) {
-      if (s->fin_part) (void)hipFree(s->fin_part);
-      s->fin_part = nullptr;
-      BCX_HIP(hipMalloc((void**)&s->fin_part, (size_t)ng * (d + 1) * sizeof(double)));
-      s->fin_cap = ng;
-    }
+    if (s->fin_part.count() < (size_t)ng * (d + 1)) BCX_HIP((hipError_t)s->fin_part.alloc((size_t)ng * (d + 1), false));
     hipLaunchKernelGGL(finalize_partial_kernel, dim3((unsigned)ng), dim3(256), 0, s->stream, d, sums, n, s->fin_part);
     sums = s->fin_part;
     n = ng;

@@ -718,12 +718,7 @@ int bcx_launch_optimize(bcx_solver* s, double tol) {
   if (k > 0) {
     const int kp64 = (k + 63) / 64 * 64;       // (the warm start forms the inverse of a kp64 x kp64 block with the same kernel)
     const size_t need = std::max((size_t)bcx_gram_rows_scratch_bytes(k, s->cfg.d), (size_t)bcx_gram_rows_scratch_bytes(kp64, kp64));
-    if (s->gram_work_bytes < need) {
-      if (s->gram_work) BCX_HIP(hipFree(s->gram_work));
-      s->gram_work = nullptr; s->gram_work_bytes = 0;
-      BCX_HIP(hipMalloc((void**)&s->gram_work, need));
-      s->gram_work_bytes = need;
-    }
+    if (s->gram_work.count() * sizeof(double) < need) BCX_HIP((hipError_t)s->gram_work.alloc((need + 7) / 8, false));
     const int rc = bcx_gram_rows(s->stream, s->act_rows, k, s->cfg.d, (int64_t)s->cfg.d, s->gram, (int64_t)s->gram_cap, s->gram_work);
     if (rc != BCX_OK) { s->err = "optimize: Gram kernel launch failed"; return rc; }
   }
@@ -736,12 +731,7 @@ int bcx_launch_optimize(bcx_solver* s, double tol) {
     const int32_t* warm_p = nullptr;
     if (!cold_only && s->gram_work) {
       const size_t need_w = bcx_warm_bytes(k);
-      if (s->warm_bytes < need_w) {
-        if (s->warm_buf) BCX_HIP(hipFree(s->warm_buf));
-        s->warm_buf = nullptr; s->warm_bytes = 0;
-        BCX_HIP(hipMalloc(&s->warm_buf, need_w));
-        s->warm_bytes = need_w;
-      }
+      if (s->warm_buf.count() < need_w) BCX_HIP((hipError_t)s->warm_buf.alloc(need_w, false));
       const int wrc = bcx_warm_start(s, k, s->warm_buf, s->gram_work, &warm_p);
       if (wrc < 0) return wrc;
       if (wrc != 0) warm_p = nullptr;
@@ -755,7 +745,7 @@ int bcx_launch_optimize(bcx_solver* s, double tol) {
       { const int g = gram_ok(); if (g != BCX_OK) return g; }
       if (h.omp_mode != OMP_OPT_FALLBACK) return BCX_OK;
       s->opt_warm_failed += 1;
-      BCX_HIP(hipMemsetAsync((char*)s->st + offsetof(DevState, omp_mode), 0, sizeof(int32_t), s->stream));
+      BCX_HIP(hipMemsetAsync((char*)s->st.get() + offsetof(DevState, omp_mode), 0, sizeof(int32_t), s->stream));
       rc = bcx_launch_optimize_lh(s, tol, k, nullptr);
       if (rc < 0) return rc;
     }
@@ -765,7 +755,7 @@ int bcx_launch_optimize(bcx_solver* s, double tol) {
       { const int g = gram_ok(); if (g != BCX_OK) return g; }
       if (h.omp_mode != OMP_OPT_FALLBACK) return BCX_OK;
       s->opt_fallbacks += 1;
-      BCX_HIP(hipMemsetAsync((char*)s->st + offsetof(DevState, omp_mode), 0, sizeof(int32_t), s->stream));
+      BCX_HIP(hipMemsetAsync((char*)s->st.get() + offsetof(DevState, omp_mode), 0, sizeof(int32_t), s->stream));
     }
     { const int g = gram_ok(); if (g != BCX_OK) return g; }      // (the forms below read the same G)
     rc = bcx_launch_optimize_grid(s, tol, k);             // 1 = not applicable

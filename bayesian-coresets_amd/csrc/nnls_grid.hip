@@ -222,9 +222,7 @@ __global__ __launch_bounds__(NN_THREADS) void optimize_grid_kernel(NnlsArgs n, G
 
 int bcx_launch_optimize_grid(bcx_solver* s, double tol, int k) {
   if (k >= OPT_MAX_K || bcx_dev_env("BCX_OPT_SINGLE")) return 1;   // caller uses the single-workgroup kernel
-  if (!s->grid_counter) {
-    BCX_HIP(hipMalloc((void**)&s->grid_counter, BCX_GRID_WORDS * sizeof(unsigned long long)));
-  }
+  if (const int rc = bcx_ensure_grid_counter(s)) return rc;
   BCX_HIP(hipMemsetAsync(s->grid_counter, 0, 2 * sizeof(unsigned long long), s->stream));   // [0] arrivals, [1] the OMP step's barrier base
   s->grid_epoch = 0;
   NnlsArgs n;

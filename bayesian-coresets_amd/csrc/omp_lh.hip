@@ -1119,7 +1119,7 @@ int bcx_launch_optimize_lh(bcx_solver* s, double tol, int k, const int32_t* warm
   const int kcap = (k + 1 + 63) / 64 * 64;
   const size_t lds = (size_t)kcap * (8 * sizeof(double) + 3 * sizeof(int));
   if (lds > OMPL_LDS_MAX) return 1;
-  if (!s->grid_counter) BCX_HIP(hipMalloc((void**)&s->grid_counter, BCX_GRID_WORDS * sizeof(unsigned long long)));
+  if (const int rc = bcx_ensure_grid_counter(s)) return rc;
   BCX_HIP(hipMemsetAsync(s->grid_counter, 0, BCX_GRID_WORDS * sizeof(unsigned long long), s->stream));
   s->grid_epoch = 0;
   NnlsArgs n;

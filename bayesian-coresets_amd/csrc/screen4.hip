@@ -440,30 +440,25 @@ int bcx_screen4_build(bcx_solver* s) {
   const int64_t n = s->cfg.n_local;
   s->ld4 = (d + 31) / 32 * 16;
   const int nw4 = s->ld4 / 4;
-  if (s->s4_cap_rows < n || !s->A4) {
-    void** all[] = {&s->A4, &s->s4_sb, &s->s4_list, &s->s4_counts, &s->s4_sent};
-    for (void** p : all) { if (*p) (void)hipFree(*p); *p = nullptr; }
-    s->s4_cap_rows = 0;
-    hipError_t e = hipMalloc(&s->A4, (size_t)n * s->ld4);
-    if (e == hipSuccess) e = hipMalloc(&s->s4_sb, (size_t)n * 8);
-    if (e == hipSuccess) e = hipMalloc(&s->s4_list, (size_t)BCX_MAX_PARTIALS * BCX_S4_SEG_CAP * 4);
-    if (e == hipSuccess) e = hipMalloc(&s->s4_counts, (size_t)BCX_MAX_PARTIALS * 4);
-    if (e == hipSuccess) e = hipMalloc(&s->s4_sent, (size_t)BCX_S4_SENTINELS * 4);
-    if (e != hipSuccess) {
+  if (s->s4_sb.count() < (size_t)n || !s->A4) {
+    auto drop = [&]() { s->A4.reset(); s->s4_sb.reset(); s->s4_list.reset(); s->s4_counts.reset(); s->s4_sent.reset(); };
+    drop();      // all go before any is asked for again
+    if (s->A4.alloc((size_t)n * s->ld4, false) || s->s4_sb.alloc((size_t)n, false) ||
+        s->s4_list.alloc((size_t)BCX_MAX_PARTIALS * BCX_S4_SEG_CAP, false) || s->s4_counts.alloc((size_t)BCX_MAX_PARTIALS, false) ||
+        s->s4_sent.alloc((size_t)BCX_S4_SENTINELS, false)) {
       (void)hipGetLastError();
-      for (void** p : all) { if (*p) (void)hipFree(*p); *p = nullptr; }
+      drop();
       s->s4_dropped = 2;
       return BCX_OK;
     }
-    s->s4_cap_rows = n;
     // no sentinels yet (-1 each); s4_warm below keeps the front pass away until a refine_kernel has written them
     BCX_HIP(hipMemsetAsync(s->s4_sent, 0xff, (size_t)BCX_S4_SENTINELS * 4, s->stream));
   }
   const unsigned grid = (unsigned)((n + 3) / 4);
   if (s->cfg.store_dtype == BCX_F16)
-    hipLaunchKernelGGL((quantise4_kernel<true>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, nw4, n, (unsigned*)s->A4, (float2*)s->s4_sb);
+    hipLaunchKernelGGL((quantise4_kernel<true>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, nw4, n, (unsigned*)s->A4.get(), s->s4_sb.get());
   else
-    hipLaunchKernelGGL((quantise4_kernel<false>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, nw4, n, (unsigned*)s->A4, (float2*)s->s4_sb);
+    hipLaunchKernelGGL((quantise4_kernel<false>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, nw4, n, (unsigned*)s->A4.get(), s->s4_sb.get());
   BCX_HIP(hipGetLastError());
   s->s4_valid = true;
   s->s4_warm = 2;          // new rows: the sentinels the last refine left name rows of the old ones
@@ -504,9 +499,9 @@ static int front4_plan(bcx_solver* s, Front4Plan* p) {
   const float kacc = screen_kacc(G8, CH8, d);
 
   Front4Args& f = p->f;
-  f.A4 = (const uint4*)s->A4; f.sb = (const float2*)s->s4_sb; f.q = (const float*)s->qst; f.sent = (const int*)s->s4_sent;
-  f.Aq = (const unsigned char*)s->Aq; f.sb8 = (const float2*)s->scr_sb; f.st = s->st;
-  f.list = (int*)s->s4_list; f.counts = (int*)s->s4_counts;
+  f.A4 = (const uint4*)s->A4.get(); f.sb = s->s4_sb; f.q = (const float*)s->qst.get(); f.sent = s->s4_sent;
+  f.Aq = (const unsigned char*)s->Aq.get(); f.sb8 = s->scr_sb; f.st = s->st;
+  f.list = s->s4_list; f.counts = s->s4_counts;
   f.n = n; f.ldv = s->ld4 / 16; f.nw4 = nw4; f.seg_cap = s->s4_seg_cap;
   f.ld8 = s->ld8; f.d = d; f.kacc = kacc; f.err_coef = sa.err_coef;
   const int G = screen_group(f.ldv), CH = screen_chunks(f.ldv, G);

@@ -400,29 +400,17 @@ int bcx_screen_build(bcx_solver* s) {
   const int d = s->cfg.d;
   const int64_t n = s->cfg.n_local;
   s->ld8 = (d + 15) / 16 * 16;
-  const size_t need = (size_t)n * s->ld8;
-  hipError_t e = hipSuccess;
-  if (s->scr_cap_rows < n || !s->Aq) {
-    if (s->Aq) (void)hipFree(s->Aq);
-    if (s->scr_sb) (void)hipFree(s->scr_sb);
-    s->Aq = nullptr; s->scr_sb = nullptr; s->scr_cap_rows = 0;
-    e = hipMalloc(&s->Aq, need);
-    if (e == hipSuccess) e = hipMalloc(&s->scr_sb, (size_t)n * 8);
-    if (e == hipSuccess && !s->scr_partials) e = hipMalloc(&s->scr_partials, (size_t)BCX_MAX_PARTIALS * BCX_PARTIAL_BYTES);
-    if (e == hipSuccess && !s->scr_stat) {
-      e = hipMalloc((void**)&s->scr_stat, SCR_WORDS * sizeof(unsigned long long));
-      if (e == hipSuccess) e = hipMemset(s->scr_stat, 0, SCR_WORDS * sizeof(unsigned long long));
-    }
-    if (e != hipSuccess) {
+  if (s->scr_sb.count() < (size_t)n || !s->Aq) {
+    s->Aq.reset(); s->scr_sb.reset();      // both go before either is asked for again
+    if (s->Aq.alloc((size_t)n * s->ld8, false) || s->scr_sb.alloc((size_t)n, false) ||
+        (!s->scr_partials && s->scr_partials.alloc((size_t)BCX_MAX_PARTIALS * BCX_PARTIAL_BYTES, false)) ||
+        (!s->scr_stat && s->scr_stat.alloc(SCR_WORDS, true))) {
       // no room for the shadow: the solver runs on the storage-precision scan, and says so in bcx_screen_stats
       (void)hipGetLastError();
-      if (s->Aq) (void)hipFree(s->Aq);
-      if (s->scr_sb) (void)hipFree(s->scr_sb);
-      s->Aq = nullptr; s->scr_sb = nullptr;
+      s->Aq.reset(); s->scr_sb.reset();
       s->scr_dropped = 2;
       return BCX_OK;
     }
-    s->scr_cap_rows = n;
   }
   hipEvent_t e0, e1;
   BCX_HIP(hipEventCreate(&e0));
@@ -430,9 +418,9 @@ int bcx_screen_build(bcx_solver* s) {
   BCX_HIP(hipEventRecord(e0, s->stream));
   const unsigned grid = (unsigned)((n + 3) / 4);
   if (s->cfg.store_dtype == BCX_F16)
-    hipLaunchKernelGGL((quantise_kernel<true>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, s->ld8, n, (unsigned*)s->Aq, (float2*)s->scr_sb);
+    hipLaunchKernelGGL((quantise_kernel<true>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, s->ld8, n, (unsigned*)s->Aq.get(), s->scr_sb.get());
   else
-    hipLaunchKernelGGL((quantise_kernel<false>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, s->ld8, n, (unsigned*)s->Aq, (float2*)s->scr_sb);
+    hipLaunchKernelGGL((quantise_kernel<false>), dim3(grid), dim3(256), 0, s->stream, s->An, s->ld, d, s->ld8, n, (unsigned*)s->Aq.get(), s->scr_sb.get());
   BCX_HIP(hipGetLastError());
   BCX_HIP(hipEventRecord(e1, s->stream));
   BCX_HIP(hipEventSynchronize(e1));
@@ -463,9 +451,9 @@ template <bool DUAL> static int launch_screen_t(bcx_solver* s, const ScreenArgs&
 int bcx_launch_screen(bcx_solver* s) {
   const int d = s->cfg.d;
   ScreenArgs a;
-  a.Aq = (const uint4*)s->Aq;
-  a.sb = (const float2*)s->scr_sb;
-  a.q = (const float*)s->qst;
+  a.Aq = (const uint4*)s->Aq.get();
+  a.sb = s->scr_sb;
+  a.q = (const float*)s->qst.get();
   a.ldq = s->ld;
   a.st = s->st;
   a.n = s->cfg.n_local;
@@ -509,10 +497,10 @@ int bcx_launch_refine(bcx_solver* s, int n_in, bool four) {
   r.in = partial_view(s->scr_partials, n_in); r.n_in = n_in;
   r.out = partial_view(s->partials, BCX_SCREEN_MAX_SURV);
   r.st = s->st; r.stat = s->scr_stat;
-  r.An = s->An; r.q = (const float*)s->qst;
+  r.An = s->An; r.q = (const float*)s->qst.get();
   r.store_f16 = f16; r.ld = s->ld; r.ldq = s->ld; r.d = d; r.dual = s->cfg.alg == BCX_ALG_GIGA;
-  r.sent = bcx_screen4_on(s) ? (int*)s->s4_sent : nullptr;   // (dropped to the 8-bit tier: nobody reads sentinels until reset)
-  r.counts = four ? (const int*)s->s4_counts : nullptr; r.seg_cap = s->s4_seg_cap; r.n = s->cfg.n_local;
+  r.sent = bcx_screen4_on(s) ? s->s4_sent.get() : nullptr;   // (dropped to the 8-bit tier: nobody reads sentinels until reset)
+  r.counts = four ? s->s4_counts.get() : nullptr; r.seg_cap = s->s4_seg_cap; r.n = s->cfg.n_local;
   // stored row and fp32 query multiplied and summed in fp64: what is left is their own rounding (2 u, fp16: its storage term)
   // and d 2^-53; 30 % head room as in bcx_scan_plan
   r.coef_mid = 1.3 * u * 3.0;

@@ -99,6 +99,24 @@ def test_incremental_build_matches_single_call(bc, normal_inputs, alg):
 
 
 @pytest.mark.parametrize("alg", ("giga", "fw", "omp"))
+def test_incremental_build_across_a_capacity_growth_matches_single_call(bc, normal_inputs, alg):
+    """The same with a second input whose calls leave the first capacity of 256 slots: the second build(200) grows the slot
+    arrays (and for OMP the Gram system, whose leading dimension changes) 256 -> 512 around 200 slots that are in use, and
+    what the growth keeps has to be what a single build(400) has."""
+    X = normal_inputs(21, 4000, 512)
+    a = _run(bc, X, alg, 400)
+    b = _solver(bc, alg)(X.T, X.sum(axis=0))
+    sel = []
+    for step in (200, 200):
+        b.build(step)
+        sel.append(np.array(b.last_trace[0]))
+    np.testing.assert_allclose(a.weights(), b.weights(), rtol=1e-12, atol=0)
+    assert a.error() == pytest.approx(b.error(), rel=1e-12)
+    if alg == "omp":
+        assert np.array_equal(np.array(a.last_trace[0]), np.concatenate(sel))
+
+
+@pytest.mark.parametrize("alg", ("giga", "fw", "omp"))
 def test_against_oracle_random_shape(bc, alg):
     """Fresh seeded input (not in the golden file): HIP engine vs the CPU oracle, d not a multiple of 4."""
     from oracle.snnls_oracle import SnnlsOracle
