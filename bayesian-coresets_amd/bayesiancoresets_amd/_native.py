@@ -6,77 +6,21 @@ import os
 
 import numpy as np
 
+from . import _abi
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # a source checkout builds the library in-tree (make -C bayesian-coresets_amd); an installed package carries it inside (setup.py)
 LIB_PATH = os.path.join(os.path.dirname(_HERE), "lib", "libbcx.so")
 if not os.path.exists(LIB_PATH) and os.path.exists(os.path.join(_HERE, "_lib", "libbcx.so")):
     LIB_PATH = os.path.join(_HERE, "_lib", "libbcx.so")
 
-ALG_GIGA, ALG_FW, ALG_OMP = 0, 1, 2
-F32, F64, F16 = 0, 1, 2
-OK, ERR_ARG, ERR_HIP, ERR_ZERO_ROW, ERR_ZERO_B, ERR_NOMEM, ERR_STATE, ERR_EXCHANGE, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7, -8
-IT_OK, IT_FAIL_SELECT, IT_FAIL_REWEIGHT, IT_FAIL_MONOTONE = 0, 1, 2, 3
+# the header's enums and integer #defines under their names less the BCX_ prefix: ALG_*, F32 / F64 / F16, OK, ERR_*, IT_*,
+# MAX_ROW_LENGTH, LOAD_CENTER_ROWS, SCREEN4_MAX_WAVES, ...; REC_HDR and CHUNK_ROWS are csrc/bcx_internal.h's, not the boundary's
+globals().update((name[4:], value) for name, value in _abi.CONSTANTS.items())
 REC_HDR = 4
-LOAD_CENTER_ROWS = 1
-MAX_ROW_LENGTH = 1048576      # BCX_MAX_ROW_LENGTH of include/bcx.h (tests/test_abi.py keeps the two equal)
 CHUNK_ROWS = 1024
-
-# every symbol include/bcx.h declares (checked by tests/test_abi.py)
-SYMBOLS = (
-    "bcx_create", "bcx_destroy", "bcx_last_error", "bcx_set_stream", "bcx_load_rows", "bcx_chunk_sums", "bcx_export_chunk_sums",
-    "bcx_finalize", "bcx_build_begin", "bcx_step_scan", "bcx_step_apply", "bcx_build_enqueue", "bcx_build_poll",
-    "bcx_step_scan_exact", "bcx_build_trace", "bcx_active_count", "bcx_get_weights", "bcx_error", "bcx_optimize",
-    "bcx_reset", "bcx_reached_numeric_limit", "bcx_get_vector", "bcx_get_norms", "bcx_get_stored_rows", "bcx_argmax_correlation", "bcx_time_scan",
-    "bcx_stats", "bcx_screen_stats", "bcx_screen4_stats", "bcx_screen_read", "bcx_screen4_read", "bcx_screen4_probe", "bcx_profile_scan", "bcx_profile_read", "bcx_version",
-    "bcx_project_write", "bcx_project_colsum", "bcx_project_select", "bcx_project_last_error",
-    "bcx_build_enqueue_exact", "bcx_exchange_export", "bcx_exchange_attach", "bcx_exchange_probe", "bcx_exchange_disable", "bcx_exchange_set_timeout",
-    "bcx_set_check_monotone", "bcx_project_profile", "bcx_project_profile_read", "bcx_exchange_stats", "bcx_load_rows_flags", "bcx_project_write_raw", "bcx_omp_stats", "bcx_project_select_ws", "bcx_project_select_scratch_bytes",
-    "bcx_project_moments", "bcx_project_colsum_moments", "bcx_project_moments_scratch_bytes",
-    "bcx_project_colsum_moments_scratch_bytes", "bcx_gram", "bcx_gram_scratch_bytes", "bcx_gram_check",
-    "bcx_project_colsum_moments_at", "bcx_project_points_colsum_moments", "bcx_linreg_posterior_draw", "bcx_sparsevi_adam_step",
-    "bcx_linreg_posterior_apply", "bcx_linreg_posterior_apply_ok",
-    "bcx_linreg_posterior_factor", "bcx_linreg_posterior_factor_scratch_bytes", "bcx_linreg_posterior_factor_status",
-    "bcx_linreg_posterior_factor_clear_status",
-    "bcx_linreg_posterior_draw_factored",
-    "bcx_sparsevi_adam_step_ws", "bcx_sparsevi_adam_scratch_bytes", "bcx_standard_normal", "bcx_column_means",
-    "bcx_center_rows", "bcx_row_sumsq", "bcx_project_write_points",
-    "bcx_laplace_sampler", "bcx_laplace_sampler_ok", "bcx_laplace_sampler_lds_bytes",
-    "bcx_project_grad_points", "bcx_psvi_gradient", "bcx_psvi_gradient_scratch_bytes",
-    "bcx_gaussian_operand", "bcx_gaussian_first_moment", "bcx_gaussian_first_moment_scratch_bytes", "bcx_gaussian_colsum_moments",
-    "bcx_gaussian_posterior_draw", "bcx_project_grad_points_gaussian", "bcx_psvi_gradient_gaussian",
-    "bcx_psvi_adam_step",
-    "bcx_project_colsum_rows", "bcx_project_select_rows_ws", "bcx_project_select_rows_scratch_bytes", "bcx_gather_rows",
-    "bcx_log_joint_grad", "bcx_log_joint_grad_scratch_bytes", "bcx_hmc_coreset", "bcx_hmc_coreset_ok", "bcx_hmc_coreset_lds_bytes",
-    "bcx_hmc_stream", "bcx_hmc_stream_scratch_bytes",
-    "bcx_nuts_coreset", "bcx_nuts_coreset_ok", "bcx_nuts_coreset_lds_bytes",
-    "bcx_nuts_adapt", "bcx_nuts_adapt_ok", "bcx_nuts_adapt_schedule",
-    "bcx_nuts_batch", "bcx_nuts_batch_table_bytes",
-    "bcx_nuts_stream", "bcx_nuts_stream_scratch_bytes",
-    "bcx_log_predictive", "bcx_log_predictive_scratch_bytes",
-    "bcx_laplace_sampler_stream", "bcx_laplace_stream_scratch_bytes",
-    "bcx_quasi_newton_step", "bcx_quasi_newton_scratch_bytes",
-    "bcx_cmc_advance", "bcx_cmc_advance_ok", "bcx_cmc_advance_lds_bytes", "bcx_cmc_state_bytes",
-    "bcx_pair_stat", "bcx_pair_stat_scratch_bytes",
-)
-
-
-class Config(ctypes.Structure):
-    _fields_ = [
-        ("alg", ctypes.c_int32), ("store_dtype", ctypes.c_int32), ("keep_exact_rows", ctypes.c_int32),
-        ("device", ctypes.c_int32), ("d", ctypes.c_int32), ("world_size", ctypes.c_int32),
-        ("rank", ctypes.c_int32), ("refresh_every", ctypes.c_int32),
-        ("n_local", ctypes.c_int64), ("n_global", ctypes.c_int64), ("row_offset", ctypes.c_int64),
-    ]
-
-
-class NutsProblem(ctypes.Structure):
-    """bcx_nuts_problem (include/bcx.h): one posterior of a bcx_nuts_batch call."""
-    _fields_ = [
-        ("w_dev", ctypes.c_void_p), ("pts_dev", ctypes.c_void_p), ("ldp", ctypes.c_int64),
-        ("mu_dev", ctypes.c_void_p), ("W_dev", ctypes.c_void_p), ("ldw", ctypes.c_int64),
-        ("k", ctypes.c_int32), ("index", ctypes.c_int32),
-    ]
-
+SYMBOLS = tuple(_abi.PROTOTYPES)      # every symbol include/bcx.h declares
+Config, NutsProblem = _abi.STRUCTS["bcx_config"], _abi.STRUCTS["bcx_nuts_problem"]
 
 _lib = None
 
@@ -127,171 +71,9 @@ def load():
         except ImportError:
             pass
     lib = ctypes.CDLL(LIB_PATH)
-    vp, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
-    P = ctypes.POINTER
-    lib.bcx_version.restype = ctypes.c_char_p
-    lib.bcx_last_error.restype = ctypes.c_char_p
-    lib.bcx_last_error.argtypes = [vp]
-    sigs = {
-        "bcx_create": [P(Config), P(vp)],
-        "bcx_destroy": [vp],
-        "bcx_set_stream": [vp, vp],
-        "bcx_load_rows": [vp, vp, i32, i32, i64, i64, i64],
-        "bcx_load_rows_flags": [vp, vp, i32, i32, i64, i64, i64, i32],
-        "bcx_chunk_sums": [vp, P(vp), P(i64), P(i64)],
-        "bcx_export_chunk_sums": [vp, vp, i64],
-        "bcx_finalize": [vp, vp, vp, i64],
-        "bcx_build_begin": [vp, i64, dbl, P(i32)],
-        "bcx_step_scan": [vp, vp],
-        "bcx_step_scan_exact": [vp, vp],
-        "bcx_step_apply": [vp, vp],
-        "bcx_build_enqueue": [vp, i64],
-        "bcx_build_poll": [vp, P(i64), P(i32), P(i32)],
-        "bcx_build_trace": [vp, vp, vp, vp, i64, P(i64)],
-        "bcx_active_count": [vp, P(i64)],
-        "bcx_get_weights": [vp, vp, vp, i64, P(i64)],
-        "bcx_error": [vp, P(dbl)],
-        "bcx_optimize": [vp, dbl, P(i32)],
-        "bcx_reset": [vp],
-        "bcx_set_check_monotone": [vp, i32],
-        "bcx_reached_numeric_limit": [vp, P(i32)],
-        "bcx_get_vector": [vp, i32, vp],
-        "bcx_get_norms": [vp, i64, i64, vp],
-        "bcx_get_stored_rows": [vp, i64, i64, vp, P(i32)],
-        "bcx_argmax_correlation": [vp, vp, P(i64), P(dbl)],
-        "bcx_time_scan": [vp, i32, i32, P(dbl), P(dbl)],
-        "bcx_stats": [vp, P(i64), P(i64), P(i64)],
-        "bcx_omp_stats": [vp, vp],
-        "bcx_screen_stats": [vp, vp],
-        "bcx_screen4_stats": [vp, vp],
-        "bcx_screen_read": [vp, i64, i64, vp, vp, vp, P(i32)],
-        "bcx_screen4_read": [vp, i64, i64, vp, vp, vp, P(i32)],
-        "bcx_screen4_probe": [vp, vp, vp, P(i32), vp, vp, i32, vp],
-        "bcx_profile_scan": [vp, i32],
-        "bcx_profile_read": [vp, P(dbl), P(i64)],
-        "bcx_build_enqueue_exact": [vp],
-        "bcx_exchange_export": [vp, vp, i32],
-        "bcx_exchange_attach": [vp, vp, i32, dbl],
-        "bcx_exchange_probe": [vp, P(i32)],
-        "bcx_exchange_disable": [vp],
-        "bcx_exchange_set_timeout": [vp, dbl],
-        "bcx_exchange_stats": [vp, P(i64), P(dbl), P(dbl), P(dbl), P(dbl), i32],
-    }
-    proj_common = [vp, i32, vp, i64, i64, i32, i32, vp, i32, i32, dbl]
-    sigs["bcx_project_write"] = proj_common + [vp, i64, vp]
-    sigs["bcx_project_write_raw"] = proj_common + [vp, i64]
-    sigs["bcx_project_write_points"] = proj_common + [vp, i64, i32]
-    sigs["bcx_project_colsum"] = proj_common + [vp, vp]
-    sigs["bcx_project_select"] = proj_common + [vp, dbl, vp, vp]
-    sigs["bcx_project_select_ws"] = proj_common + [vp, dbl, vp, vp, i64]
-    sigs["bcx_project_colsum_rows"] = proj_common + [vp, i64, vp, vp]
-    sigs["bcx_project_select_rows_ws"] = proj_common + [vp, i64, vp, dbl, vp, vp, i64]
-    sigs["bcx_gather_rows"] = [vp, vp, i64, i32, vp, i64, vp, i64]
-    sigs["bcx_project_profile"] = [i32]
-    sigs["bcx_project_profile_read"] = [P(dbl), P(i64), P(dbl)]
-    sigs["bcx_project_moments"] = [vp, vp, i64, i64, i32, vp, i64, vp, i64]
-    sigs["bcx_project_colsum_moments"] = [vp, vp, i64, i32, i32, vp, i32, i32, dbl, vp, vp]
-    sigs["bcx_project_colsum_moments_at"] = [vp, vp, i64, i32, i32, vp, i32, i32, dbl, vp, vp, vp]
-    sigs["bcx_project_points_colsum_moments"] = [vp, vp, i64, i64, i32, i32, vp, i32, i32, dbl, vp, i64, vp, i64, i32, vp, vp, vp]
-    sigs["bcx_linreg_posterior_draw"] = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, dbl, vp, vp, i32, vp, vp]
-    sigs["bcx_linreg_posterior_apply"] = [vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, dbl, vp, vp, i32, vp, vp, vp]
-    sigs["bcx_linreg_posterior_apply_ok"] = [i32, i32]
-    sigs["bcx_sparsevi_adam_step"] = [vp, i32, i32, vp, dbl, vp, i64, vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, i32]
-    sigs["bcx_gram"] = [vp, vp, i32, i32, i64, vp, i64, vp, i64]
-    sigs["bcx_gram_check"] = [vp, vp]
-    sigs["bcx_linreg_posterior_factor"] = [vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, dbl, vp, i64, vp, i64, vp, vp]
-    sigs["bcx_linreg_posterior_factor_status"] = [vp, i32, vp]
-    sigs["bcx_linreg_posterior_factor_clear_status"] = [vp, i32, vp]
-    sigs["bcx_standard_normal"] = [vp, ctypes.c_uint64, ctypes.c_uint64, i64, vp]
-    sigs["bcx_column_means"] = [vp, vp, i32, i32, i32, i64, vp, i64]
-    sigs["bcx_center_rows"] = [vp, vp, i64, i32, i64]
-    sigs["bcx_laplace_sampler"] = [vp, i32, i32, i32, vp, vp, i64, vp, i32, dbl, i32, vp, vp, i32, i32, vp, vp, vp]
-    sigs["bcx_laplace_sampler_ok"] = [i32, i32]
-    lib.bcx_laplace_sampler_lds_bytes.restype = ctypes.c_int64
-    lib.bcx_laplace_sampler_lds_bytes.argtypes = [i32, i32]
-    sigs["bcx_laplace_sampler_stream"] = sigs["bcx_laplace_sampler"] + [vp, i64]
-    lib.bcx_laplace_stream_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_laplace_stream_scratch_bytes.argtypes = [i32, i32]
-    sigs["bcx_row_sumsq"] = [vp, vp, i64, i32, i64, vp]
-    sigs["bcx_project_grad_points"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp]
-    sigs["bcx_psvi_gradient"] = [vp, i32, vp, i32, i64, i32, i32, vp, i32, i32, dbl, vp, vp, i64, vp, dbl, vp, vp]
-    sigs["bcx_gaussian_operand"] = [vp, vp, i32, i64, i32, vp, i64, vp, vp, i64, i32, vp]
-    sigs["bcx_gaussian_first_moment"] = [vp, vp, i64, i64, i32, vp, vp, i64]
-    lib.bcx_gaussian_first_moment_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_gaussian_first_moment_scratch_bytes.argtypes = [i64, i32]
-    sigs["bcx_gaussian_colsum_moments"] = [vp, vp, dbl, i32, vp, i32, i64, vp]
-    sigs["bcx_gaussian_posterior_draw"] = [vp, i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, i32, i32, vp, vp, vp, vp]
-    sigs["bcx_project_grad_points_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp]
-    sigs["bcx_psvi_gradient_gaussian"] = [vp, vp, i32, i64, i32, vp, i32, i64, vp, vp, i64, vp, dbl, vp, vp]
-    sigs["bcx_psvi_adam_step"] = [vp, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp, i32, dbl, dbl, dbl, vp, i64, vp, vp]
-    sigs["bcx_log_joint_grad"] = [vp, i32, vp, i64, i64, i32, vp, vp, i32, i32, vp, vp, vp]
-    lib.bcx_log_joint_grad_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_log_joint_grad_scratch_bytes.argtypes = [i64, i32, i32]
-    hmc_common = [vp, vp, i64, i32, i32, i32, i32, dbl, dbl, vp, i32, vp, vp, vp, vp, vp, vp, vp]
-    sigs["bcx_hmc_coreset"] = [vp, i32, i32, i32, vp, vp, i64] + hmc_common
-    sigs["bcx_hmc_stream"] = [vp, i32, i64, i32, vp, vp, i64] + hmc_common + [vp, i64]
-    sigs["bcx_hmc_coreset_ok"] = [i32, i32]
-    lib.bcx_hmc_coreset_lds_bytes.restype = ctypes.c_int64
-    lib.bcx_hmc_coreset_lds_bytes.argtypes = [i32, i32]
-    sigs["bcx_cmc_advance"] = [vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, dbl, i32, i32, i32, vp, vp, vp, i64, i64, vp, i64,
-                               vp, i64, vp, i32, vp, vp, vp, vp, vp]
-    sigs["bcx_cmc_advance_ok"] = [i32, i32]
-    lib.bcx_cmc_advance_lds_bytes.restype = ctypes.c_int64
-    lib.bcx_cmc_advance_lds_bytes.argtypes = [i32, i32]
-    lib.bcx_cmc_state_bytes.restype = ctypes.c_int64
-    lib.bcx_cmc_state_bytes.argtypes = [i32]
-    sigs["bcx_nuts_coreset"] = [vp, i32, i32, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp]
-    sigs["bcx_nuts_coreset_ok"] = [i32, i32]
-    lib.bcx_nuts_coreset_lds_bytes.restype = ctypes.c_int64
-    lib.bcx_nuts_coreset_lds_bytes.argtypes = [i32, i32]
-    sigs["bcx_nuts_adapt"] = sigs["bcx_nuts_coreset"] + [i32, vp, vp]
-    sigs["bcx_nuts_adapt_ok"] = [i32, i32]
-    sigs["bcx_nuts_adapt_schedule"] = [i32, ctypes.POINTER(ctypes.c_int32), i32]
-    sigs["bcx_nuts_batch"] = [vp, i32, i32, ctypes.POINTER(NutsProblem), vp, i32, i32, i32, i32, i32, dbl, vp, i64, i32, vp, vp, vp, vp, vp, vp,
-                              vp, i32, vp, vp]
-    lib.bcx_nuts_batch_table_bytes.restype = ctypes.c_int64
-    lib.bcx_nuts_batch_table_bytes.argtypes = [i32]
-    sigs["bcx_nuts_stream"] = [vp, i32, i64, i32, vp, vp, i64, vp, vp, i64, i32, i32, i32, i32, dbl, dbl, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp,
-                               vp, i64]
-    lib.bcx_nuts_stream_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_nuts_stream_scratch_bytes.argtypes = [i64, i32, i32, i32]
-    sigs["bcx_log_predictive"] = [vp, i32, vp, i64, i64, i32, vp, i64, i64, i32, vp, vp, vp, i64]
-    lib.bcx_log_predictive_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_log_predictive_scratch_bytes.argtypes = [i64, i32, i64, i32]
-    sigs["bcx_pair_stat"] = [vp, i32, vp, i64, i64, vp, i64, vp, i64, i64, vp, i64, i32, dbl, i32, vp, vp, i64]
-    lib.bcx_pair_stat_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_pair_stat_scratch_bytes.argtypes = [i64, i64, i32, i32]
-    lib.bcx_hmc_stream_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_hmc_stream_scratch_bytes.argtypes = [i64, i32, i32]
-    lib.bcx_psvi_gradient_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_psvi_gradient_scratch_bytes.argtypes = [i32, i32]
-    sigs["bcx_linreg_posterior_draw_factored"] = [vp, i32, i32, vp, i64, vp, vp, vp, i32, vp, vp]
-    sigs["bcx_sparsevi_adam_step_ws"] = [vp, i32, i32, vp, dbl, vp, i64, vp, vp, vp, vp, i32, dbl, dbl, dbl, vp, i32, vp, i64]
-    lib.bcx_linreg_posterior_factor_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_linreg_posterior_factor_scratch_bytes.argtypes = [i32]
-    sigs["bcx_quasi_newton_step"] = [vp, i32, i32, vp, dbl, vp, i64, i32, vp, vp, i32, dbl, vp, vp, vp, vp, i64]
-    lib.bcx_quasi_newton_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_quasi_newton_scratch_bytes.argtypes = [i32, i32]
-    lib.bcx_sparsevi_adam_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_sparsevi_adam_scratch_bytes.argtypes = [i32, i32]
-    lib.bcx_gram_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_gram_scratch_bytes.argtypes = [i32, i32]
-    lib.bcx_project_moments_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_project_moments_scratch_bytes.argtypes = [i64, i32]
-    lib.bcx_project_colsum_moments_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_project_colsum_moments_scratch_bytes.argtypes = [i32, i32]
-    lib.bcx_project_select_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_project_select_scratch_bytes.argtypes = [i32, i64, i32]
-    lib.bcx_project_select_rows_scratch_bytes.restype = ctypes.c_int64
-    lib.bcx_project_select_rows_scratch_bytes.argtypes = [i32, i64, i32]
-    lib.bcx_project_last_error.restype = ctypes.c_char_p
-    lib.bcx_project_last_error.argtypes = []
-    for name, args in sigs.items():
-        if name.endswith("_scratch_bytes"):
-            continue
+    for name, (restype, argtypes) in _abi.PROTOTYPES.items():
         fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = ctypes.c_int
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
@@ -300,6 +82,19 @@ class EngineError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("bcx error %d: %s" % (code, msg))
         self.code = code
+
+
+def check(rc):
+    """The status of an entry point that takes no handle: raise with bcx_project_last_error()'s text unless it is 0."""
+    if rc != 0:
+        raise EngineError(rc, load().bcx_project_last_error().decode())
+    return rc
+
+
+def stream_ptr(device):
+    """The HIP stream torch is issuing work on for `device`, as the entry points take it."""
+    import torch
+    return int(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _current_stream_ptr():
@@ -620,7 +415,7 @@ class Engine(object):
         assert got.value == ld4
         return codes, sc, bd
 
-    SCREEN4_MAX_WAVES = 2048      # BCX_SCREEN4_MAX_WAVES of include/bcx.h
+    SCREEN4_MAX_WAVES = SCREEN4_MAX_WAVES
 
     def screen4_probe(self, query, sentinels, list_stride=1024):
         """One launch of the front pass kernel alone against `query` ([d]) and 64 sentinel rows (-1: none).  Returns a dict:
@@ -665,10 +460,7 @@ def device_row_sumsq(rows):
         rows = rows.to(torch.float64).contiguous()
     out = torch.empty(rows.shape[0], dtype=torch.float64, device=rows.device)
     with torch.cuda.device(rows.device):
-        rc = lib.bcx_row_sumsq(int(torch.cuda.current_stream(rows.device).cuda_stream), rows.data_ptr(), rows.shape[0], rows.shape[1],
-                               rows.stride(0), out.data_ptr())
-    if rc != 0:
-        raise EngineError(rc, lib.bcx_project_last_error().decode())
+        check(lib.bcx_row_sumsq(stream_ptr(rows.device), rows.data_ptr(), rows.shape[0], rows.shape[1], rows.stride(0), out.data_ptr()))
     return out.cpu().numpy()
 
 
@@ -679,7 +471,5 @@ def device_centred_copy(rows):
     lib = load()
     out = rows.to(torch.float64).contiguous().clone()
     with torch.cuda.device(out.device):
-        rc = lib.bcx_center_rows(int(torch.cuda.current_stream(out.device).cuda_stream), out.data_ptr(), out.shape[0], out.shape[1], out.stride(0))
-    if rc != 0:
-        raise EngineError(rc, lib.bcx_project_last_error().decode())
+        check(lib.bcx_center_rows(stream_ptr(out.device), out.data_ptr(), out.shape[0], out.shape[1], out.stride(0)))
     return out

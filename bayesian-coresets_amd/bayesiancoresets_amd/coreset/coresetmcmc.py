@@ -175,7 +175,7 @@ class CoresetMCMC(Coreset, _DeviceNormals):
         Z, pts = self._Z, st["pts"]
         ptr = lambda t: None if t is None else t.data_ptr()
         with torch.cuda.device(self.device):
-            stream = int(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = nat.stream_ptr(self.device)
             for i in range(T):
                 Vi, si = (V[i], s[i]) if keep else (V[0], s[0])
                 rc = lib.bcx_cmc_advance(stream, self._fam, M, D, w.data_ptr(), pts.data_ptr(), pts.stride(0), st["mu"].data_ptr(),
@@ -188,8 +188,7 @@ class CoresetMCMC(Coreset, _DeviceNormals):
                     rc = lib.bcx_sparsevi_adam_step_ws(stream, M, K, si.data_ptr(), scaling, Vi.data_ptr(), K, w.data_ptr(), m1.data_ptr(),
                                                        m2.data_ptr(), sched_d.data_ptr(), i, b1, b2, eps, ptr(wtrace), 1, work.data_ptr(),
                                                        work.numel() * 8)
-                if rc != 0:
-                    raise nat.EngineError(rc, lib.bcx_project_last_error().decode())
+                nat.check(rc)
             got = head[:M + 1].cpu().numpy()                                    # the one read-back: weights and status
         out, worst = got[:M].copy(), int(got[M:].view(np.int32)[1])
         st["iteration"] = i0 + T

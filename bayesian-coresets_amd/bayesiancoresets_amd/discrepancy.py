@@ -122,13 +122,11 @@ def _enqueue(torch, lib, kind, A, GA, B, GB, c, splits, out):
         raise ValueError("pair statistic: %d x %d draws, D = %d, splits = %d out of range" % (nA, nB or nA, D, splits))
     work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=A.device)
     with torch.cuda.device(A.device):
-        rc = lib.bcx_pair_stat(int(torch.cuda.current_stream(A.device).cuda_stream), kind, A.data_ptr(), nA, A.stride(0),
-                               GA.data_ptr() if GA is not None else None, GA.stride(0) if GA is not None else D,
-                               B.data_ptr() if B is not None else None, nB, B.stride(0) if B is not None else D,
-                               GB.data_ptr() if GB is not None else None, GB.stride(0) if GB is not None else D,
-                               D, float(c), splits, out.data_ptr(), work.data_ptr(), work.numel() * 8)
-    if rc != 0:
-        raise _native.EngineError(rc, lib.bcx_project_last_error().decode())
+        _native.check(lib.bcx_pair_stat(_native.stream_ptr(A.device), kind, A.data_ptr(), nA, A.stride(0),
+                                        GA.data_ptr() if GA is not None else None, GA.stride(0) if GA is not None else D,
+                                        B.data_ptr() if B is not None else None, nB, B.stride(0) if B is not None else D,
+                                        GB.data_ptr() if GB is not None else None, GB.stride(0) if GB is not None else D,
+                                        D, float(c), splits, out.data_ptr(), work.data_ptr(), work.numel() * 8))
 
 
 def _pair_stat(kind, A, GA=None, B=None, GB=None, c=1.0, splits=0, device="cuda"):

@@ -77,16 +77,13 @@ class GaussianPosteriorSampler(_DeviceNormals):
 
     def _args(self, k, w_dev, p_dev, theta):
         """Argument list of bcx_gaussian_posterior_draw; slots 11 / 12 take the normal numbers and their column means."""
-        stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-        return [stream, k, self.D, w_dev.data_ptr() if k else None, p_dev.data_ptr() if k else None, p_dev.stride(0) if k else 0,
+        return [self._nat.stream_ptr(self.device), k, self.D, w_dev.data_ptr() if k else None, p_dev.data_ptr() if k else None, p_dev.stride(0) if k else 0,
                 self._c0.data_ptr(), None if self._Sig is None else self._Sig.data_ptr(), self._W.data_ptr(), self._WT.data_ptr(),
                 self._lam.data_ptr(), 0, 0, theta.shape[0], self.ld, theta.data_ptr(), self._tbar.data_ptr(), self._state.data_ptr(),
                 self._status.data_ptr()]
 
     def _run(self, a):
-        rc = self._lib.bcx_gaussian_posterior_draw(*a)
-        if rc != 0:
-            raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+        self._nat.check(self._lib.bcx_gaussian_posterior_draw(*a))
 
     def clear_status(self):
         self._status.zero_()

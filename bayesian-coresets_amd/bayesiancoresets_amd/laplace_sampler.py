@@ -104,8 +104,7 @@ class LaplacePosteriorSampler(_DeviceNormals):
 
     def _args(self, k, w_dev, pts_dev, warm, R, rbar, theta, work=None):
         """Argument list of bcx_laplace_sampler, or -- with a scratch buffer -- of bcx_laplace_sampler_stream (``_fn``)."""
-        stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-        a = [stream, self._fam, k, self.D, w_dev.data_ptr() if k else None, pts_dev.data_ptr() if k else None, self.cols,
+        a = [self._nat.stream_ptr(self.device), self._fam, k, self.D, w_dev.data_ptr() if k else None, pts_dev.data_ptr() if k else None, self.cols,
              self._mu.data_ptr(), int(warm), self.tol, self.max_iter, R.data_ptr(), rbar.data_ptr(), theta.shape[0], self.ld,
              theta.data_ptr(), self._tbar.data_ptr(), self._status.data_ptr()]
         if k:
@@ -163,9 +162,7 @@ class LaplacePosteriorSampler(_DeviceNormals):
             if self._work is None or self._work.numel() * 8 < int(self._lib.bcx_laplace_stream_scratch_bytes(k, self.D)):
                 self._work = self._stream_work(k)
             work = self._work
-        rc = self._fn(work)(*self._args(k, w_dev, pts_dev, False, R, self._column_means(R), theta, work))
-        if rc != 0:
-            raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+        self._nat.check(self._fn(work)(*self._args(k, w_dev, pts_dev, False, R, self._column_means(R), theta, work)))
         self.newton_steps = self.check()
         self.mean = self._tbar
         return theta[:, :self.D]
@@ -230,9 +227,7 @@ class _LaplacePlan(object):
             self._b0, self._bstep = self.rbar.data_ptr(), self.rbar.stride(0) * 8
         a[8] = 1 if i > 0 else 0                            # (warm: the mode of the previous ADAM step)
         a[11], a[12] = self._r0 + i * self._rstep, self._b0 + i * self._bstep
-        rc = s._fn(self.work)(*a)
-        if rc != 0:
-            raise s._nat.EngineError(rc, s._lib.bcx_project_last_error().decode())
+        s._nat.check(s._fn(self.work)(*a))
         return self.buffers()
 
     def check(self):

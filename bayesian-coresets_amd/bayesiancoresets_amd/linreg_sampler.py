@@ -31,10 +31,7 @@ class _DeviceNormals(object):
         torch = self._torch
         out = torch.empty(*shape, dtype=torch.float64, device=self.device)
         count = out.numel()
-        rc = self._lib.bcx_standard_normal(int(torch.cuda.current_stream(self.device).cuda_stream), self._seed, self._offset, count,
-                                           out.data_ptr())
-        if rc != 0:
-            raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+        self._nat.check(self._lib.bcx_standard_normal(self._nat.stream_ptr(self.device), self._seed, self._offset, count, out.data_ptr()))
         self._offset += (count + 1) // 2
         return out
 
@@ -52,10 +49,8 @@ class _DeviceNormals(object):
         if blocks.stride(-1) != 1 or blocks.stride(-2) != self.ld or (three and nb > 1 and blocks.stride(0) < n * self.ld):
             blocks = blocks.contiguous()
         out = torch.empty((nb, self.ld) if three else (self.ld,), dtype=torch.float64, device=self.device)
-        rc = self._lib.bcx_column_means(int(torch.cuda.current_stream(self.device).cuda_stream), blocks.data_ptr(), nb, n, self.ld,
-                                        blocks.stride(0) if three else 0, out.data_ptr(), self.ld)
-        if rc != 0:
-            raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+        self._nat.check(self._lib.bcx_column_means(self._nat.stream_ptr(self.device), blocks.data_ptr(), nb, n, self.ld,
+                                                   blocks.stride(0) if three else 0, out.data_ptr(), self.ld))
         return out
 
 
@@ -133,35 +128,29 @@ class LinregPosteriorSampler(_DeviceNormals):
     def _factor_args(self, st, w_dev):
         """Argument list of bcx_linreg_posterior_factor at the points ``st`` and the device-resident weights ``w_dev``."""
         f = self._factor_state()
-        stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-        return [stream, st["k"], self.D, st["ldk"], w_dev.data_ptr(), st["XT"].data_ptr(), st["y"].data_ptr(), f["S0inv"].data_ptr(), self.D,
-                f["rhs0"].data_ptr(), self.sigsq, f["work"].data_ptr(), f["work"].numel() * 8, f["U"].data_ptr(), self.ld,
-                f["u"].data_ptr(), None]                    # (no mean: the draws are U (u + r))
+        return [self._nat.stream_ptr(self.device), st["k"], self.D, st["ldk"], w_dev.data_ptr(), st["XT"].data_ptr(), st["y"].data_ptr(),
+                f["S0inv"].data_ptr(), self.D, f["rhs0"].data_ptr(), self.sigsq, f["work"].data_ptr(), f["work"].numel() * 8,
+                f["U"].data_ptr(), self.ld, f["u"].data_ptr(), None]            # (no mean: the draws are U (u + r))
 
     def _draw_factored_args(self, theta, tbar=None):
         """Argument list of bcx_linreg_posterior_draw_factored (theta = mu_w + R U^T); slots 6 / 7 take the normal numbers and
         their column means."""
         f = self._factor
-        stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-        return [stream, self.D, self.ld, f["U"].data_ptr(), self.ld, f["u"].data_ptr(), 0, 0, theta.shape[0], theta.data_ptr(),
-                (self._tbar if tbar is None else tbar).data_ptr()]
+        return [self._nat.stream_ptr(self.device), self.D, self.ld, f["U"].data_ptr(), self.ld, f["u"].data_ptr(), 0, 0, theta.shape[0],
+                theta.data_ptr(), (self._tbar if tbar is None else tbar).data_ptr()]
 
     def clear_factor_status(self):
         """Enqueues a clear of the factorisations' status word: the next ``factor_status`` covers every factorisation after it."""
-        stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-        rc = self._lib.bcx_linreg_posterior_factor_clear_status(stream, self.D, self._factor_state()["work"].data_ptr())
-        if rc != 0:
-            raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+        self._nat.check(self._lib.bcx_linreg_posterior_factor_clear_status(self._nat.stream_ptr(self.device), self.D,
+                                                                           self._factor_state()["work"].data_ptr()))
 
     def factor_status(self):
         """Synchronises; raises if any factorisation since ``clear_factor_status`` lost its workgroups or met a pivot that was
         not positive (a NaN included: NaN weights or points -- where the reference would go on with NaN draws and weights,
         this is an error)."""
         if self._factor is not None:
-            stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-            rc = self._lib.bcx_linreg_posterior_factor_status(stream, self.D, self._factor["work"].data_ptr())
-            if rc != 0:
-                raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+            self._nat.check(self._lib.bcx_linreg_posterior_factor_status(self._nat.stream_ptr(self.device), self.D,
+                                                                         self._factor["work"].data_ptr()))
 
     def _points(self, pts):
         """Device block [K0 (k x k) | X mu0 (k) | y (k) | X U0 (k x ld) | X Sig0 (k x ld)] of the points ``pts`` (k x (D+1))."""
@@ -206,13 +195,10 @@ class LinregPosteriorSampler(_DeviceNormals):
         theta = mu0 + R U0T -- the D x D form passes L^-1 and mu_w)."""
         k = st["k"] if st is not None else 0
         lib, dp = self._lib, (lambda key: st[key].data_ptr() if k else None)
-        stream = int(self._torch.cuda.current_stream(self.device).cuda_stream)
-        rc = lib.bcx_linreg_posterior_draw(stream, k, self.D, self.ld, w_dev.data_ptr() if k else None, dp("K0"), dp("xmu0"), dp("y"),
-                                           dp("XU0"), dp("XS0"), (self._U0T if U0T is None else U0T).data_ptr(), (self._mu0 if mu0 is None else mu0).data_ptr(),
-                                           self.sigsq, R.data_ptr(), rbar.data_ptr(), R.shape[0], theta.data_ptr(),
-                                           (self._tbar if tbar is None else tbar).data_ptr())
-        if rc != 0:
-            raise self._nat.EngineError(rc, lib.bcx_project_last_error().decode())
+        self._nat.check(lib.bcx_linreg_posterior_draw(
+            self._nat.stream_ptr(self.device), k, self.D, self.ld, w_dev.data_ptr() if k else None, dp("K0"), dp("xmu0"), dp("y"),
+            dp("XU0"), dp("XS0"), (self._U0T if U0T is None else U0T).data_ptr(), (self._mu0 if mu0 is None else mu0).data_ptr(),
+            self.sigsq, R.data_ptr(), rbar.data_ptr(), R.shape[0], theta.data_ptr(), (self._tbar if tbar is None else tbar).data_ptr()))
 
     def _theta_buf(self, n):
         t = self._theta.get(n)
@@ -237,15 +223,11 @@ class LinregPosteriorSampler(_DeviceNormals):
         R = self._noise(n)
         if k and not st["low_rank"]:
             self.clear_factor_status()
-            rc = self._lib.bcx_linreg_posterior_factor(*self._factor_args(st, w_dev))
-            if rc != 0:
-                raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+            self._nat.check(self._lib.bcx_linreg_posterior_factor(*self._factor_args(st, w_dev)))
             a = self._draw_factored_args(theta)
             rbar = self._column_means(R)
             a[6], a[7] = R.data_ptr(), rbar.data_ptr()
-            rc = self._lib.bcx_linreg_posterior_draw_factored(*a)
-            if rc != 0:
-                raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+            self._nat.check(self._lib.bcx_linreg_posterior_draw_factored(*a))
             self.factor_status()
         else:
             self._launch(st, w_dev, R, self._column_means(R), theta)
@@ -344,7 +326,7 @@ class _Plan(object):
         if a is None or self._w_ptr != w_dev.data_ptr():
             # the argument lists, built once: per step only the two pointers into the noise (or its image) move
             s, st = self.s, self.st
-            stream = int(s._torch.cuda.current_stream(s.device).cuda_stream)
+            stream = s._nat.stream_ptr(s.device)
             self._w_ptr, self._pre = w_dev.data_ptr(), None
             if self.fast:
                 a = [stream, st["k"], s.D, s.ld, w_dev.data_ptr(), st["K0"].data_ptr(), st["xmu0"].data_ptr(), st["y"].data_ptr(),
@@ -368,13 +350,9 @@ class _Plan(object):
             self._b0, self._bstep = means.data_ptr(), means.stride(0) * 8
             self._args = a
         if self._pre is not None:
-            rc = self._pre[0](*self._pre[1])
-            if rc != 0:
-                raise self.s._nat.EngineError(rc, self.s._lib.bcx_project_last_error().decode())
+            self.s._nat.check(self._pre[0](*self._pre[1]))
         a[self._at[0]], a[self._at[1]] = self._r0 + i * self._rstep, self._b0 + i * self._bstep
-        rc = self._fn(*a)
-        if rc != 0:
-            raise self.s._nat.EngineError(rc, self.s._lib.bcx_project_last_error().decode())
+        self.s._nat.check(self._fn(*a))
         return self.buffers()
 
     def check(self):

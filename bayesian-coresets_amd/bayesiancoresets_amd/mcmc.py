@@ -143,11 +143,9 @@ def log_joint_grad(family, pts, wts, thetas, device="cuda"):
     grad = torch.empty(C, D, dtype=torch.float64, device=device)
     work = torch.empty(max(int(lib.bcx_log_joint_grad_scratch_bytes(N, D, C)), 8) // 8, dtype=torch.float64, device=device)
     with torch.cuda.device(device):
-        rc = lib.bcx_log_joint_grad(int(torch.cuda.current_stream(device).cuda_stream), FAMILIES[family], Z.data_ptr() if N else None, N,
-                                    Z.stride(0) if N else cols, D, w.data_ptr() if w is not None else None, th.data_ptr(), C, D,
-                                    value.data_ptr(), grad.data_ptr(), work.data_ptr())
-    if rc != 0:
-        raise _native.EngineError(rc, lib.bcx_project_last_error().decode())
+        _native.check(lib.bcx_log_joint_grad(_native.stream_ptr(device), FAMILIES[family], Z.data_ptr() if N else None, N,
+                                             Z.stride(0) if N else cols, D, w.data_ptr() if w is not None else None, th.data_ptr(), C, D,
+                                             value.data_ptr(), grad.data_ptr(), work.data_ptr()))
     if as_tensor:
         return value, grad
     return value.cpu().numpy(), grad.cpu().numpy()
@@ -298,7 +296,7 @@ class DeviceHMC(_DeviceNormals):
                     list(scratch))
 
         with torch.cuda.device(self.device):
-            stream = int(torch.cuda.current_stream(self.device).cuda_stream)
+            stream = self._nat.stream_ptr(self.device)
             torch.cuda.synchronize(self.device)
             t0 = time.perf_counter()
             if nuts_streamed:
@@ -316,8 +314,7 @@ class DeviceHMC(_DeviceNormals):
                 rc = lib.bcx_hmc_stream(*native_args(stream, work.data_ptr(), nbytes))
             else:
                 rc = lib.bcx_hmc_coreset(*native_args(stream))
-            if rc != 0:
-                raise self._nat.EngineError(rc, lib.bcx_project_last_error().decode())
+            self._nat.check(rc)
             torch.cuda.synchronize(self.device)
             seconds = time.perf_counter() - t0
         st = self._status.cpu().numpy()
@@ -426,12 +423,10 @@ class DeviceHMC(_DeviceNormals):
         noise = torch.empty(P, C, T, R, **f64)
         pairs = (C * T * R + 1) // 2
         with torch.cuda.device(self.device):
-            stream = int(torch.cuda.current_stream(self.device).cuda_stream)
-            for p in range(P):      # (the _normal(C, T, R) call of the p-th sample, into its slice)
+            stream = nat.stream_ptr(self.device)
+            for p in range(P):     # (the _normal(C, T, R) call of the p-th sample, into its slice)
                 seed, offset = (self._seed, self._offset + p * pairs) if seeds is None else (int(seeds[p]) & 0xFFFFFFFFFFFFFFFF, 0)
-                rc = lib.bcx_standard_normal(stream, seed, offset, C * T * R, noise[p].data_ptr())
-                if rc != 0:
-                    raise nat.EngineError(rc, lib.bcx_project_last_error().decode())
+                nat.check(lib.bcx_standard_normal(stream, seed, offset, C * T * R, noise[p].data_ptr()))
             if seeds is None:
                 self._offset += P * pairs
             samples = torch.empty(P, C, T, ld, **f64)
@@ -447,11 +442,10 @@ class DeviceHMC(_DeviceNormals):
             ptr = lambda t: None if t is None else t.data_ptr()
             torch.cuda.synchronize(self.device)
             t0 = time.perf_counter()
-            rc = lib.bcx_nuts_batch(stream, self._fam, P, records, table.data_ptr(), D, C, n_warmup, n_samples, self.max_depth, self.STEP0,
-                                    noise.data_ptr(), R, ld, samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(),
-                                    eps.data_ptr(), status.data_ptr(), NUTS_METRICS[self.adapt_metric] if adapt else 0, ptr(frames), ptr(metric))
-            if rc != 0:
-                raise nat.EngineError(rc, lib.bcx_project_last_error().decode())
+            nat.check(lib.bcx_nuts_batch(stream, self._fam, P, records, table.data_ptr(), D, C, n_warmup, n_samples, self.max_depth, self.STEP0,
+                                         noise.data_ptr(), R, ld, samples.data_ptr(), ptr(xis), ptr(props), diag.data_ptr(), acc.data_ptr(),
+                                         eps.data_ptr(), status.data_ptr(), NUTS_METRICS[self.adapt_metric] if adapt else 0, ptr(frames),
+                                         ptr(metric)))
             torch.cuda.synchronize(self.device)
             seconds = time.perf_counter() - t0
         del keep

@@ -60,10 +60,8 @@ def log_predictive(family, pts, samples, device="cuda", *, _dev_splits=0):
         nbytes = int(lib.bcx_log_predictive_scratch_bytes(N, D, S, splits))
         work = torch.empty(max(nbytes, 8) // 8, dtype=torch.float64, device=device)
         with torch.cuda.device(device):
-            rc = lib.bcx_log_predictive(int(torch.cuda.current_stream(device).cuda_stream), FAMILIES[family], Z.data_ptr(), N, Z.stride(0),
-                                        D, th.data_ptr(), S, D, splits, lppd.data_ptr(), mean.data_ptr(), work.data_ptr(), work.numel() * 8)
-        if rc != 0:
-            raise _native.EngineError(rc, lib.bcx_project_last_error().decode())
+            _native.check(lib.bcx_log_predictive(_native.stream_ptr(device), FAMILIES[family], Z.data_ptr(), N, Z.stride(0), D, th.data_ptr(),
+                                                 S, D, splits, lppd.data_ptr(), mean.data_ptr(), work.data_ptr(), work.numel() * 8))
     elif pts is not None and np.ndim(pts) == 2 and np.shape(pts)[1] != cols:
         raise ValueError("points have %d columns, the model takes %d" % (np.shape(pts)[1], cols))
     elpd = float(lppd.sum().item()) if N else 0.0

@@ -123,11 +123,10 @@ class DeviceProjector(Projector):
 
     # -- plumbing -----------------------------------------------------------
     def _stream(self):
-        return int(self._torch.cuda.current_stream(self.device).cuda_stream)
+        return self._nat.stream_ptr(self.device)
 
     def _check(self, rc):
-        if rc != 0:
-            raise self._nat.EngineError(rc, self._lib.bcx_project_last_error().decode())
+        self._nat.check(rc)
 
     # -- measurement: hipEvents around the projection kernel alone (csrc/proj.hip, bcx_project_profile) ------
     def profile(self, on):

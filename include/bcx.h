@@ -14,6 +14,12 @@
  * outputs are caller-allocated HOST buffers unless a parameter says "dev";
  * device pointers are passed as const void* (from torch.Tensor.data_ptr()).
  * One host thread per handle.
+ *
+ * The Python binding (bayesiancoresets_amd/_abi.py) PARSES THIS FILE at import -- signatures, constants and the two structs are
+ * written down here only -- and refuses to load a declaration outside this grammar: one prototype per `;` with every parameter
+ * named; parameters int32_t, int64_t, uint64_t, double or a pointer (any pointer is passed as an address), `(void)` for none;
+ * returns int, int32_t, int64_t or const char*; struct fields of the same types; anonymous enums with an explicit value for
+ * every name; `#define BCX_NAME <integer>`.  No arrays, function pointers or structs by value.
  */
 #ifndef BCX_H
 #define BCX_H

@@ -24,8 +24,9 @@ def test_binding():
     lib = _native.load()
     vp, i32, i64, dbl = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
     single = list(lib.bcx_nuts_adapt.argtypes)
-    # bcx_nuts_adapt's arguments with the problem's own (k, weights, rows, frame) in the records and no fixed_eps
-    assert list(lib.bcx_nuts_batch.argtypes) == [vp, i32, i32, ctypes.POINTER(_native.NutsProblem), vp, i32] + single[10:15] + single[16:]
+    # bcx_nuts_adapt's arguments with the problem's own (k, weights, rows, frame) in the records (their array: an address, as every
+    # pointer of the header) and no fixed_eps
+    assert list(lib.bcx_nuts_batch.argtypes) == [vp, i32, i32, vp, vp, i32] + single[10:15] + single[16:]
     assert single[15] is dbl and single[2] is i32 and single[6] is i64
     assert lib.bcx_nuts_batch.restype is ctypes.c_int
 
