@@ -8,6 +8,7 @@
 #include <vector>
 #include "../../include/bcx.h"
 #include "dev_buf.h"
+#include "host_err.h"
 
 #define BCX_CHUNK_ROWS 1024      // rows per column-sum chunk (fixed summation tree, shard-count independent)
 #define BCX_MAX_CAND 64          // candidate rows re-scored in fp64 per shard per iteration
@@ -281,8 +282,6 @@ bool bcx_screen4_on(const bcx_solver* s);
 int bcx_screen4_build(bcx_solver* s);
 int bcx_launch_screen4(bcx_solver* s);
 int bcx_launch_front4_probe(bcx_solver* s, int* n_waves);   // front4_kernel alone, the plan of bcx_launch_screen4 (bcx_screen4_probe)
-// proj.hip: sets the message bcx_project_last_error() returns (the entry points outside the solver report through it)
-void bcx_project_set_error(const std::string& msg);
 // proj.hip: the likelihood tables of proj_math.h (PJT_DOUBLES doubles) in the current device's memory; nullptr: no memory
 const double* proj_tables();
 

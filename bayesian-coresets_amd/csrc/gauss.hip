@@ -17,21 +17,9 @@
 #include <string>
 #include "bcx_internal.h"
 #include "dev_util.h"
+#include "launch_host.h"
 
 
-#define GS_HIP(call)                                                              \
-  do {                                                                            \
-    hipError_t _e = (call);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      bcx_project_set_error(std::string(#call) + ": " + hipGetErrorString(_e));   \
-      return BCX_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
-
-static int gs_arg_error(const char* who, const char* what) {
-  bcx_project_set_error(std::string(who) + ": " + what);
-  return BCX_ERR_ARG;
-}
 
 #define GS_MAX_DIM 4096       // coordinates (the operand kernel keeps one row in LDS)
 
@@ -72,10 +60,10 @@ __global__ __launch_bounds__(256) void gauss_operand_kernel(const double* __rest
 extern "C" int bcx_gaussian_operand(void* stream, const void* rows_dev, int32_t n, int64_t ldx, int32_t D, const void* Siginv_dev,
                                     int64_t ldsig, const void* tbar_dev, void* out_dev, int64_t ldo, int32_t mode, void* work_dev) {
   static const char* who = "bcx_gaussian_operand";
-  if (!rows_dev || !out_dev || n < 0 || D < 1 || D > GS_MAX_DIM || ldx < D || ldo < D + 1) return gs_arg_error(who, "bad arguments (1 <= D <= 4096, ldo >= D + 1)");
-  if (Siginv_dev && ldsig < D) return gs_arg_error(who, "Siginv leading dimension shorter than D");
-  if (mode != 0 && mode != 1) return gs_arg_error(who, "mode must be 0 (draws: bias) or 1 (points: coordinate mean)");
-  if (!tbar_dev && !work_dev) return gs_arg_error(who, "without tbar_dev the mean of the rows is formed in work_dev (D doubles)");
+  if (!rows_dev || !out_dev || n < 0 || D < 1 || D > GS_MAX_DIM || ldx < D || ldo < D + 1) return bcx_fail(BCX_ERR_ARG, who, "bad arguments (1 <= D <= 4096, ldo >= D + 1)");
+  if (Siginv_dev && ldsig < D) return bcx_fail(BCX_ERR_ARG, who, "Siginv leading dimension shorter than D");
+  if (mode != 0 && mode != 1) return bcx_fail(BCX_ERR_ARG, who, "mode must be 0 (draws: bias) or 1 (points: coordinate mean)");
+  if (!tbar_dev && !work_dev) return bcx_fail(BCX_ERR_ARG, who, "without tbar_dev the mean of the rows is formed in work_dev (D doubles)");
   if (n == 0) return BCX_OK;
   hipStream_t st = (hipStream_t)stream;
   const double* tbar = (const double*)tbar_dev;
@@ -90,7 +78,7 @@ extern "C" int bcx_gaussian_operand(void* stream, const void* rows_dev, int32_t 
   else
     hipLaunchKernelGGL(gauss_operand_kernel<false>, dim3(n), dim3(256), lds, st, (const double*)rows_dev, ldx, (int)D, (const double*)Siginv_dev,
                        ldsig, tbar, (double*)out_dev, ldo);
-  GS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -133,15 +121,15 @@ extern "C" int64_t bcx_gaussian_first_moment_scratch_bytes(int64_t N, int32_t D)
 extern "C" int bcx_gaussian_first_moment(void* stream, const void* Z_dev, int64_t N, int64_t ldz, int32_t D, void* xsum_dev, void* work_dev,
                                          int64_t work_bytes) {
   static const char* who = "bcx_gaussian_first_moment";
-  if (!Z_dev || !xsum_dev || !work_dev || N < 0 || D < 1 || ldz < D) return gs_arg_error(who, "bad arguments");
-  if (work_bytes < bcx_gaussian_first_moment_scratch_bytes(N, D)) return gs_arg_error(who, "scratch too small");
+  if (!Z_dev || !xsum_dev || !work_dev || N < 0 || D < 1 || ldz < D) return bcx_fail(BCX_ERR_ARG, who, "bad arguments");
+  if (work_bytes < bcx_gaussian_first_moment_scratch_bytes(N, D)) return bcx_fail(BCX_ERR_ARG, who, "scratch too small");
   hipStream_t st = (hipStream_t)stream;
   const int64_t R = gs_slab_rows(N);
   const int slabs = (int)(N ? (N + R - 1) / R : 0);
   if (slabs)
     hipLaunchKernelGGL(gauss_xsum_part_kernel, dim3(slabs), dim3(256), 0, st, (const double*)Z_dev, N, ldz, (int)D, R, (double*)work_dev);
   hipLaunchKernelGGL(gauss_xsum_reduce_kernel, dim3((D + 255) / 256), dim3(256), 0, st, (const double*)work_dev, slabs, (int)D, (double*)xsum_dev);
-  GS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -168,12 +156,12 @@ __global__ __launch_bounds__(256) void gauss_center_kernel(int S, double* __rest
 extern "C" int bcx_gaussian_colsum_moments(void* stream, const void* xsum_dev, double n_rows, int32_t D, const void* operand_dev, int32_t S,
                                            int64_t ldt, void* colsum_dev) {
   static const char* who = "bcx_gaussian_colsum_moments";
-  if (!xsum_dev || !operand_dev || !colsum_dev || D < 1 || S < 1 || ldt < D + 1) return gs_arg_error(who, "bad arguments (ldt >= D + 1)");
+  if (!xsum_dev || !operand_dev || !colsum_dev || D < 1 || S < 1 || ldt < D + 1) return bcx_fail(BCX_ERR_ARG, who, "bad arguments (ldt >= D + 1)");
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(gauss_colsum_kernel, dim3((S + 3) / 4), dim3(256), 0, st, (const double*)xsum_dev, n_rows, (int)D, (const double*)operand_dev,
                      (int)S, ldt, (double*)colsum_dev);
   hipLaunchKernelGGL(gauss_center_kernel, dim3(1), dim3(256), 0, st, (int)S, (double*)colsum_dev);
-  GS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -280,10 +268,10 @@ extern "C" int bcx_gaussian_posterior_draw(void* stream, int32_t k, int32_t D, c
                                            const void* lam_dev, const void* R_dev, const void* Rbar_dev, int32_t S, int32_t ld,
                                            void* theta_dev, void* tbar_dev, void* state_dev, void* status_dev) {
   static const char* who = "bcx_gaussian_posterior_draw";
-  if (k < 0 || D < 1 || D > GPS_MAX_DIM || S < 1 || ld < D) return gs_arg_error(who, "bad sizes (1 <= D <= 1024, ld >= D)");
-  if (k > 0 && (!w_dev || !pts_dev || ldp < D)) return gs_arg_error(who, "weights and points required for k > 0 (ldp >= D)");
+  if (k < 0 || D < 1 || D > GPS_MAX_DIM || S < 1 || ld < D) return bcx_fail(BCX_ERR_ARG, who, "bad sizes (1 <= D <= 1024, ld >= D)");
+  if (k > 0 && (!w_dev || !pts_dev || ldp < D)) return bcx_fail(BCX_ERR_ARG, who, "weights and points required for k > 0 (ldp >= D)");
   if (!c0_dev || !W_dev || !WT_dev || !lam_dev || !R_dev || !Rbar_dev || !theta_dev || !tbar_dev || !state_dev || !status_dev)
-    return gs_arg_error(who, "null pointer");
+    return bcx_fail(BCX_ERR_ARG, who, "null pointer");
   GpsArgs a;
   a.k = k; a.D = D; a.S = S; a.ld = ld; a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.ldp = ldp;
   a.c0 = (const double*)c0_dev; a.Sig = (const double*)Siginv_dev; a.W = (const double*)W_dev; a.WT = (const double*)WT_dev;
@@ -292,6 +280,6 @@ extern "C" int bcx_gaussian_posterior_draw(void* stream, int32_t k, int32_t D, c
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(gps_prep_kernel, dim3(1), dim3(256), 0, st, a);
   hipLaunchKernelGGL(gps_draw_kernel, dim3((D + 63) / 64, (S + 1 + 15) / 16), dim3(256), 0, st, a);
-  GS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }

@@ -33,6 +33,7 @@
 #include <chrono>
 #include "bcx_internal.h"
 #include "dev_util.h"
+#include "launch_host.h"
 
 typedef double gk4d __attribute__((ext_vector_type(4)));
 typedef double gk2d __attribute__((ext_vector_type(2)));
@@ -453,19 +454,18 @@ struct GramSkPlan { int ntb, nI, nJ, ntiles, nst, wgs; };
 // Resident workgroups of the kernel on the CURRENT device (the function attribute and the CU count are per device: a process
 // that drives several GPUs gets each one's own figure).
 template <int NTB> static int gk_resident_wgs() {
-  static std::atomic<int> cache[64];                   // 0: not yet asked on that device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  int n = cache[dev].load(std::memory_order_acquire);
+  static PerDevice<int> cache;                         // 0: not yet asked on that device
+  const int dev = device_slot_or_zero();
+  int n = cache.of[dev].load(std::memory_order_acquire);
   if (n > 0) return n;
-  int cus = 256, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  int per_cu = 0;
   (void)hipFuncSetAttribute((const void*)gram_sk_kernel<NTB>, hipFuncAttributeMaxDynamicSharedMemorySize, GK_LDS_BYTES(NTB));
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)gram_sk_kernel<NTB>, 256, GK_LDS_BYTES(NTB)) != hipSuccess || per_cu < 1)
     per_cu = 1;
+  (void)hipGetLastError();                             // (neither query's failure is the next entry point's)
   if (per_cu > 2) per_cu = 2;
-  n = std::max(8, cus * per_cu / 8 * 8);
-  cache[dev].store(n, std::memory_order_release);
+  n = std::max(8, cu_count() * per_cu / 8 * 8);
+  cache.of[dev].store(n, std::memory_order_release);
   return n;
 }
 
@@ -507,12 +507,13 @@ static unsigned long long gram_next_epoch() { return gram_epoch_counter().fetch_
 unsigned long long bcx_gram_sk_epoch_now() { return gram_epoch_counter().load(); }
 // Did a workgroup of a call numbered after `since` that used the scratch `work` give up waiting for a peer's partial tile
 // (the GPU shared with another process, preemption, fewer resident workgroups than planned)?  Its G is then not valid.
-// Synchronises the stream.  1: yes, 0: no, < 0: HIP error.  (Differences, not magnitudes: the counter starts from the clock
-// and may wrap; stale contents of the scratch fall outside the few numbers issued since.)
+// Synchronises the stream.  1: yes, 0: no, < 0: HIP error (bcx_project_last_error() has the text).  (Differences, not
+// magnitudes: the counter starts from the clock and may wrap; stale contents of the scratch fall outside the few numbers
+// issued since.)
 int bcx_gram_sk_timed_out(hipStream_t st, const double* work, unsigned long long since) {
   unsigned long long v = 0;
-  if (hipMemcpyAsync(&v, work, sizeof v, hipMemcpyDeviceToHost, st) != hipSuccess) return BCX_ERR_HIP;
-  if (hipStreamSynchronize(st) != hipSuccess) return BCX_ERR_HIP;
+  BCX_TRY("bcx_gram", hipMemcpyAsync(&v, work, sizeof v, hipMemcpyDeviceToHost, st));
+  BCX_TRY("bcx_gram", hipStreamSynchronize(st));
   if (since == 0) since = gram_epoch0;
   const unsigned long long age = v - since, span = gram_epoch_counter().load() - since;
   return age != 0 && age <= span ? 1 : 0;
@@ -534,5 +535,6 @@ int bcx_gram_sk(hipStream_t st, const double* rows, int k, int d, int64_t ld, do
   a.timeout_ticks = 500000000LL;                    // 5 s of the 100 MHz wall clock
   if (pl.ntb == 4) hipLaunchKernelGGL(gram_sk_kernel<4>, dim3(pl.wgs), dim3(256), GK_LDS_BYTES(4), st, a);
   else hipLaunchKernelGGL(gram_sk_kernel<2>, dim3(pl.wgs), dim3(256), GK_LDS_BYTES(2), st, a);
-  return hipGetLastError() == hipSuccess ? BCX_OK : BCX_ERR_HIP;
+  BCX_TRY("bcx_gram", hipGetLastError());
+  return BCX_OK;
 }

@@ -149,11 +149,9 @@ extern "C" int64_t bcx_log_joint_grad_scratch_bytes(int64_t N, int32_t D, int32_
 extern "C" int bcx_log_joint_grad(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D, const void* w_dev,
                                   const void* Theta_dev, int32_t C, int32_t ldt, void* value_dev, void* grad_dev, void* work_dev) {
   if ((family != LAP_LOGISTIC && family != LAP_POISSON) || N < 0 || D < 1 || D > HMC_DMAX || C < 1 || ldt < D || !Theta_dev || !value_dev ||
-      !grad_dev || !work_dev || (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0)))) {
-    bcx_project_set_error("bcx_log_joint_grad: bad arguments (family 0 logistic / 1 Poisson, D <= 32, ldt >= D, work_dev of "
-                          "bcx_log_joint_grad_scratch_bytes)");
-    return BCX_ERR_ARG;
-  }
+      !grad_dev || !work_dev || (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_log_joint_grad", "bad arguments (family 0 logistic / 1 Poisson, D <= 32, ldt >= D, work_dev of "
+                                                       "bcx_log_joint_grad_scratch_bytes)");
   hipStream_t st = (hipStream_t)stream;
   for (int c0 = 0; c0 < C; c0 += LJ_CCHUNK) {
     const int cc = C - c0 < LJ_CCHUNK ? C - c0 : LJ_CCHUNK;
@@ -162,7 +160,7 @@ extern "C" int bcx_log_joint_grad(void* stream, int32_t family, const void* Z_de
     hipLaunchKernelGGL(lj_finalize_kernel, dim3((unsigned)(((int64_t)cc * (D + 1) + 255) / 256)), dim3(256), 0, st, (const double*)work_dev, nwg,
                        th, cc, (int)D, (int)ldt, (double*)value_dev + c0, (double*)grad_dev + (size_t)c0 * ldt);
   }
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_log_joint_grad: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_log_joint_grad", hipGetLastError());
   return BCX_OK;
 }
 
@@ -299,11 +297,9 @@ extern "C" int bcx_hmc_coreset(void* stream, int32_t family, int32_t k, int32_t 
                                void* xi_dev, void* prop_dev, void* diag_dev, void* accept_dev, void* eps_dev, void* status_dev) {
   if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
       leapfrog < 1 || !bcx_hmc_coreset_ok(k, D) || (W_dev && ldw < D) ||
-      (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0)))) {
-    bcx_project_set_error("bcx_hmc_coreset: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, the points within "
-                          "bcx_hmc_coreset_ok, at least one transition and leapfrog step, eps0 > 0)");
-    return BCX_ERR_ARG;
-  }
+      (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_hmc_coreset", "bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, the points within "
+                                                    "bcx_hmc_coreset_ok, at least one transition and leapfrog step, eps0 > 0)");
   HmcCoresetArgs a;
   a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, leapfrog, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev, prop_dev,
                   diag_dev, accept_dev, eps_dev, status_dev);
@@ -311,13 +307,10 @@ extern "C" int bcx_hmc_coreset(void* stream, int32_t family, int32_t k, int32_t 
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)bcx_hmc_coreset_lds_bytes(k, D);
   static PerDevice<size_t> lds_max;
-  if (raise_dynamic_lds((const void*)hmc_coreset_kernel, lds, 16 * 1024, lds_max) != hipSuccess) {
-    bcx_project_set_error("bcx_hmc_coreset: hipFuncSetAttribute failed");
-    return BCX_ERR_HIP;
-  }
-  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_hmc_coreset: memset failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_hmc_coreset", raise_dynamic_lds((const void*)hmc_coreset_kernel, lds, 16 * 1024, lds_max));
+  BCX_TRY("bcx_hmc_coreset", hipMemsetAsync(status_dev, 0, sizeof(int), st));
   hipLaunchKernelGGL(hmc_coreset_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_hmc_coreset: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_hmc_coreset", hipGetLastError());
   return BCX_OK;
 }
 
@@ -435,12 +428,10 @@ extern "C" int bcx_cmc_advance(void* stream, int32_t family, int32_t k, int32_t 
       !(eps0 > 0.0) || first_transition < 0 || (int64_t)first_transition + thin > INT32_MAX || n_adapt_transitions < 0 || ld < D || ld > 32 ||
       !bcx_cmc_advance_ok(k, D) || !w_dev || !pts_dev || ldp < cols || (W_dev && ldw < D) || !noise_dev || !state_dev || N < 1 || !Z_dev ||
       ldz < cols || (rows_dev ? n_rows < 1 : n_rows != 0) || !core_dev || ldc < chains || !colsum_dev || !samples_dev || !diag_dev ||
-      !status_dev) {
-    bcx_project_set_error("bcx_cmc_advance: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, 1 <= k <= 4096 points within "
-                          "bcx_cmc_advance_ok, at most 8192 chains, ldc >= chains, at least one transition and leapfrog step, eps0 > 0, "
-                          "n_rows 0 without rows_dev)");
-    return BCX_ERR_ARG;
-  }
+      !status_dev)
+    return bcx_fail(BCX_ERR_ARG, "bcx_cmc_advance", "bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, 1 <= k <= 4096 points within "
+                                                    "bcx_cmc_advance_ok, at most 8192 chains, ldc >= chains, at least one transition and leapfrog step, eps0 > 0, "
+                                                    "n_rows 0 without rows_dev)");
   CmcArgs a;
   a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_adapt_transitions, 0, leapfrog, eps0, 0.0, noise_dev, ld, samples_dev, xi_dev, prop_dev,
                   diag_dev, nullptr, nullptr, status_dev);
@@ -451,14 +442,11 @@ extern "C" int bcx_cmc_advance(void* stream, int32_t family, int32_t k, int32_t 
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)bcx_cmc_advance_lds_bytes(k, D);
   static PerDevice<size_t> lds_max;
-  if (raise_dynamic_lds((const void*)cmc_advance_kernel, lds, 16 * 1024, lds_max) != hipSuccess) {
-    bcx_project_set_error("bcx_cmc_advance: hipFuncSetAttribute failed");
-    return BCX_ERR_HIP;
-  }
-  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_cmc_advance: memset failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_cmc_advance", raise_dynamic_lds((const void*)cmc_advance_kernel, lds, 16 * 1024, lds_max));
+  BCX_TRY("bcx_cmc_advance", hipMemsetAsync(status_dev, 0, sizeof(int), st));
   hipLaunchKernelGGL(cmc_advance_kernel, dim3(chains), dim3(HMC_THREADS), lds, st, a);
   hipLaunchKernelGGL(cmc_centre_kernel, dim3(1), dim3(256), 0, st, (double*)colsum_dev, (int)chains);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_cmc_advance: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_cmc_advance", hipGetLastError());
   return BCX_OK;
 }
 
@@ -518,18 +506,16 @@ extern "C" int bcx_hmc_stream(void* stream, int32_t family, int64_t N, int32_t D
                               int64_t work_bytes) {
   if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
       leapfrog < 1 || chains > HMC_STREAM_CMAX || N < 0 || (W_dev && ldw < D) || !work_dev ||
-      work_bytes < bcx_hmc_stream_scratch_bytes(N, D, chains) || (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0)))) {
-    bcx_project_set_error("bcx_hmc_stream: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, at most 256 chains, work_dev of "
-                          "bcx_hmc_stream_scratch_bytes, at least one transition and leapfrog step, eps0 > 0)");
-    return BCX_ERR_ARG;
-  }
+      work_bytes < bcx_hmc_stream_scratch_bytes(N, D, chains) || (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_hmc_stream", "bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, at most 256 chains, work_dev of "
+                                                   "bcx_hmc_stream_scratch_bytes, at least one transition and leapfrog step, eps0 > 0)");
   const HmcPar p = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, leapfrog, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev,
                            prop_dev, diag_dev, accept_dev, eps_dev, status_dev);
   hipStream_t st = (hipStream_t)stream;
   HmcChain* state = (HmcChain*)work_dev;
   double* Theta = (double*)((char*)work_dev + (size_t)chains * sizeof(HmcChain));
   double* part = (double*)((char*)work_dev + hmc_stream_part_offset(chains));
-  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_hmc_stream: memset failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_hmc_stream", hipMemsetAsync(status_dev, 0, sizeof(int), st));
   hipLaunchKernelGGL(hmc_stream_start_kernel, dim3(chains), dim3(HMC_STEP_THREADS), 0, st, (const double*)mu_dev, (int)D, Theta);
   auto pass_and_step = [&](int phase, int t) {
     const int nwg = lj_pass(st, family, (const double*)Z_dev, N, ldz, D, (const double*)w_dev, Theta, chains, 32, part, 0);
@@ -538,8 +524,8 @@ extern "C" int bcx_hmc_stream(void* stream, int32_t family, int64_t N, int32_t D
   pass_and_step(0, 0);
   for (int t = 0; t < p.T; ++t) {
     for (int l = 1; l <= p.L; ++l) pass_and_step(l, t);
-    if ((t & 63) == 63 && hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_hmc_stream: launch failed"); return BCX_ERR_HIP; }
+    if ((t & 63) == 63) BCX_TRY("bcx_hmc_stream", hipGetLastError());
   }
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_hmc_stream: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_hmc_stream", hipGetLastError());
   return BCX_OK;
 }

@@ -203,22 +203,17 @@ extern "C" int bcx_laplace_sampler(void* stream, int32_t family, int32_t k, int3
                                    int32_t S, int32_t ld, void* theta_dev, void* tbar_dev, void* status_dev) {
   if ((family != LAP_LOGISTIC && family != LAP_POISSON) || !bcx_laplace_sampler_ok(k, D) || S < 1 || ld < D || max_iter < 1 || !(tol > 0.0) ||
       !mu_dev || !R_dev || !Rbar_dev || !theta_dev || !tbar_dev || !status_dev ||
-      (k > 0 && (!w_dev || !pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0)))) {
-    bcx_project_set_error("bcx_laplace_sampler: bad arguments (family 0 logistic / 1 Poisson, D <= 32 parameters, the points within "
-                          "bcx_laplace_sampler_ok)");
-    return BCX_ERR_ARG;
-  }
+      (k > 0 && (!w_dev || !pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_laplace_sampler", "bad arguments (family 0 logistic / 1 Poisson, D <= 32 parameters, the points within "
+                                                        "bcx_laplace_sampler_ok)");
   LapArgs a;
   a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.mu = (double*)mu_dev; a.R = (const double*)R_dev;
   a.Rbar = (const double*)Rbar_dev; a.theta = (double*)theta_dev; a.tbar = (double*)tbar_dev; a.status = (int*)status_dev;
   a.tol = tol; a.family = family; a.k = k; a.D = D; a.ldp = (int)ldp; a.S = S; a.ld = ld; a.max_iter = max_iter; a.warm = warm;
   const size_t lds = (size_t)bcx_laplace_sampler_lds_bytes(k, D);
   static PerDevice<size_t> lds_max;
-  if (raise_dynamic_lds((const void*)laplace_sampler_kernel, lds, 32 * 1024, lds_max) != hipSuccess) {
-    bcx_project_set_error("bcx_laplace_sampler: hipFuncSetAttribute failed");
-    return BCX_ERR_HIP;
-  }
+  BCX_TRY("bcx_laplace_sampler", raise_dynamic_lds((const void*)laplace_sampler_kernel, lds, 32 * 1024, lds_max));
   hipLaunchKernelGGL(laplace_sampler_kernel, dim3(1), dim3(LAP_THREADS), lds, (hipStream_t)stream, a);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_laplace_sampler: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_laplace_sampler", hipGetLastError());
   return BCX_OK;
 }

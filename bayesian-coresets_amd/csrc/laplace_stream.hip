@@ -350,17 +350,13 @@ extern "C" int bcx_laplace_sampler_stream(void* stream, int32_t family, int32_t 
                                           void* work_dev, int64_t work_bytes) {
   if ((family != LAP_LOGISTIC && family != LAP_POISSON) || k < 0 || D < 1 || D > LS_DMAX || S < 1 || ld < D || max_iter < 1 || !(tol > 0.0) ||
       !mu_dev || !R_dev || !Rbar_dev || !theta_dev || !tbar_dev || !status_dev || !work_dev ||
-      work_bytes < bcx_laplace_stream_scratch_bytes(k, D) || (k > 0 && (!w_dev || !pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0)))) {
-    bcx_project_set_error("bcx_laplace_sampler_stream: bad arguments (family 0 logistic / 1 Poisson, D <= 32 parameters, work_dev of "
-                          "bcx_laplace_stream_scratch_bytes)");
-    return BCX_ERR_ARG;
-  }
+      work_bytes < bcx_laplace_stream_scratch_bytes(k, D) || (k > 0 && (!w_dev || !pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_laplace_sampler_stream", "bad arguments (family 0 logistic / 1 Poisson, D <= 32 parameters, work_dev of "
+                                                               "bcx_laplace_stream_scratch_bytes)");
   static PerDevice<int> resident_of;
   const int resident = one_wg_per_cu((const void*)laplace_stream_kernel, LS_THREADS, resident_of);
-  if (resident < 1) {
-    bcx_project_set_error("bcx_laplace_sampler_stream: the kernel's workgroups cannot be resident together on this device");
-    return BCX_ERR_STATE;
-  }
+  if (resident < 1)
+    return bcx_fail(BCX_ERR_STATE, "bcx_laplace_sampler_stream", "the kernel's workgroups cannot be resident together on this device");
   const int G = std::min(ls_cap_wgs(k), resident);
   LapStreamArgs a;
   a.w = (const double*)w_dev; a.pts = (const double*)pts_dev; a.mu = (double*)mu_dev; a.R = (const double*)R_dev;
@@ -369,11 +365,8 @@ extern "C" int bcx_laplace_sampler_stream(void* stream, int32_t family, int32_t 
   a.tol = tol; a.ldp = ldp; a.family = family; a.k = k; a.D = D; a.S = S; a.ld = ld; a.max_iter = max_iter; a.warm = warm;
   a.rec = ls_record(D);
   const GridSync gs = grid_sync_at((unsigned long long*)work_dev, 200000000LL);         // 2 s of the 100 MHz wall clock per wait
-  if (hipMemsetAsync(work_dev, 0, LS_SYNC_BYTES, (hipStream_t)stream) != hipSuccess) {
-    bcx_project_set_error("bcx_laplace_sampler_stream: memset failed");
-    return BCX_ERR_HIP;
-  }
+  BCX_TRY("bcx_laplace_sampler_stream", hipMemsetAsync(work_dev, 0, LS_SYNC_BYTES, (hipStream_t)stream));
   hipLaunchKernelGGL(laplace_stream_kernel, dim3(G), dim3(LS_THREADS), 0, (hipStream_t)stream, a, gs);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_laplace_sampler_stream: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_laplace_sampler_stream", hipGetLastError());
   return BCX_OK;
 }

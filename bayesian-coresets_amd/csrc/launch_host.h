@@ -1,6 +1,6 @@
-// launch_host.h -- host-side launch plumbing the sampler entry points share (csrc/hmc.hip, nuts.hip, nuts_stream.hip,
-// laplace.hip, laplace_stream.hip, svi.hip): the current device's slot in a per-device cache, the dynamic LDS a kernel may have,
-// raising a kernel's dynamic-LDS limit once per device, and the size of a grid whose workgroups must be resident together.
+// launch_host.h -- host-side launch plumbing of the entry points that take no bcx_solver*: reporting a HIP status (hip_fail,
+// BCX_TRY), the current device's slot in a per-device cache, its CU count, the dynamic LDS a kernel may have, raising a
+// kernel's dynamic-LDS limit once per device, and the size of a grid whose workgroups must be resident together.
 // Host only.  Every cache is one PerDevice per kernel, a function-local static at the call site: zero means "not asked yet".
 // (GridSync's set-up, grid_sync_at, sits next to the struct in csrc/nnls_common.h.)
 #pragma once
@@ -8,6 +8,21 @@
 #include <atomic>
 #include <stddef.h>
 #include <stdint.h>
+#include "../../include/bcx.h"
+#include "host_err.h"
+
+// A HIP status that is not hipSuccess: the message (host_err.h) becomes "<who>: <step>: <HIP's reason>", HIP's sticky last
+// error is drained so that the next entry point's hipGetLastError() does not report this failure again, and BCX_ERR_HIP is returned.
+static inline int hip_fail(const char* who, const char* step, hipError_t e) {
+  (void)hipGetLastError();
+  return bcx_fail(BCX_ERR_HIP, who, std::string(step) + ": " + hipGetErrorString(e));
+}
+// `who`: the entry point (a helper that serves several passes the name it reports under); the step is the call's source text.
+#define BCX_TRY(who, call)                                          \
+  do {                                                              \
+    const hipError_t _e = (call);                                   \
+    if (_e != hipSuccess) return hip_fail(who, #call, _e);          \
+  } while (0)
 
 #define BCX_MAX_DEVICES 64
 template <class T> struct PerDevice { std::atomic<T> of[BCX_MAX_DEVICES]; };
@@ -22,6 +37,21 @@ static inline int device_slot_or_fail() {
 static inline int device_slot_or_zero() {
   const int dev = device_slot_or_fail();
   return dev < 0 ? 0 : dev;
+}
+
+// CUs of the current device, asked once per device.  A query that fails answers 256 (an MI355X), is not cached, and leaves
+// no HIP error behind: the plans that size scratch and the launches that use it then still agree.
+inline int cu_count() {
+  static PerDevice<int> cache;
+  const int dev = device_slot_or_fail();
+  int cus = dev < 0 ? 0 : cache.of[dev].load(std::memory_order_relaxed);
+  if (cus > 0) return cus;
+  if (dev >= 0 && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) {
+    cache.of[dev].store(cus, std::memory_order_relaxed);
+    return cus;
+  }
+  (void)hipGetLastError();
+  return 256;
 }
 
 // dynamic LDS one workgroup of `kernel` may have on the current device: the device's limit minus the kernel's static use
@@ -46,7 +76,7 @@ static inline int64_t lds_room(const void* kernel, PerDevice<int64_t>& cache) {
 
 // Let `kernel` have `bytes` of dynamic LDS.  Nothing to do at or below `threshold` (what a kernel may have unasked) or at or
 // below the largest request so far on the current device; else the attribute is raised and the request remembered.  The caller
-// reports a failure in its own words.
+// reports a failure under its own name (BCX_TRY).
 static inline hipError_t raise_dynamic_lds(const void* kernel, size_t bytes, size_t threshold, PerDevice<size_t>& cache) {
   if (bytes <= threshold) return hipSuccess;
   std::atomic<size_t>& largest = cache.of[device_slot_or_zero()];
@@ -62,12 +92,9 @@ static inline int one_wg_per_cu(const void* kernel, int threads, PerDevice<int>&
   const int dev = device_slot_or_zero();
   int n = cache.of[dev].load(std::memory_order_acquire);
   if (n != 0) return n;
-  int cus = 0, per_cu = 0;
-  if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1 ||
-      hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess || per_cu < 1)
-    n = -1;
-  else
-    n = cus;                                          // (the query over-reports for some kernels; one per CU keeps a margin)
+  int per_cu = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, threads, 0) != hipSuccess) (void)hipGetLastError();
+  n = per_cu < 1 ? -1 : cu_count();                   // (the query over-reports for some kernels; one per CU keeps a margin)
   cache.of[dev].store(n, std::memory_order_release);
   return n;
 }

@@ -46,6 +46,7 @@
 #include "bcx_internal.h"
 #include "dev_util.h"
 #include "chol32.h"
+#include "launch_host.h"
 
 typedef double lp4d __attribute__((ext_vector_type(4)));
 
@@ -682,15 +683,6 @@ __global__ __launch_bounds__(256) void lrp_draw_kernel(LpDrawArgs a) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-#define LRP_HIP(call)                                                             \
-  do {                                                                            \
-    hipError_t _e = (call);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      bcx_project_set_error(std::string(#call) + ": " + hipGetErrorString(_e));   \
-      return BCX_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
-
 static int lrp_helpers(int nt) {
   static const int forced = [] { const char* e = bcx_dev_env("BCX_LRP_HELPERS"); return e ? atoi(e) : 0; }();      // dev
   if (forced >= 1 && forced <= LP_MAX_H) return forced;
@@ -725,6 +717,7 @@ static bool lrp_one_xcd(hipStream_t st) {
       for (int i = 0; ok && i < n; ++i) ok = (i % 8 == 0) == (h[i] == h[0]);
       (void)hipFree(d);
     }
+    if (!ok) (void)hipGetLastError();
     k = ok ? 1 : 2;
     known[dev].store(k);
   }
@@ -752,12 +745,10 @@ extern "C" int bcx_linreg_posterior_factor(void* stream, int32_t k, int32_t D, i
                                            void* work_dev, int64_t work_bytes, void* U_dev, int64_t ldu, void* u_dev, void* mu_dev) {
   if (k < 0 || k > 4096 || D < 1 || D > LP_NB * LP_MAX_NT || ldx < (k + 31) / 32 * 32 || lds0 < D || ldu < D || (ldu & 1) || !(sigsq > 0.0) ||
       !S0inv_dev || !rhs0_dev || !work_dev || !U_dev || !u_dev || (k > 0 && (!w_dev || !XT_dev || !y_dev)) ||
-      work_bytes < bcx_linreg_posterior_factor_scratch_bytes(D) || (((uintptr_t)work_dev | (uintptr_t)XT_dev | (uintptr_t)U_dev) & 15)) {
-    bcx_project_set_error("bcx_linreg_posterior_factor: bad arguments (k <= 4096 points, D <= 1024 features, the features by points "
-                          "with a row stride of k rounded up to 32, zero padded, 16-byte aligned; scratch of "
-                          "bcx_linreg_posterior_factor_scratch_bytes(D) bytes)");
-    return BCX_ERR_ARG;
-  }
+      work_bytes < bcx_linreg_posterior_factor_scratch_bytes(D) || (((uintptr_t)work_dev | (uintptr_t)XT_dev | (uintptr_t)U_dev) & 15))
+    return bcx_fail(BCX_ERR_ARG, "bcx_linreg_posterior_factor", "bad arguments (k <= 4096 points, D <= 1024 features, the features by points "
+                                                                "with a row stride of k rounded up to 32, zero padded, 16-byte aligned; scratch of "
+                                                                "bcx_linreg_posterior_factor_scratch_bytes(D) bytes)");
   LpArgs a;
   a.w = (const double*)w_dev; a.XT = (const double*)XT_dev; a.y = (const double*)y_dev;
   a.S0inv = (const double*)S0inv_dev; a.rhs0 = (const double*)rhs0_dev;
@@ -782,7 +773,7 @@ extern "C" int bcx_linreg_posterior_factor(void* stream, int32_t k, int32_t D, i
   if (LP_FIXED_WGS + a.H <= 28 && lrp_one_xcd((hipStream_t)stream)) hipLaunchKernelGGL(lrp_chol_kernel<true>, dim3(8 * (LP_FIXED_WGS + a.H)), dim3(256), 0, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(lrp_chol_kernel<false>, dim3(LP_FIXED_WGS + a.H), dim3(256), 0, (hipStream_t)stream, a);
   if (a.mu) hipLaunchKernelGGL(lrp_mean_kernel, dim3(nt), dim3(256), 0, (hipStream_t)stream, a);
-  LRP_HIP(hipGetLastError());
+  BCX_TRY("bcx_linreg_posterior_factor", hipGetLastError());
   return BCX_OK;
 }
 
@@ -791,20 +782,20 @@ static int* lrp_status_word(const void* work_dev, int nt) {
 }
 // Enqueues status word = 0 (before the first factorisation a status read covers: a loop's, or a single call's).
 extern "C" int bcx_linreg_posterior_factor_clear_status(void* stream, int32_t D, void* work_dev) {
-  if (D < 1 || D > LP_NB * LP_MAX_NT || !work_dev) { bcx_project_set_error("bcx_linreg_posterior_factor_clear_status: bad arguments"); return BCX_ERR_ARG; }
-  LRP_HIP(hipMemsetAsync(lrp_status_word(work_dev, (D + LP_NB - 1) / LP_NB), 0, sizeof(int), (hipStream_t)stream));
+  if (D < 1 || D > LP_NB * LP_MAX_NT || !work_dev) return bcx_fail(BCX_ERR_ARG, "bcx_linreg_posterior_factor_clear_status", "bad arguments");
+  BCX_TRY("bcx_linreg_posterior_factor_clear_status", hipMemsetAsync(lrp_status_word(work_dev, (D + LP_NB - 1) / LP_NB), 0, sizeof(int), (hipStream_t)stream));
   return BCX_OK;
 }
 // After a synchronisation of the stream, the worst of every factorisation since the last clear (reading does not clear): 0 ok,
 // BCX_ERR_TIMEOUT a wait between the workgroups of lrp_chol_kernel expired (its outputs are not valid), BCX_ERR_STATE a pivot
 // was not positive or NaN (P not positive definite: NaN / non-finite weights or points upstream).
 extern "C" int bcx_linreg_posterior_factor_status(void* stream, int32_t D, const void* work_dev) {
-  if (D < 1 || D > LP_NB * LP_MAX_NT || !work_dev) { bcx_project_set_error("bcx_linreg_posterior_factor_status: bad arguments"); return BCX_ERR_ARG; }
+  if (D < 1 || D > LP_NB * LP_MAX_NT || !work_dev) return bcx_fail(BCX_ERR_ARG, "bcx_linreg_posterior_factor_status", "bad arguments");
   int v = 0;
-  LRP_HIP(hipMemcpyAsync(&v, lrp_status_word(work_dev, (D + LP_NB - 1) / LP_NB), sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
-  LRP_HIP(hipStreamSynchronize((hipStream_t)stream));
-  if (v == 1) { bcx_project_set_error("linreg posterior factorisation: a wait between workgroups timed out (GPU shared or preempted)"); return BCX_ERR_TIMEOUT; }
-  if (v == 2) { bcx_project_set_error("linreg posterior factorisation: the precision matrix is not positive definite"); return BCX_ERR_STATE; }
+  BCX_TRY("bcx_linreg_posterior_factor_status", hipMemcpyAsync(&v, lrp_status_word(work_dev, (D + LP_NB - 1) / LP_NB), sizeof v, hipMemcpyDeviceToHost, (hipStream_t)stream));
+  BCX_TRY("bcx_linreg_posterior_factor_status", hipStreamSynchronize((hipStream_t)stream));
+  if (v == 1) return bcx_fail(BCX_ERR_TIMEOUT, "linreg posterior factorisation", "a wait between workgroups timed out (GPU shared or preempted)");
+  if (v == 2) return bcx_fail(BCX_ERR_STATE, "linreg posterior factorisation", "the precision matrix is not positive definite");
   return BCX_OK;
 }
 
@@ -813,14 +804,12 @@ extern "C" int bcx_linreg_posterior_factor_status(void* stream, int32_t D, const
 extern "C" int bcx_linreg_posterior_draw_factored(void* stream, int32_t D, int32_t ld, const void* U_dev, int64_t ldu, const void* u_dev,
                                                   const void* R_dev, const void* Rbar_dev, int32_t S, void* theta_dev, void* tbar_dev) {
   if (D < 1 || D > LP_NB * LP_MAX_NT || ld < D || (ld & 1) || ldu < D || (ldu & 1) || S < 1 || S > (1 << 22) || !U_dev || !u_dev || !R_dev ||
-      !Rbar_dev || !theta_dev || !tbar_dev || (((uintptr_t)U_dev | (uintptr_t)R_dev | (uintptr_t)Rbar_dev) & 15)) {
-    bcx_project_set_error("bcx_linreg_posterior_draw_factored: bad arguments (even leading dimensions, 16-byte aligned rows)");
-    return BCX_ERR_ARG;
-  }
+      !Rbar_dev || !theta_dev || !tbar_dev || (((uintptr_t)U_dev | (uintptr_t)R_dev | (uintptr_t)Rbar_dev) & 15))
+    return bcx_fail(BCX_ERR_ARG, "bcx_linreg_posterior_draw_factored", "bad arguments (even leading dimensions, 16-byte aligned rows)");
   LpDrawArgs a;
   a.U = (const double*)U_dev; a.u = (const double*)u_dev; a.R = (const double*)R_dev; a.Rbar = (const double*)Rbar_dev;
   a.theta = (double*)theta_dev; a.tbar = (double*)tbar_dev; a.ldu = ldu; a.D = D; a.S = S; a.ld = ld;
   hipLaunchKernelGGL(lrp_draw_kernel, dim3((S + 1 + 15) / 16, (ld + 15) / 16), dim3(256), 0, (hipStream_t)stream, a);
-  LRP_HIP(hipGetLastError());
+  BCX_TRY("bcx_linreg_posterior_draw_factored", hipGetLastError());
   return BCX_OK;
 }

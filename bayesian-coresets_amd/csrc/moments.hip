@@ -24,6 +24,7 @@
 #include "dev_util.h"
 
 #include "moments_quad.h"
+#include "launch_host.h"
 
 #define MOM_BLK 64          // columns per block
 #define MOM_ROWS 32         // rows staged per chunk (4 waves x 2 k-steps x 4 rows)
@@ -164,20 +165,10 @@ __global__ __launch_bounds__(256) void moments_mean_kernel(const double* __restr
 template <bool AL>
 __global__ __launch_bounds__(256) void moments_quad_kernel(MqArgs q) { moments_quad_body<AL>(q, blockIdx.x, gridDim.x); }
 
-#define MOM_HIP(call)                                                             \
-  do {                                                                            \
-    hipError_t _e = (call);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      bcx_project_set_error(std::string(#call) + ": " + hipGetErrorString(_e));   \
-      return BCX_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
-
 static void moments_plan(int64_t N, int C, int* nblk, int* nslices, int64_t* rows_per_slice) {
   *nblk = (C + MOM_BLK - 1) / MOM_BLK;
   const int npairs = *nblk * (*nblk + 1) / 2;
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = cu_count();
   const int64_t chunks = (N + MOM_ROWS - 1) / MOM_ROWS;
   // two workgroups per CU are resident; two rounds of them, and never fewer than 8 chunks per slice
   int64_t sl = std::max<int64_t>(1, (int64_t)(4 * cus) / npairs);
@@ -197,11 +188,9 @@ extern "C" int64_t bcx_project_moments_scratch_bytes(int64_t N, int32_t C) {
 // M_dev (C x ldm doubles, both triangles) = Z^T Z over the N rows of Z_dev (N x ldz doubles, C = D + 1 columns used).
 extern "C" int bcx_project_moments(void* stream, const void* Z_dev, int64_t N, int64_t ldz, int32_t C, void* M_dev, int64_t ldm,
                                    void* work_dev, int64_t work_bytes) {
-  if (!Z_dev || !M_dev || !work_dev || N < 0 || C < 1 || C > MOM_MAX_COLS || ldz < C || ldm < C) {
-    bcx_project_set_error("bcx_project_moments: bad arguments (1 <= columns <= 1024)");
-    return BCX_ERR_ARG;
-  }
-  if (work_bytes < bcx_project_moments_scratch_bytes(N, C)) { bcx_project_set_error("bcx_project_moments: scratch too small"); return BCX_ERR_ARG; }
+  if (!Z_dev || !M_dev || !work_dev || N < 0 || C < 1 || C > MOM_MAX_COLS || ldz < C || ldm < C)
+    return bcx_fail(BCX_ERR_ARG, "bcx_project_moments", "bad arguments (1 <= columns <= 1024)");
+  if (work_bytes < bcx_project_moments_scratch_bytes(N, C)) return bcx_fail(BCX_ERR_ARG, "bcx_project_moments", "scratch too small");
   int nblk, nslices; int64_t rps;
   moments_plan(N, C, &nblk, &nslices, &rps);
   const int npairs = nblk * (nblk + 1) / 2;
@@ -210,7 +199,7 @@ extern "C" int bcx_project_moments(void* stream, const void* Z_dev, int64_t N, i
                      rps, (double*)work_dev);
   hipLaunchKernelGGL(moments_reduce_kernel, dim3(npairs), dim3(256), 0, st, (const double*)work_dev, nblk, nslices, (int)C,
                      (double*)M_dev, ldm);
-  MOM_HIP(hipGetLastError());
+  BCX_TRY("bcx_project_moments", hipGetLastError());
   return BCX_OK;
 }
 
@@ -342,8 +331,7 @@ __global__ __launch_bounds__(256, 2) void gram_tile_kernel(const double* __restr
 static void gram_plan(int k, int d, int* nblk, int* nslices, int64_t* len_per_slice, int* pshift) {
   *nblk = (k + MOM_BLK - 1) / MOM_BLK;
   const int npairs = *nblk * (*nblk + 1) / 2;
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+  const int cus = cu_count();
   const int64_t chunks = ((int64_t)d + MOM_ROWS - 1) / MOM_ROWS;
   static const int force = [] { const char* e = bcx_dev_env("BCX_GRAM_SLICES"); return e ? atoi(e) : 0; }();    // dev knobs
   static const int force_p = [] { const char* e = bcx_dev_env("BCX_GRAM_PATCH"); return e ? atoi(e) : -1; }();
@@ -390,7 +378,8 @@ int bcx_gram_rows_tiled(hipStream_t st, const double* rows, int k, int d, int64_
     hipLaunchKernelGGL(gram_tile_kernel<false>, dim3(grid), dim3(256), 0, st, rows, k, d, ld, nblk, lps, ps, work, G, ldg);
     hipLaunchKernelGGL(moments_reduce_kernel, dim3(npairs), dim3(256), 0, st, (const double*)work, nblk, nslices, k, G, ldg);
   }
-  return hipGetLastError() == hipSuccess ? BCX_OK : BCX_ERR_HIP;
+  BCX_TRY("bcx_gram", hipGetLastError());      // (also for the callers in the solver and csrc/qn.hip: they pass the text on)
+  return BCX_OK;
 }
 // The same through the C ABI (include/bcx.h): the dense re-weight's Gram as an operator of its own.
 extern "C" int64_t bcx_gram_scratch_bytes(int32_t k, int32_t d) {
@@ -399,22 +388,18 @@ extern "C" int64_t bcx_gram_scratch_bytes(int32_t k, int32_t d) {
 }
 extern "C" int bcx_gram(void* stream, const void* rows_dev, int32_t k, int32_t d, int64_t ld, void* G_dev, int64_t ldg,
                         void* work_dev, int64_t work_bytes) {
-  if (!rows_dev || !G_dev || !work_dev || k < 1 || d < 1 || k > BCX_GRAM_MAX_ROWS || ld < d || ldg < k) {
-    bcx_project_set_error("bcx_gram: bad arguments");
-    return BCX_ERR_ARG;
-  }
-  if (work_bytes < bcx_gram_rows_scratch_bytes(k, d)) { bcx_project_set_error("bcx_gram: scratch too small"); return BCX_ERR_ARG; }
-  const int rc = bcx_gram_rows((hipStream_t)stream, (const double*)rows_dev, k, d, ld, (double*)G_dev, ldg, (double*)work_dev);
-  if (rc != BCX_OK) bcx_project_set_error("bcx_gram: kernel launch failed");
-  return rc;
+  if (!rows_dev || !G_dev || !work_dev || k < 1 || d < 1 || k > BCX_GRAM_MAX_ROWS || ld < d || ldg < k)
+    return bcx_fail(BCX_ERR_ARG, "bcx_gram", "bad arguments");
+  if (work_bytes < bcx_gram_rows_scratch_bytes(k, d)) return bcx_fail(BCX_ERR_ARG, "bcx_gram", "scratch too small");
+  return bcx_gram_rows((hipStream_t)stream, (const double*)rows_dev, k, d, ld, (double*)G_dev, ldg, (double*)work_dev);
 }
 
 extern "C" int bcx_gram_check(void* stream, const void* work_dev) {
-  if (!work_dev) { bcx_project_set_error("bcx_gram_check: bad arguments"); return BCX_ERR_ARG; }
+  if (!work_dev) return bcx_fail(BCX_ERR_ARG, "bcx_gram_check", "bad arguments");
   // (every call so far that used this scratch: the word only ever holds the number of a call that gave up a wait)
   const int t = bcx_gram_sk_timed_out((hipStream_t)stream, (const double*)work_dev, 0ull);
-  if (t < 0) { bcx_project_set_error("bcx_gram_check: reading the status word failed"); return t; }
-  if (t) { bcx_project_set_error("bcx_gram: a workgroup timed out waiting for a peer's partial tile; G is not valid"); return BCX_ERR_TIMEOUT; }
+  if (t < 0) return t;
+  if (t) return bcx_fail(BCX_ERR_TIMEOUT, "bcx_gram", "a workgroup timed out waiting for a peer's partial tile; G is not valid");
   return BCX_OK;
 }
 
@@ -436,10 +421,8 @@ extern "C" int bcx_project_colsum_moments_at(void* stream, const void* M_dev, in
                                              const void* theta_dev, int32_t S, int32_t ldt, double sigsq, void* colsum_dev,
                                              void* work_dev, const void* tbar_dev) {
   if (!M_dev || !theta_dev || !colsum_dev || !work_dev || D < 1 || D >= MOM_MAX_COLS || ycol < 0 || ycol >= ldm || ldm < D ||
-      S < 1 || ldt < D || !(sigsq > 0.0)) {
-    bcx_project_set_error("bcx_project_colsum_moments: bad arguments");
-    return BCX_ERR_ARG;
-  }
+      S < 1 || ldt < D || !(sigsq > 0.0))
+    return bcx_fail(BCX_ERR_ARG, "bcx_project_colsum_moments", "bad arguments");
   int nct, Spad;
   mq_plan(D, S, &nct, &Spad);
   double* work = (double*)work_dev;
@@ -458,7 +441,7 @@ extern "C" int bcx_project_colsum_moments_at(void* stream, const void* M_dev, in
   q.tbar = tbar; q.sigsq = sigsq; q.colsum = (double*)colsum_dev; q.work = work; q.nct = nct; q.Spad = Spad; q.dbg = mqdbg;
   if (al) hipLaunchKernelGGL(moments_quad_kernel<true>, dim3(tiles), dim3(256), 0, st, q);
   else hipLaunchKernelGGL(moments_quad_kernel<false>, dim3(tiles), dim3(256), 0, st, q);
-  MOM_HIP(hipGetLastError());
+  BCX_TRY("bcx_project_colsum_moments", hipGetLastError());
   return BCX_OK;
 }
 

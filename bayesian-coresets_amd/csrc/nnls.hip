@@ -711,7 +711,7 @@ int bcx_launch_optimize(bcx_solver* s, double tol) {
   auto gram_ok = [&]() -> int {
     if (!s->gram_work) return BCX_OK;
     const int t = bcx_gram_sk_timed_out(s->stream, s->gram_work, gram_since);
-    if (t < 0) return t;
+    if (t < 0) { s->err = std::string("optimize: ") + bcx_fail_text(); return t; }
     if (t) { s->err = "optimize: the Gram kernel timed out waiting for a peer workgroup's partial tile (GPU shared or preempted); result discarded"; return BCX_ERR_TIMEOUT; }
     return BCX_OK;
   };
@@ -720,7 +720,7 @@ int bcx_launch_optimize(bcx_solver* s, double tol) {
     const size_t need = std::max((size_t)bcx_gram_rows_scratch_bytes(k, s->cfg.d), (size_t)bcx_gram_rows_scratch_bytes(kp64, kp64));
     if (s->gram_work.count() * sizeof(double) < need) BCX_HIP((hipError_t)s->gram_work.alloc((need + 7) / 8, false));
     const int rc = bcx_gram_rows(s->stream, s->act_rows, k, s->cfg.d, (int64_t)s->cfg.d, s->gram, (int64_t)s->gram_cap, s->gram_work);
-    if (rc != BCX_OK) { s->err = "optimize: Gram kernel launch failed"; return rc; }
+    if (rc != BCX_OK) { s->err = std::string("optimize: Gram kernel launch failed: ") + bcx_fail_text(); return rc; }
   }
   if (k > 0) {
     // incremental Lawson-Hanson on the double-double inverse (omp_lh.hip), started WARM from the largest independent part of

@@ -300,12 +300,10 @@ extern "C" int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t
                                 void* status_dev) {
   if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
       max_depth < 1 || max_depth > NUTS_JMAX || noise_ld < nuts_noise_row(D, max_depth) || !bcx_nuts_coreset_ok(k, D) ||
-      (W_dev && ldw < D) || (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0)))) {
-    bcx_project_set_error("bcx_nuts_coreset: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, the points within "
-                          "bcx_nuts_coreset_ok, at least one transition, max_depth 1 .. 10, noise_ld >= D + 3 max_depth + "
-                          "2 (2^max_depth - 1), eps0 > 0)");
-    return BCX_ERR_ARG;
-  }
+      (W_dev && ldw < D) || (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_nuts_coreset", "bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, the points within "
+                                                     "bcx_nuts_coreset_ok, at least one transition, max_depth 1 .. 10, noise_ld >= D + 3 max_depth + "
+                                                     "2 (2^max_depth - 1), eps0 > 0)");
   NutsArgs a;
   a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, 0, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev, prop_dev,
                   diag_dev, accept_dev, eps_dev, status_dev);
@@ -313,13 +311,10 @@ extern "C" int bcx_nuts_coreset(void* stream, int32_t family, int32_t k, int32_t
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)bcx_nuts_coreset_lds_bytes(k, D);
   static PerDevice<size_t> lds_max;
-  if (raise_dynamic_lds((const void*)nuts_coreset_kernel<false>, lds, 16 * 1024, lds_max) != hipSuccess) {
-    bcx_project_set_error("bcx_nuts_coreset: hipFuncSetAttribute failed");
-    return BCX_ERR_HIP;
-  }
-  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_nuts_coreset: memset failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_nuts_coreset", raise_dynamic_lds((const void*)nuts_coreset_kernel<false>, lds, 16 * 1024, lds_max));
+  BCX_TRY("bcx_nuts_coreset", hipMemsetAsync(status_dev, 0, sizeof(int), st));
   hipLaunchKernelGGL(nuts_coreset_kernel<false>, dim3(chains), dim3(HMC_THREADS), lds, st, a);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_coreset: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_nuts_coreset", hipGetLastError());
   return BCX_OK;
 }
 
@@ -341,11 +336,9 @@ extern "C" int bcx_nuts_adapt(void* stream, int32_t family, int32_t k, int32_t D
   if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
       max_depth < 1 || max_depth > NUTS_JMAX || noise_ld < nuts_noise_row(D, max_depth) || !bcx_nuts_adapt_ok(k, D) ||
       (W_dev && ldw < D) || (k > 0 && (!pts_dev || ldp < D + (family == LAP_POISSON ? 1 : 0))) ||
-      (metric != NUTS_METRIC_DIAG && metric != NUTS_METRIC_DENSE) || fixed_eps > 0.0 || !frames_dev || !metric_dev) {
-    bcx_project_set_error("bcx_nuts_adapt: bad arguments (those of bcx_nuts_coreset with the points within bcx_nuts_adapt_ok; metric 1 "
-                          "diag / 2 dense; no fixed_eps with a metric; frames_dev and metric_dev)");
-    return BCX_ERR_ARG;
-  }
+      (metric != NUTS_METRIC_DIAG && metric != NUTS_METRIC_DENSE) || fixed_eps > 0.0 || !frames_dev || !metric_dev)
+    return bcx_fail(BCX_ERR_ARG, "bcx_nuts_adapt", "bad arguments (those of bcx_nuts_coreset with the points within bcx_nuts_adapt_ok; metric 1 "
+                                                   "diag / 2 dense; no fixed_eps with a metric; frames_dev and metric_dev)");
   NutsAdaptArgs g;
   NutsArgs& a = g.nuts;
   a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, 0, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev, prop_dev,
@@ -354,17 +347,14 @@ extern "C" int bcx_nuts_adapt(void* stream, int32_t family, int32_t k, int32_t D
   g.frames = (double*)frames_dev; g.metric_out = (double*)metric_dev; g.metric = metric;
   for (int i = 0; i < 2 * NUTS_ADAPT_WINDOWS; ++i) g.win[i] = 0;
   g.nwin = nuts_adapt_schedule(n_warmup, g.win, NUTS_ADAPT_WINDOWS);
-  if (g.nwin > NUTS_ADAPT_WINDOWS) { bcx_project_set_error("bcx_nuts_adapt: more than 32 warm-up windows"); return BCX_ERR_ARG; }
+  if (g.nwin > NUTS_ADAPT_WINDOWS) return bcx_fail(BCX_ERR_ARG, "bcx_nuts_adapt", "more than 32 warm-up windows");
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)bcx_nuts_coreset_lds_bytes(k, D);
   static PerDevice<size_t> lds_max;
-  if (raise_dynamic_lds((const void*)nuts_coreset_kernel<true>, lds, 0, lds_max) != hipSuccess) {   // (its static LDS is past 48 KiB)
-    bcx_project_set_error("bcx_nuts_adapt: hipFuncSetAttribute failed");
-    return BCX_ERR_HIP;
-  }
-  if (hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) { bcx_project_set_error("bcx_nuts_adapt: memset failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_nuts_adapt", raise_dynamic_lds((const void*)nuts_coreset_kernel<true>, lds, 0, lds_max));   // (its static LDS is past 48 KiB)
+  BCX_TRY("bcx_nuts_adapt", hipMemsetAsync(status_dev, 0, sizeof(int), st));
   hipLaunchKernelGGL(nuts_coreset_kernel<true>, dim3(chains), dim3(HMC_THREADS), lds, st, g);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_adapt: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_nuts_adapt", hipGetLastError());
   return BCX_OK;
 }
 
@@ -382,12 +372,9 @@ template <bool ADAPT, class Args>
 static int nuts_batch_launch(const Args& g, const bcx_nuts_problem* table, int32_t P, int32_t chains, size_t lds, size_t threshold,
                              hipStream_t st) {
   static PerDevice<size_t> lds_max;
-  if (raise_dynamic_lds((const void*)nuts_batch_kernel<ADAPT>, lds, threshold, lds_max) != hipSuccess) {
-    bcx_project_set_error("bcx_nuts_batch: hipFuncSetAttribute failed");
-    return BCX_ERR_HIP;
-  }
+  BCX_TRY("bcx_nuts_batch", raise_dynamic_lds((const void*)nuts_batch_kernel<ADAPT>, lds, threshold, lds_max));
   hipLaunchKernelGGL(nuts_batch_kernel<ADAPT>, dim3((unsigned)P * (unsigned)chains), dim3(HMC_THREADS), lds, st, g, table);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_batch: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_nuts_batch", hipGetLastError());
   return BCX_OK;
 }
 extern "C" int bcx_nuts_batch(void* stream, int32_t family, int32_t P, const bcx_nuts_problem* problems, void* table_dev, int32_t D,
@@ -398,50 +385,38 @@ extern "C" int bcx_nuts_batch(void* stream, int32_t family, int32_t P, const bcx
   if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
       P < 1 || (int64_t)P * chains > INT32_MAX || !problems || !table_dev || max_depth < 1 || max_depth > NUTS_JMAX ||
       noise_ld < nuts_noise_row(D, max_depth) || (metric != 0 && metric != NUTS_METRIC_DIAG && metric != NUTS_METRIC_DENSE) ||
-      (metric != 0) != (frames_dev != nullptr) || (metric != 0) != (metric_dev != nullptr)) {
-    bcx_project_set_error("bcx_nuts_batch: bad arguments (those of bcx_nuts_coreset without fixed_eps; P >= 1 problems, P x chains "
-                          "<= 2^31 - 1, problems and table_dev; metric 0 none / 1 diag / 2 dense, frames_dev and metric_dev iff a metric)");
-    return BCX_ERR_ARG;
-  }
+      (metric != 0) != (frames_dev != nullptr) || (metric != 0) != (metric_dev != nullptr))
+    return bcx_fail(BCX_ERR_ARG, "bcx_nuts_batch", "bad arguments (those of bcx_nuts_coreset without fixed_eps; P >= 1 problems, P x chains "
+                                                   "<= 2^31 - 1, problems and table_dev; metric 0 none / 1 diag / 2 dense, frames_dev and metric_dev iff a metric)");
   const int64_t row = D + (family == LAP_POISSON ? 1 : 0);
   for (int32_t p = 0; p < P; ++p) {
     const bcx_nuts_problem& q = problems[p];
-    if (q.k < 0 || (q.W_dev && q.ldw < D) || (q.k > 0 && (!q.pts_dev || q.ldp < row))) {
-      bcx_project_set_error(("bcx_nuts_batch: problem " + std::to_string(p) + ": bad arguments (k >= 0, ldw >= D with W_dev, pts_dev and "
-                             "ldp >= the row with k > 0)").c_str());
-      return BCX_ERR_ARG;
-    }
+    if (q.k < 0 || (q.W_dev && q.ldw < D) || (q.k > 0 && (!q.pts_dev || q.ldp < row)))
+      return bcx_fail(BCX_ERR_ARG, "bcx_nuts_batch", "problem " + std::to_string(p) + ": bad arguments (k >= 0, ldw >= D with W_dev, pts_dev and "
+                                                     "ldp >= the row with k > 0)");
   }
   // what asks the device: every problem within one workgroup's LDS, next to the static LDS of the kernel that runs
   int64_t lds = 0;
   for (int32_t p = 0; p < P; ++p) {
     const int32_t k = problems[p].k;
     const int64_t b = bcx_nuts_coreset_lds_bytes(k, D);
-    if (!(metric ? bcx_nuts_adapt_ok(k, D) && nuts_batch_fits<true>(b) : bcx_nuts_coreset_ok(k, D) && nuts_batch_fits<false>(b))) {
-      bcx_project_set_error(("bcx_nuts_batch: problem " + std::to_string(p) + ": " + std::to_string(k) + " points of " + std::to_string(D) +
-                             " parameters are outside " + (metric ? "bcx_nuts_adapt_ok" : "bcx_nuts_coreset_ok")).c_str());
-      return BCX_ERR_ARG;
-    }
+    if (!(metric ? bcx_nuts_adapt_ok(k, D) && nuts_batch_fits<true>(b) : bcx_nuts_coreset_ok(k, D) && nuts_batch_fits<false>(b)))
+      return bcx_fail(BCX_ERR_ARG, "bcx_nuts_batch", "problem " + std::to_string(p) + ": " + std::to_string(k) + " points of " + std::to_string(D) +
+                                                     " parameters are outside " + (metric ? "bcx_nuts_adapt_ok" : "bcx_nuts_coreset_ok"));
     if (b > lds) lds = b;
   }
   int win[2 * NUTS_ADAPT_WINDOWS] = {0};
   const int nwin = metric ? nuts_adapt_schedule(n_warmup, win, NUTS_ADAPT_WINDOWS) : 0;
-  if (nwin > NUTS_ADAPT_WINDOWS) { bcx_project_set_error("bcx_nuts_batch: more than 32 warm-up windows"); return BCX_ERR_ARG; }
+  if (nwin > NUTS_ADAPT_WINDOWS) return bcx_fail(BCX_ERR_ARG, "bcx_nuts_batch", "more than 32 warm-up windows");
   // the dispatch order: k descending (the caller's order among equals), each record with its place in the caller's order
   std::vector<bcx_nuts_problem> table(problems, problems + P);
   for (int32_t p = 0; p < P; ++p) table[p].index = p;
   std::stable_sort(table.begin(), table.end(), [](const bcx_nuts_problem& x, const bcx_nuts_problem& y) { return x.k > y.k; });
   hipStream_t st = (hipStream_t)stream;
   // (the records are pageable host memory that ends with this call: the copy is waited for)
-  if (hipMemcpyAsync(table_dev, table.data(), (size_t)P * sizeof(bcx_nuts_problem), hipMemcpyHostToDevice, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess) {
-    bcx_project_set_error("bcx_nuts_batch: the upload of the problem table failed");
-    return BCX_ERR_HIP;
-  }
-  if (hipMemset2DAsync(status_dev, 2 * sizeof(int), 0, sizeof(int), (size_t)P, st) != hipSuccess) {      // status[2 p] of every problem
-    bcx_project_set_error("bcx_nuts_batch: memset failed");
-    return BCX_ERR_HIP;
-  }
+  BCX_TRY("bcx_nuts_batch", hipMemcpyAsync(table_dev, table.data(), (size_t)P * sizeof(bcx_nuts_problem), hipMemcpyHostToDevice, st));
+  BCX_TRY("bcx_nuts_batch", hipStreamSynchronize(st));
+  BCX_TRY("bcx_nuts_batch", hipMemset2DAsync(status_dev, 2 * sizeof(int), 0, sizeof(int), (size_t)P, st));      // status[2 p] of every problem
   NutsAdaptArgs g;
   NutsArgs& a = g.nuts;
   a.par = hmc_par(D, nullptr, nullptr, D, chains, n_warmup, n_samples, 0, eps0, 0.0, noise_dev, ld, samples_dev, xi_dev, prop_dev, diag_dev,

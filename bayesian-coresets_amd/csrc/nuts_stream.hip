@@ -453,18 +453,14 @@ extern "C" int bcx_nuts_stream(void* stream, int32_t family, int64_t N, int32_t 
   if (!hmc_common_ok(family, D, chains, n_warmup, n_samples, eps0, ld, noise_dev, samples_dev, diag_dev, accept_dev, eps_dev, status_dev) ||
       N < 0 || chains > NS_CMAX || max_depth < 1 || max_depth > NUTS_JMAX || !scratch_dev || noise_ld < nuts_noise_row(D, max_depth) ||
       (W_dev && ldw < D) || scratch_bytes < bcx_nuts_stream_scratch_bytes(N, D, chains, max_depth) ||
-      (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0)))) {
-    bcx_project_set_error("bcx_nuts_stream: bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, at most 256 chains, at least one "
-                          "transition, max_depth 1 .. 10, noise_ld >= D + 3 max_depth + 2 (2^max_depth - 1), eps0 > 0, ldw >= D, ldz >= D "
-                          "(Poisson: D + 1), scratch_dev of bcx_nuts_stream_scratch_bytes)");
-    return BCX_ERR_ARG;
-  }
+      (N > 0 && (!Z_dev || ldz < D + (family == LAP_POISSON ? 1 : 0))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_nuts_stream", "bad arguments (family 0 logistic / 1 Poisson, D <= ld <= 32, at most 256 chains, at least one "
+                                                    "transition, max_depth 1 .. 10, noise_ld >= D + 3 max_depth + 2 (2^max_depth - 1), eps0 > 0, ldw >= D, ldz >= D "
+                                                    "(Poisson: D + 1), scratch_dev of bcx_nuts_stream_scratch_bytes)");
   static PerDevice<int> resident_of;
   const int resident = one_wg_per_cu((const void*)nuts_stream_kernel, NS_THREADS, resident_of);
-  if (resident < 1) {
-    bcx_project_set_error("bcx_nuts_stream: the kernel's workgroups cannot be resident together on this device");
-    return BCX_ERR_STATE;
-  }
+  if (resident < 1)
+    return bcx_fail(BCX_ERR_STATE, "bcx_nuts_stream", "the kernel's workgroups cannot be resident together on this device");
   const int G = std::max(1, std::min(ns_cap_wgs(N), resident));
   NsArgs a;
   a.par = hmc_par(D, mu_dev, W_dev, ldw, chains, n_warmup, n_samples, 0, eps0, fixed_eps, noise_dev, ld, samples_dev, xi_dev, prop_dev,
@@ -476,11 +472,9 @@ extern "C" int bcx_nuts_stream(void* stream, int32_t family, int64_t N, int32_t 
   a.N = N; a.ldz = ldz; a.noise_ld = noise_ld; a.family = family; a.J = max_depth; a.rec = ns_record_doubles(max_depth);
   const GridSync gs = grid_sync_at((unsigned long long*)scratch_dev, 200000000LL);      // 2 s of the 100 MHz wall clock per wait
   hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(scratch_dev, 0, NS_SYNC_BYTES, st) != hipSuccess || hipMemsetAsync(status_dev, 0, sizeof(int), st) != hipSuccess) {
-    bcx_project_set_error("bcx_nuts_stream: memset failed");
-    return BCX_ERR_HIP;
-  }
+  BCX_TRY("bcx_nuts_stream", hipMemsetAsync(scratch_dev, 0, NS_SYNC_BYTES, st));
+  BCX_TRY("bcx_nuts_stream", hipMemsetAsync(status_dev, 0, sizeof(int), st));
   hipLaunchKernelGGL(nuts_stream_kernel, dim3(G), dim3(NS_THREADS), 0, st, a, gs);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_nuts_stream: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_nuts_stream", hipGetLastError());
   return BCX_OK;
 }

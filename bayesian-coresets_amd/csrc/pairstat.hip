@@ -179,17 +179,7 @@ __global__ __launch_bounds__(256) void pair_total_kernel(const double* __restric
 // ranges of B's tiles per tile of A: the caller's count, or enough workgroups to fill the device a few times over
 static int ps_ranges(int64_t tiles_a, int64_t tiles_b, int splits) {
   if (splits > 0) return splits;
-  static PerDevice<int> cus_of;
-  std::atomic<int>& slot = cus_of.of[device_slot_or_zero()];
-  int cus = slot.load(std::memory_order_acquire);
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-    slot.store(cus, std::memory_order_release);
-  }
+  const int cus = cu_count();
   int64_t want = ((int64_t)8 * cus + tiles_a - 1) / tiles_a;
   if (want > tiles_b) want = tiles_b;
   if (want > PS_MAX_SPLITS) want = PS_MAX_SPLITS;
@@ -211,12 +201,10 @@ extern "C" int bcx_pair_stat(void* stream, int32_t kind, const void* A_dev, int6
   if (sym) { nB = 0; ldb = lda; ldgb = ldga; }
   if ((kind != 0 && kind != 1) || !ps_shape_ok(nA, nB, D, splits) || !A_dev || lda < D || (!sym && (nB < 1 || ldb < D)) ||
       (kind == 1 && (!GA_dev || ldga < D || !(c > 0.0) || !(c < INFINITY) || (!sym && (!GB_dev || ldgb < D)))) || !out_dev || !work_dev ||
-      work_bytes < bcx_pair_stat_scratch_bytes(nA, nB, D, splits)) {
-    bcx_project_set_error("bcx_pair_stat: bad arguments (kind 0 distances / 1 Stein terms, 1 <= rows <= 2^20 a side, 1 <= D <= 32, row "
-                          "strides >= D, scores and a finite c > 0 for kind 1, 0 <= splits <= 1024, work_dev of "
-                          "bcx_pair_stat_scratch_bytes)");
-    return BCX_ERR_ARG;
-  }
+      work_bytes < bcx_pair_stat_scratch_bytes(nA, nB, D, splits))
+    return bcx_fail(BCX_ERR_ARG, "bcx_pair_stat", "bad arguments (kind 0 distances / 1 Stein terms, 1 <= rows <= 2^20 a side, 1 <= D <= 32, row "
+                                                  "strides >= D, scores and a finite c > 0 for kind 1, 0 <= splits <= 1024, work_dev of "
+                                                  "bcx_pair_stat_scratch_bytes)");
   hipStream_t st = (hipStream_t)stream;
   PairArgs a;
   a.A = (const double*)A_dev; a.GA = (const double*)GA_dev; a.nA = nA; a.lda = lda; a.ldga = ldga;
@@ -228,6 +216,6 @@ extern "C" int bcx_pair_stat(void* stream, int32_t kind, const void* A_dev, int6
   if (kind == 1) hipLaunchKernelGGL(pair_tiles_kernel<1>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(pair_tiles_kernel<0>, grid, dim3(256), 0, st, a);
   hipLaunchKernelGGL(pair_total_kernel, dim3(1), dim3(256), 0, st, (const double*)work_dev, tiles_a * (int64_t)a.ranges, (double*)out_dev);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_pair_stat: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_pair_stat", hipGetLastError());
   return BCX_OK;
 }

@@ -182,17 +182,7 @@ __global__ __launch_bounds__(256) void pred_combine_kernel(const double* __restr
 // PRED_MIN_RANGE draws
 static int pred_splits(int64_t N, int64_t S, int splits) {
   if (splits > 0) return splits;
-  static PerDevice<int> cus_of;
-  std::atomic<int>& slot = cus_of.of[device_slot_or_zero()];
-  int cus = slot.load(std::memory_order_acquire);
-  if (cus == 0) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1) {
-      (void)hipGetLastError();
-      cus = 256;
-    }
-    slot.store(cus, std::memory_order_release);
-  }
+  const int cus = cu_count();
   const int64_t tiles = (N + PRED_ROWS - 1) / PRED_ROWS;
   if (tiles < 1) return 1;
   int64_t want = ((int64_t)8 * cus + tiles - 1) / tiles;
@@ -214,22 +204,20 @@ extern "C" int bcx_log_predictive(void* stream, int32_t family, const void* Z_de
                                   void* work_dev, int64_t work_bytes) {
   if ((family != LAP_LOGISTIC && family != LAP_POISSON) || !pred_shape_ok(N, D, S, splits) || ldt < D || !Theta_dev ||
       (N > 0 && (!Z_dev || !lppd_dev || !work_dev || ldz < D + (family == LAP_POISSON ? 1 : 0) ||
-                 work_bytes < bcx_log_predictive_scratch_bytes(N, D, S, splits)))) {
-    bcx_project_set_error("bcx_log_predictive: bad arguments (family 0 logistic / 1 Poisson, 1 <= D <= 32, S >= 1, ldt >= D, 0 <= splits <= "
-                          "4096, work_dev of bcx_log_predictive_scratch_bytes)");
-    return BCX_ERR_ARG;
-  }
+                 work_bytes < bcx_log_predictive_scratch_bytes(N, D, S, splits))))
+    return bcx_fail(BCX_ERR_ARG, "bcx_log_predictive", "bad arguments (family 0 logistic / 1 Poisson, 1 <= D <= 32, S >= 1, ldt >= D, 0 <= splits <= "
+                                                       "4096, work_dev of bcx_log_predictive_scratch_bytes)");
   if (N == 0) return BCX_OK;
   hipStream_t st = (hipStream_t)stream;
   PredArgs a;
   a.Z = (const double*)Z_dev; a.Th = (const double*)Theta_dev; a.rec = (double*)work_dev;
-  if (!(a.tab = proj_tables())) { bcx_project_set_error("bcx_log_predictive: no device memory for the likelihood tables"); return BCX_ERR_NOMEM; }
+  if (!(a.tab = proj_tables())) return bcx_fail(BCX_ERR_NOMEM, "bcx_log_predictive", "no device memory for the likelihood tables");
   a.N = N; a.ldz = ldz; a.S = S; a.ldt = ldt; a.D = D; a.splits = pred_splits(N, S, splits);
   const dim3 grid((unsigned)((N + PRED_ROWS - 1) / PRED_ROWS), (unsigned)a.splits);
   if (family == LAP_LOGISTIC) hipLaunchKernelGGL(pred_rows_kernel<LAP_LOGISTIC>, grid, dim3(256), 0, st, a);
   else hipLaunchKernelGGL(pred_rows_kernel<LAP_POISSON>, grid, dim3(256), 0, st, a);
   hipLaunchKernelGGL(pred_combine_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const double*)work_dev, N, a.splits, S,
                      (double*)lppd_dev, (double*)mean_dev);
-  if (hipGetLastError() != hipSuccess) { bcx_project_set_error("bcx_log_predictive: launch failed"); return BCX_ERR_HIP; }
+  BCX_TRY("bcx_log_predictive", hipGetLastError());
   return BCX_OK;
 }

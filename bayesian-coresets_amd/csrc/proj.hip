@@ -23,6 +23,7 @@
 #include "dev_util.h"
 #include "proj_math.h"
 #include "moments_quad.h"
+#include "launch_host.h"
 
 enum { FAM_LOGISTIC = 0, FAM_POISSON = 1, FAM_LINREG = 2, FAM_GAUSSIAN = 3 };
 enum { PMODE_WRITE = 0, PMODE_COLSUM = 1, PMODE_SELECT = 2 };
@@ -1215,32 +1216,18 @@ __global__ __launch_bounds__(256) void select_final_kernel(const double* bv, con
 }
 
 // ---- C ABI --------------------------------------------------------------------------------------
-static thread_local std::string g_proj_err;
-extern "C" const char* bcx_project_last_error(void) { return g_proj_err.c_str(); }
-void bcx_project_set_error(const std::string& msg) { g_proj_err = msg; }   // (moments.hip reports through the same string)
-
-#define PROJ_HIP(call)                                                            \
-  do {                                                                            \
-    hipError_t _e = (call);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      g_proj_err = std::string(#call) + ": " + hipGetErrorString(_e);             \
-      return BCX_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
+extern "C" const char* bcx_project_last_error(void) { return bcx_fail_text(); }   // (host_err.h: every file's failures)
 
 // Persistent launch: as many workgroups as are resident at once (2 per CU: 64 KiB of staging LDS each), every one
 // striding over the 128-row blocks -- with more workgroups than that the last wave of blocks leaves most CUs idle.
 static int proj_grid(int64_t N) {
   // resident workgroups of the CURRENT device (looked up per device id, once; races write the same value)
-  static std::atomic<int> resident_of[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-  int resident = resident_of[dev].load(std::memory_order_relaxed);
+  static PerDevice<int> resident_of;
+  const int dev = device_slot_or_zero();
+  int resident = resident_of.of[dev].load(std::memory_order_relaxed);
   if (!resident) {
-    int cus = 0;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    resident = std::min(2 * cus, 2048);
-    resident_of[dev].store(resident, std::memory_order_relaxed);
+    resident = std::min(2 * cu_count(), 2048);
+    resident_of.of[dev].store(resident, std::memory_order_relaxed);
   }
   const int64_t blocks = (N + PJ_ROWS - 1) / PJ_ROWS;
   return (int)std::max<int64_t>(1, std::min<int64_t>(blocks, resident));
@@ -1282,22 +1269,22 @@ template <int FAM, int MODE, int NCT, bool ALIGNED_ONLY = false, bool GATHER = f
   if (timed) {
     if (g_prof.used == g_prof.ev.size()) {
       hipEvent_t a, b;
-      PROJ_HIP(hipEventCreate(&a));
-      PROJ_HIP(hipEventCreate(&b));
+      BCX_TRY("bcx_project", hipEventCreate(&a));
+      BCX_TRY("bcx_project", hipEventCreate(&b));
       g_prof.ev.emplace_back(a, b);
     }
-    PROJ_HIP(hipEventRecord(g_prof.ev[g_prof.used].first, st));
+    BCX_TRY("bcx_project", hipEventRecord(g_prof.ev[g_prof.used].first, st));
   }
 if (aligned) {
-    PROJ_HIP(hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, true, NCT, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    BCX_TRY("bcx_project", hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, true, NCT, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     hipLaunchKernelGGL((proj_kernel<FAM, MODE, true, NCT, GATHER>), grid, dim3(256), shmem, st, p);
   } else if constexpr (!ALIGNED_ONLY) {
-    PROJ_HIP(hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, false, NCT, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
+    BCX_TRY("bcx_project", hipFuncSetAttribute((const void*)proj_kernel<FAM, MODE, false, NCT, GATHER>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shmem));
     hipLaunchKernelGGL((proj_kernel<FAM, MODE, false, NCT, GATHER>), grid, dim3(256), shmem, st, p);
   }
-  PROJ_HIP(hipGetLastError());
+  BCX_TRY("bcx_project", hipGetLastError());
   if (timed) {
-    PROJ_HIP(hipEventRecord(g_prof.ev[g_prof.used].second, st));
+    BCX_TRY("bcx_project", hipEventRecord(g_prof.ev[g_prof.used].second, st));
     g_prof.used++;
     g_prof.flops += 2.0 * (double)p.N * p.D * p.S;
   }
@@ -1315,8 +1302,8 @@ extern "C" int bcx_project_profile(int32_t on) {
 extern "C" int bcx_project_profile_read(double* ms_total, int64_t* launches, double* flops) {
   for (size_t i = 0; i < g_prof.used; ++i) {
     float ms = 0.f;
-    PROJ_HIP(hipEventSynchronize(g_prof.ev[i].second));
-    PROJ_HIP(hipEventElapsedTime(&ms, g_prof.ev[i].first, g_prof.ev[i].second));
+    BCX_TRY("bcx_project_profile_read", hipEventSynchronize(g_prof.ev[i].second));
+    BCX_TRY("bcx_project_profile_read", hipEventElapsedTime(&ms, g_prof.ev[i].first, g_prof.ev[i].second));
     g_prof.ms += ms;
     g_prof.launches++;
   }
@@ -1398,8 +1385,8 @@ template <int MODE, bool GATHER = false> static int launch_family(int family, di
   const int nct = proj_nct(MODE, family, p.S, proj_aligned(p), p.D);
   const size_t tab_bytes = family == FAM_POISSON ? PJT_BYTES(PJT_DOUBLES) : family == FAM_LOGISTIC ? PJT_BYTES(PJT_DOUBLES_LOGISTIC) : 0;
   const size_t shmem = (nct == 8 ? PJ_STAGING_BYTES(8) : PJ_STAGING_BYTES(4)) + extra_lds + tab_bytes;
-  if (tab_bytes && !(p.tab = proj_tables())) { g_proj_err = "bcx_project: no device memory for the likelihood tables"; return BCX_ERR_NOMEM; }
-  if (shmem > 160 * 1024) { g_proj_err = "bcx_project: S too large for the column-sum accumulators (S <= 3072)"; return BCX_ERR_ARG; }
+  if (tab_bytes && !(p.tab = proj_tables())) return bcx_fail(BCX_ERR_NOMEM, "bcx_project", "no device memory for the likelihood tables");
+  if (shmem > 160 * 1024) return bcx_fail(BCX_ERR_ARG, "bcx_project", "S too large for the column-sum accumulators (S <= 3072)");
   const bool aligned = proj_aligned(p);
   if constexpr (MODE == PMODE_SELECT) {
     if (nct == 8 && family == FAM_LINREG) return launch_one<FAM_LINREG, MODE, 8, true, GATHER>(true, grid, shmem, st, p);
@@ -1421,7 +1408,7 @@ template <int MODE, bool GATHER = false> static int launch_family(int family, di
     case FAM_POISSON: return launch_one<FAM_POISSON, MODE, 4, false, GATHER>(aligned, grid, shmem, st, p);
     case FAM_LINREG: return launch_one<FAM_LINREG, MODE, 4, false, GATHER>(aligned, grid, shmem, st, p);
     case FAM_GAUSSIAN: return launch_one<FAM_GAUSSIAN, MODE, 4, false, GATHER>(aligned, grid, shmem, st, p);
-    default: g_proj_err = "unknown likelihood family"; return BCX_ERR_ARG;
+    default: return bcx_fail(BCX_ERR_ARG, "bcx_project", "unknown likelihood family");   // (fill() has refused it)
   }
 }
 
@@ -1429,16 +1416,13 @@ static int fill(ProjArgs& p, int family, const void* Z, int64_t N, int64_t ldz, 
                 int S, int ldt, double param) {
   if (!Z || !theta || N < 0 || D < 1 || S < 1 || ldz < D || ldt < D || S > 4096 || (int64_t)(S + 128) * ldt >= (int64_t)1 << 31) {
     // (the kernel forms Theta offsets (column) * ldt in 32 bits, columns up to S rounded to the tile width)
-    g_proj_err = "bcx_project: bad arguments";
-    return BCX_ERR_ARG;
+    return bcx_fail(BCX_ERR_ARG, "bcx_project", "bad arguments");
   }
-  if (family < FAM_LOGISTIC || family > FAM_GAUSSIAN) { g_proj_err = "bcx_project: unknown likelihood family"; return BCX_ERR_ARG; }
+  if (family < FAM_LOGISTIC || family > FAM_GAUSSIAN) return bcx_fail(BCX_ERR_ARG, "bcx_project", "unknown likelihood family");
   const bool has_y = family == FAM_POISSON || family == FAM_LINREG;
-  if (has_y && (ycol < 0 || ycol >= ldz)) { g_proj_err = "bcx_project: response column required"; return BCX_ERR_ARG; }
-  if (family == FAM_GAUSSIAN && ldt < D + 1) {
-    g_proj_err = "bcx_project: family 3 takes the S x (D + 1) operand of bcx_gaussian_operand (ldt >= D + 1)";
-    return BCX_ERR_ARG;
-  }
+  if (has_y && (ycol < 0 || ycol >= ldz)) return bcx_fail(BCX_ERR_ARG, "bcx_project", "response column required");
+  if (family == FAM_GAUSSIAN && ldt < D + 1)
+    return bcx_fail(BCX_ERR_ARG, "bcx_project", "family 3 takes the S x (D + 1) operand of bcx_gaussian_operand (ldt >= D + 1)");
   p.Z = (const double*)Z; p.theta = (const double*)theta; p.N = N; p.ldz = ldz; p.ldt = ldt; p.D = D; p.S = S;
   p.ycol = has_y ? ycol : -1; p.param = param;
   p.out = nullptr; p.ldo = 0; p.rowsum = nullptr; p.colpart = nullptr; p.resid = nullptr; p.resid_sum = 0.0;
@@ -1453,7 +1437,7 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
   ProjArgs p;
   int rc = fill(p, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param);
   if (rc) return rc;
-  if (!out_dev || ldo < S) { g_proj_err = "bcx_project_write: bad output"; return BCX_ERR_ARG; }
+  if (!out_dev || ldo < S) return bcx_fail(BCX_ERR_ARG, "bcx_project_write", "bad output");
   if (N == 0) return BCX_OK;
   p.out = (double*)out_dev; p.ldo = ldo; p.rowsum = (double*)rowsum_dev;
   hipStream_t st = (hipStream_t)stream;
@@ -1461,7 +1445,7 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
   if (N <= PJ_SMALL_ROWS && S <= 1024 && D <= 4096 && !no_small) {
     // a handful of rows: one workgroup per row, likelihood and centring in the same launch (proj_small_kernel)
     const size_t tabd = family == FAM_POISSON ? PJT_DOUBLES : family == FAM_LOGISTIC ? PJT_DOUBLES_LOGISTIC : 0;
-    if (tabd && !(p.tab = proj_tables())) { g_proj_err = "bcx_project: no device memory for the likelihood tables"; return BCX_ERR_NOMEM; }
+    if (tabd && !(p.tab = proj_tables())) return bcx_fail(BCX_ERR_NOMEM, "bcx_project", "no device memory for the likelihood tables");
     const size_t lds = ((size_t)((D + 1) & ~1) + tabd) * sizeof(double);
     const bool al = ((uintptr_t)p.theta % 16 == 0) && p.ldt % 2 == 0;
     const int cen = center ? 1 : 0;
@@ -1475,7 +1459,7 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
     if (family == FAM_LOGISTIC) PJ_SMALL(FAM_LOGISTIC); else if (family == FAM_POISSON) PJ_SMALL(FAM_POISSON);
     else if (family == FAM_GAUSSIAN) PJ_SMALL(FAM_GAUSSIAN); else PJ_SMALL(FAM_LINREG);
 #undef PJ_SMALL
-    PROJ_HIP(hipGetLastError());
+    BCX_TRY("bcx_project_write", hipGetLastError());
     return BCX_OK;
   }
   static const bool no_mid = bcx_dev_env("BCX_PROJ_NO_MID") != nullptr;        // dev: the tiled kernel beyond 32 rows
@@ -1483,7 +1467,7 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
     // a few hundred rows that every shard projects alike (the coreset points): 32 x 32 blocks of the product straight from
     // L2-resident operands (proj_mid_kernel)
     const size_t tabd = family == FAM_POISSON ? PJT_DOUBLES : family == FAM_LOGISTIC ? PJT_DOUBLES_LOGISTIC : 0;
-    if (tabd && !(p.tab = proj_tables())) { g_proj_err = "bcx_project: no device memory for the likelihood tables"; return BCX_ERR_NOMEM; }
+    if (tabd && !(p.tab = proj_tables())) return bcx_fail(BCX_ERR_NOMEM, "bcx_project", "no device memory for the likelihood tables");
     const bool al = ((uintptr_t)p.theta % 16 == 0) && p.ldt % 2 == 0 && ((uintptr_t)p.Z % 16 == 0) && p.ldz % 2 == 0;
     const dim3 mgrid((unsigned)((N + 31) / 32), (unsigned)((S + 31) / 32));
 #define PJ_MID(F)                                                                                                     \
@@ -1494,7 +1478,7 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
     if (family == FAM_LOGISTIC) PJ_MID(FAM_LOGISTIC); else if (family == FAM_POISSON) PJ_MID(FAM_POISSON);
     else if (family == FAM_GAUSSIAN) PJ_MID(FAM_GAUSSIAN); else PJ_MID(FAM_LINREG);
 #undef PJ_MID
-    PROJ_HIP(hipGetLastError());
+    BCX_TRY("bcx_project_write", hipGetLastError());
   } else {
     int wgrid = 0;
     proj_plan(PMODE_WRITE, family, N, S, proj_aligned(p), D, &wgrid, &p.team);
@@ -1506,7 +1490,7 @@ static int project_write(void* stream, int32_t family, const void* Z_dev, int64_
     hipLaunchKernelGGL(center_kernel<true>, dim3(g), dim3(256), 0, st, p.out, ldo, N, S);
   else
     hipLaunchKernelGGL(center_kernel<false>, dim3(g), dim3(256), 0, st, p.out, ldo, N, S);
-  PROJ_HIP(hipGetLastError());
+  BCX_TRY("bcx_project_write", hipGetLastError());
   return BCX_OK;
 }
 
@@ -1550,11 +1534,9 @@ extern "C" int bcx_project_points_colsum_moments(void* stream, const void* Zc_de
   ProjArgs p;
   int rc = fill(p, FAM_LINREG, Zc_dev, Nc, ldzc, D, ycol, theta_dev, S, ldt, sigsq);
   if (rc) return rc;
-  if (!out_dev || ldo < S) { g_proj_err = "bcx_project_points_colsum_moments: bad output"; return BCX_ERR_ARG; }
-  if (!M_dev || !colsum_dev || !work_dev || D >= 1024 || ycol_m < 0 || ycol_m >= ldm || ldm < D) {
-    g_proj_err = "bcx_project_points_colsum_moments: bad arguments (the moments of bcx_project_moments, D < 1024)";
-    return BCX_ERR_ARG;
-  }
+  if (!out_dev || ldo < S) return bcx_fail(BCX_ERR_ARG, "bcx_project_points_colsum_moments", "bad output");
+  if (!M_dev || !colsum_dev || !work_dev || D >= 1024 || ycol_m < 0 || ycol_m >= ldm || ldm < D)
+    return bcx_fail(BCX_ERR_ARG, "bcx_project_points_colsum_moments", "bad arguments (the moments of bcx_project_moments, D < 1024)");
   p.out = (double*)out_dev; p.ldo = ldo; p.rowsum = nullptr;
   MqArgs q;
   mq_plan(D, S, &q.nct, &q.Spad);
@@ -1569,7 +1551,7 @@ extern "C" int bcx_project_points_colsum_moments(void* stream, const void* Zc_de
   if (alp) hipLaunchKernelGGL((proj_mid_quad_kernel<true, true>), grid, dim3(256), 0, st, p, q, nq, gx);
   else if (alq) hipLaunchKernelGGL((proj_mid_quad_kernel<false, true>), grid, dim3(256), 0, st, p, q, nq, gx);
   else hipLaunchKernelGGL((proj_mid_quad_kernel<false, false>), grid, dim3(256), 0, st, p, q, nq, gx);
-  PROJ_HIP(hipGetLastError());
+  BCX_TRY("bcx_project_points_colsum_moments", hipGetLastError());
   return BCX_OK;
 }
 
@@ -1577,12 +1559,10 @@ extern "C" int bcx_project_points_colsum_moments(void* stream, const void* Zc_de
 // offset from Z itself, in 16-byte units where the rows are 16-byte aligned and in elements otherwise: a matrix beyond that
 // reach (64 GiB / 32 GiB) is refused -- the caller gathers with bcx_gather_rows and takes the contiguous entry.
 static int rows_check(const ProjArgs& p, const void* rows_dev, int64_t n_rows, int64_t N, const char* who) {
-  if (N < 0 || (n_rows > 0 && (!rows_dev || N < 1))) { g_proj_err = std::string(who) + ": bad index table"; return BCX_ERR_ARG; }
+  if (N < 0 || (n_rows > 0 && (!rows_dev || N < 1))) return bcx_fail(BCX_ERR_ARG, who, "bad index table");
   const int64_t last = N > 0 ? (N - 1) * p.ldz : 0;
-  if ((proj_aligned(p) ? last >> 1 : last) > (int64_t)0xffffffffLL) {
-    g_proj_err = std::string(who) + ": the matrix is beyond the 32-bit reach of the gathered requests (bcx_gather_rows + the contiguous entry)";
-    return BCX_ERR_ARG;
-  }
+  if ((proj_aligned(p) ? last >> 1 : last) > (int64_t)0xffffffffLL)
+    return bcx_fail(BCX_ERR_ARG, who, "the matrix is beyond the 32-bit reach of the gathered requests (bcx_gather_rows + the contiguous entry)");
   return BCX_OK;
 }
 
@@ -1593,7 +1573,7 @@ static int project_colsum(void* stream, int32_t family, const void* Z_dev, int64
   ProjArgs p;
   int rc = fill(p, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param);
   if (rc) return rc;
-  if (!colsum_dev || !work_dev) { g_proj_err = "bcx_project_colsum: bad output"; return BCX_ERR_ARG; }
+  if (!colsum_dev || !work_dev) return bcx_fail(BCX_ERR_ARG, "bcx_project_colsum", "bad output");
   if (gather && (rc = rows_check(p, rows_dev, N, n_total, "bcx_project_colsum_rows"))) return rc;
   p.rows = (const int64_t*)rows_dev;
   hipStream_t st = (hipStream_t)stream;
@@ -1606,7 +1586,7 @@ static int project_colsum(void* stream, int32_t family, const void* Z_dev, int64
   if (rc) return rc;
   hipLaunchKernelGGL(colsum_reduce_kernel, dim3((S + 63) / 64), dim3(256), 0, st, p.colpart, grid, S, (double*)colsum_dev);
   hipLaunchKernelGGL(colsum_center_kernel, dim3(1), dim3(256), 0, st, S, (double*)colsum_dev);
-  PROJ_HIP(hipGetLastError());
+  BCX_TRY("bcx_project_colsum", hipGetLastError());
   return BCX_OK;
 }
 
@@ -1642,7 +1622,7 @@ static int project_select(void* stream, int32_t family, const void* Z_dev, int64
   ProjArgs p;
   int rc = fill(p, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param);
   if (rc) return rc;
-  if (!resid_dev || !result_dev || !work_dev) { g_proj_err = "bcx_project_select: bad output"; return BCX_ERR_ARG; }
+  if (!resid_dev || !result_dev || !work_dev) return bcx_fail(BCX_ERR_ARG, "bcx_project_select", "bad output");
   if (gather && (rc = rows_check(p, rows_dev, N, n_total, "bcx_project_select_rows_ws"))) return rc;
   p.rows = (const int64_t*)rows_dev;
   hipStream_t st = (hipStream_t)stream;
@@ -1661,8 +1641,7 @@ static int project_select(void* stream, int32_t family, const void* Z_dev, int64
     // framework's allocator -- bcx_project_select_ws)
     if (hipMallocAsync(&part, (size_t)ngc * (size_t)N * 4 * sizeof(double), st) != hipSuccess) {
       (void)hipGetLastError();
-      g_proj_err = "bcx_project_select: no scratch for the row moments (" + std::to_string((size_t)ngc * (size_t)N * 32) + " bytes)";
-      return BCX_ERR_NOMEM;
+      return bcx_fail(BCX_ERR_NOMEM, "bcx_project_select", "no scratch for the row moments (" + std::to_string((size_t)ngc * (size_t)N * 32) + " bytes)");
     }
     own = true;
   }
@@ -1676,8 +1655,8 @@ static int project_select(void* stream, int32_t family, const void* Z_dev, int64
                      p.best_idx);
   hipLaunchKernelGGL(select_final_kernel, dim3(1), dim3(256), 0, st, p.best_val, p.best_idx, nparts, (double*)result_dev,
                      (int64_t*)((double*)result_dev + 1));
-  PROJ_HIP(hipGetLastError());
-  if (own) PROJ_HIP(hipFreeAsync(part, st));
+  BCX_TRY("bcx_project_select", hipGetLastError());
+  if (own) BCX_TRY("bcx_project_select", hipFreeAsync(part, st));
   return BCX_OK;
 }
 
@@ -1693,7 +1672,7 @@ extern "C" int bcx_project_select(void* stream, int32_t family, const void* Z_de
 extern "C" int bcx_project_select_ws(void* stream, int32_t family, const void* Z_dev, int64_t N, int64_t ldz, int32_t D,
                                      int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
                                      const void* resid_dev, double resid_sum, void* result_dev, void* work_dev, int64_t work_bytes) {
-  if (work_bytes < bcx_project_select_scratch_bytes(family, N, S)) { g_proj_err = "bcx_project_select_ws: scratch too small"; return BCX_ERR_ARG; }
+  if (work_bytes < bcx_project_select_scratch_bytes(family, N, S)) return bcx_fail(BCX_ERR_ARG, "bcx_project_select_ws", "scratch too small");
   return project_select(stream, family, Z_dev, N, ldz, D, ycol, theta_dev, S, ldt, param, resid_dev, resid_sum, result_dev, work_dev,
                         work_dev ? (char*)work_dev + 4096 * sizeof(double) : nullptr);
 }
@@ -1708,10 +1687,8 @@ extern "C" int bcx_project_select_rows_ws(void* stream, int32_t family, const vo
                                           int32_t ycol, const void* theta_dev, int32_t S, int32_t ldt, double param,
                                           const void* rows_dev, int64_t n_rows, const void* resid_dev, double resid_sum,
                                           void* result_dev, void* work_dev, int64_t work_bytes) {
-  if (n_rows < 0 || work_bytes < bcx_project_select_rows_scratch_bytes(family, n_rows, S)) {
-    g_proj_err = "bcx_project_select_rows_ws: scratch too small";
-    return BCX_ERR_ARG;
-  }
+  if (n_rows < 0 || work_bytes < bcx_project_select_rows_scratch_bytes(family, n_rows, S))
+    return bcx_fail(BCX_ERR_ARG, "bcx_project_select_rows_ws", "scratch too small");
   return project_select(stream, family, Z_dev, n_rows, ldz, D, ycol, theta_dev, S, ldt, param, resid_dev, resid_sum, result_dev, work_dev,
                         work_dev ? (char*)work_dev + 4096 * sizeof(double) : nullptr, rows_dev, N, true);
 }
@@ -1738,10 +1715,8 @@ __global__ __launch_bounds__(256) void gather_rows_kernel(const double* Z, int64
 }
 extern "C" int bcx_gather_rows(void* stream, const void* Z_dev, int64_t ldz, int32_t C, const void* rows_dev, int64_t n_rows,
                                void* out_dev, int64_t ldo) {
-  if (n_rows < 0 || C < 1 || ldz < C || ldo < C || (n_rows > 0 && (!Z_dev || !rows_dev || !out_dev))) {
-    g_proj_err = "bcx_gather_rows: bad arguments";
-    return BCX_ERR_ARG;
-  }
+  if (n_rows < 0 || C < 1 || ldz < C || ldo < C || (n_rows > 0 && (!Z_dev || !rows_dev || !out_dev)))
+    return bcx_fail(BCX_ERR_ARG, "bcx_gather_rows", "bad arguments");
   if (n_rows == 0) return BCX_OK;
   const bool vec = (uintptr_t)Z_dev % 16 == 0 && (uintptr_t)out_dev % 16 == 0 && ldz % 2 == 0 && ldo % 2 == 0;
   const int64_t total = n_rows * (vec ? (C + 1) / 2 : C);
@@ -1750,14 +1725,14 @@ extern "C" int bcx_gather_rows(void* stream, const void* Z_dev, int64_t ldz, int
                               (const int64_t*)rows_dev, n_rows, (double*)out_dev, ldo);
   else hipLaunchKernelGGL(gather_rows_kernel<false>, dim3(g), dim3(256), 0, (hipStream_t)stream, (const double*)Z_dev, ldz, (int)C,
                           (const int64_t*)rows_dev, n_rows, (double*)out_dev, ldo);
-  PROJ_HIP(hipGetLastError());
+  BCX_TRY("bcx_gather_rows", hipGetLastError());
   return BCX_OK;
 }
 
 // rows_dev (N x ld doubles, S used per row) -= its row means, in place: projector.py:21 for rows that were written raw
 // (the same kernel bcx_project_write centres with).
 extern "C" int bcx_center_rows(void* stream, void* rows_dev, int64_t N, int32_t S, int64_t ld) {
-  if (!rows_dev || N < 0 || S < 1 || ld < S) { g_proj_err = "bcx_center_rows: bad arguments"; return BCX_ERR_ARG; }
+  if (!rows_dev || N < 0 || S < 1 || ld < S) return bcx_fail(BCX_ERR_ARG, "bcx_center_rows", "bad arguments");
   if (N == 0) return BCX_OK;
   hipStream_t st = (hipStream_t)stream;
   const int g = (int)std::min<int64_t>((N + 3) / 4, 8192);
@@ -1765,15 +1740,15 @@ extern "C" int bcx_center_rows(void* stream, void* rows_dev, int64_t N, int32_t 
     hipLaunchKernelGGL(center_kernel<true>, dim3(g), dim3(256), 0, st, (double*)rows_dev, ld, N, (int)S);
   else
     hipLaunchKernelGGL(center_kernel<false>, dim3(g), dim3(256), 0, st, (double*)rows_dev, ld, N, (int)S);
-  PROJ_HIP(hipGetLastError());
+  BCX_TRY("bcx_center_rows", hipGetLastError());
   return BCX_OK;
 }
 // out_dev[n] = sum of squares of row n of rows_dev (N x ld doubles, S used per row): hilbert.py:19-22 drops the rows where it is 0.
 extern "C" int bcx_row_sumsq(void* stream, const void* rows_dev, int64_t N, int32_t S, int64_t ld, void* out_dev) {
-  if (!rows_dev || !out_dev || N < 0 || S < 1 || ld < S) { g_proj_err = "bcx_row_sumsq: bad arguments"; return BCX_ERR_ARG; }
+  if (!rows_dev || !out_dev || N < 0 || S < 1 || ld < S) return bcx_fail(BCX_ERR_ARG, "bcx_row_sumsq", "bad arguments");
   if (N == 0) return BCX_OK;
   const int g = (int)std::min<int64_t>((N + 3) / 4, 8192);
   hipLaunchKernelGGL(row_sumsq_kernel, dim3(g), dim3(256), 0, (hipStream_t)stream, (const double*)rows_dev, ld, N, (int)S, (double*)out_dev);
-  PROJ_HIP(hipGetLastError());
+  BCX_TRY("bcx_row_sumsq", hipGetLastError());
   return BCX_OK;
 }

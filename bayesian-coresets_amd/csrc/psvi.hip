@@ -32,6 +32,7 @@
 #include <string>
 #include "bcx_internal.h"
 #include "dev_util.h"
+#include "launch_host.h"
 
 enum { PS_LOGISTIC = 0, PS_POISSON = 1, PS_LINREG = 2, PS_GAUSSIAN = 3 };
 
@@ -188,37 +189,23 @@ __global__ __launch_bounds__(256) void psvi_gwrite_kernel(const double* __restri
 }
 
 // ---- host side ----------------------------------------------------------------------------------------------------------------
-#define PS_HIP(call)                                                              \
-  do {                                                                            \
-    hipError_t _e = (call);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      bcx_project_set_error(std::string(#call) + ": " + hipGetErrorString(_e));   \
-      return BCX_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
-
-static int ps_arg_error(const char* who, const char* what) {
-  bcx_project_set_error(std::string(who) + ": " + what);
-  return BCX_ERR_ARG;
-}
-
 // the checks both entries share; *dz: the length of a gradient row
 static int ps_check(const char* who, int32_t family, const void* P, int32_t k, int64_t ldp, int32_t D, int32_t ycol,
                     const void* theta, int32_t S, int64_t ldt, double param, const void* work, int* dz) {
-  if (family == PS_GAUSSIAN) return ps_arg_error(who, "family 3 (Gaussian mean) has entry points of its own: bcx_project_grad_points_gaussian / bcx_psvi_gradient_gaussian");
-  if (family < PS_LOGISTIC || family > PS_LINREG) return ps_arg_error(who, "unknown likelihood family");
-  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return ps_arg_error(who, "k (pseudo-points) must be in 1 .. 4096");
-  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return ps_arg_error(who, "S (samples) must be in 1 .. 8192");
-  if (D < 1 || D > BCX_PSVI_MAX_DIM) return ps_arg_error(who, "D (features) must be in 1 .. 1024");
-  if (!P || !theta || !work) return ps_arg_error(who, "null pointer");
-  if (ldp < D || ldt < D) return ps_arg_error(who, "leading dimension shorter than D");
-  if (family != PS_LOGISTIC && (ycol < 0 || ycol >= ldp)) return ps_arg_error(who, "response column required");
-  if (family == PS_LINREG && !(param != 0.0)) return ps_arg_error(who, "sigsq must be non-zero");
+  if (family == PS_GAUSSIAN) return bcx_fail(BCX_ERR_ARG, who, "family 3 (Gaussian mean) has entry points of its own: bcx_project_grad_points_gaussian / bcx_psvi_gradient_gaussian");
+  if (family < PS_LOGISTIC || family > PS_LINREG) return bcx_fail(BCX_ERR_ARG, who, "unknown likelihood family");
+  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return bcx_fail(BCX_ERR_ARG, who, "k (pseudo-points) must be in 1 .. 4096");
+  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return bcx_fail(BCX_ERR_ARG, who, "S (samples) must be in 1 .. 8192");
+  if (D < 1 || D > BCX_PSVI_MAX_DIM) return bcx_fail(BCX_ERR_ARG, who, "D (features) must be in 1 .. 1024");
+  if (!P || !theta || !work) return bcx_fail(BCX_ERR_ARG, who, "null pointer");
+  if (ldp < D || ldt < D) return bcx_fail(BCX_ERR_ARG, who, "leading dimension shorter than D");
+  if (family != PS_LOGISTIC && (ycol < 0 || ycol >= ldp)) return bcx_fail(BCX_ERR_ARG, who, "response column required");
+  if (family == PS_LINREG && !(param != 0.0)) return bcx_fail(BCX_ERR_ARG, who, "sigsq must be non-zero");
   *dz = family == PS_LINREG ? D + 1 : D;
   return BCX_OK;
 }
 
-static int ps_coef(hipStream_t st, int32_t family, const double* P, int k, int64_t ldp, int D, int ycol, const double* theta, int S,
+static int ps_coef(const char* who, hipStream_t st, int32_t family, const double* P, int k, int64_t ldp, int D, int ycol, const double* theta, int S,
                    int64_t ldt, double param, const double* resid, double* C) {
   const dim3 grid((k + 31) / 32, (S + 31) / 32);
   const double rsig = family == PS_LINREG ? 1.0 / param : 0.0;
@@ -228,7 +215,7 @@ static int ps_coef(hipStream_t st, int32_t family, const double* P, int k, int64
     hipLaunchKernelGGL(psvi_coef_kernel<PS_POISSON>, grid, dim3(256), 0, st, P, k, ldp, D, ycol, theta, S, ldt, rsig, resid, C);
   else
     hipLaunchKernelGGL(psvi_coef_kernel<PS_LINREG>, grid, dim3(256), 0, st, P, k, ldp, D, ycol, theta, S, ldt, rsig, resid, C);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -244,7 +231,7 @@ extern "C" int bcx_project_grad_points(void* stream, int32_t family, const void*
   int dz = 0;
   int rc = ps_check(who, family, P_dev, k, ldp, D, ycol, theta_dev, S, ldt, param, work_dev, &dz);
   if (rc) return rc;
-  if (!glls_dev) return ps_arg_error(who, "null output");
+  if (!glls_dev) return bcx_fail(BCX_ERR_ARG, who, "null output");
   hipStream_t st = (hipStream_t)stream;
   const double* P = (const double*)P_dev;
   const double* theta = (const double*)theta_dev;
@@ -252,8 +239,8 @@ extern "C" int bcx_project_grad_points(void* stream, int32_t family, const void*
   double* tmean = C + (int64_t)k * S;
   hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)nullptr, 0.0,
                      (const double*)nullptr, (int64_t)0, (const double*)nullptr, (double*)nullptr, theta, (int64_t)ldt, D, dz, tmean);
-  PS_HIP(hipGetLastError());
-  rc = ps_coef(st, family, P, k, ldp, D, ycol, theta, S, ldt, param, nullptr, C);
+  BCX_TRY(who, hipGetLastError());
+  rc = ps_coef(who, st, family, P, k, ldp, D, ycol, theta, S, ldt, param, nullptr, C);
   if (rc) return rc;
   const int64_t total = (int64_t)k * S * dz;
   const int64_t want = (total + 255) / 256;
@@ -264,7 +251,7 @@ extern "C" int bcx_project_grad_points(void* stream, int32_t family, const void*
   else
     hipLaunchKernelGGL(psvi_gwrite_kernel<false>, dim3(blocks), dim3(256), 0, st, C, S, theta, (int64_t)ldt, D, dz, tmean,
                        (double*)glls_dev, total);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -276,8 +263,8 @@ extern "C" int bcx_psvi_gradient(void* stream, int32_t family, const void* P_dev
   int dz = 0;
   int rc = ps_check(who, family, P_dev, k, ldp, D, ycol, theta_dev, S, ldt, param, work_dev, &dz);
   if (rc) return rc;
-  if (!colsum_dev || !corevecs_dev || !w_dev || !out_dev) return ps_arg_error(who, "null pointer");
-  if (ldcv < S) return ps_arg_error(who, "corevecs leading dimension shorter than S");
+  if (!colsum_dev || !corevecs_dev || !w_dev || !out_dev) return bcx_fail(BCX_ERR_ARG, who, "null pointer");
+  if (ldcv < S) return bcx_fail(BCX_ERR_ARG, who, "corevecs leading dimension shorter than S");
   hipStream_t st = (hipStream_t)stream;
   const double* P = (const double*)P_dev;
   const double* theta = (const double*)theta_dev;
@@ -290,10 +277,10 @@ extern "C" int bcx_psvi_gradient(void* stream, int32_t family, const void* P_dev
   double* tmean = A + (int64_t)k * S;
   hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)colsum_dev, scaling, cv, ldcv, w,
                      resid, theta, (int64_t)ldt, D, dz, tmean);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   hipLaunchKernelGGL(psvi_wgrad_kernel, dim3(k), dim3(256), 0, st, S, cv, ldcv, (const double*)resid, wgrad);
-  PS_HIP(hipGetLastError());
-  rc = ps_coef(st, family, P, k, ldp, D, ycol, theta, S, ldt, param, resid, A);
+  BCX_TRY(who, hipGetLastError());
+  rc = ps_coef(who, st, family, P, k, ldp, D, ycol, theta, S, ldt, param, resid, A);
   if (rc) return rc;
   const dim3 grid((k + 31) / 32, (dz + 31) / 32);
   if (family == PS_LINREG)
@@ -302,7 +289,7 @@ extern "C" int bcx_psvi_gradient(void* stream, int32_t family, const void* P_dev
   else
     hipLaunchKernelGGL(psvi_ugrad_kernel<false>, grid, dim3(256), 0, st, (const double*)A, k, S, theta, (int64_t)ldt, D, dz,
                        (const double*)tmean, w, ugrad);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -347,11 +334,11 @@ __global__ __launch_bounds__(256) void psvi_gauss_ugrad_kernel(const double* __r
 
 static int ps_gauss_check(const char* who, const void* op, int32_t S, int64_t ldt, int32_t D, const void* H, int32_t k, int64_t ldh,
                           const void* work) {
-  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return ps_arg_error(who, "k (pseudo-points) must be in 1 .. 4096");
-  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return ps_arg_error(who, "S (samples) must be in 1 .. 8192");
-  if (D < 1 || D > BCX_PSVI_MAX_DIM) return ps_arg_error(who, "D (coordinates) must be in 1 .. 1024");
-  if (!op || !H || !work) return ps_arg_error(who, "null pointer");
-  if (ldt < D + 1 || ldh < D + 1) return ps_arg_error(who, "operands of bcx_gaussian_operand required (leading dimensions >= D + 1)");
+  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return bcx_fail(BCX_ERR_ARG, who, "k (pseudo-points) must be in 1 .. 4096");
+  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return bcx_fail(BCX_ERR_ARG, who, "S (samples) must be in 1 .. 8192");
+  if (D < 1 || D > BCX_PSVI_MAX_DIM) return bcx_fail(BCX_ERR_ARG, who, "D (coordinates) must be in 1 .. 1024");
+  if (!op || !H || !work) return bcx_fail(BCX_ERR_ARG, who, "null pointer");
+  if (ldt < D + 1 || ldh < D + 1) return bcx_fail(BCX_ERR_ARG, who, "operands of bcx_gaussian_operand required (leading dimensions >= D + 1)");
   return BCX_OK;
 }
 
@@ -360,19 +347,19 @@ extern "C" int bcx_project_grad_points_gaussian(void* stream, const void* operan
   static const char* who = "bcx_project_grad_points_gaussian";
   int rc = ps_gauss_check(who, operand_dev, S, ldt, D, H_dev, k, ldh, work_dev);
   if (rc) return rc;
-  if (!glls_dev) return ps_arg_error(who, "null output");
+  if (!glls_dev) return bcx_fail(BCX_ERR_ARG, who, "null output");
   hipStream_t st = (hipStream_t)stream;
   const double* op = (const double*)operand_dev;
   double* gmean = (double*)work_dev + (int64_t)k * S;       // (the place the other families keep it: same scratch size)
   hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)nullptr, 0.0,
                      (const double*)nullptr, (int64_t)0, (const double*)nullptr, (double*)nullptr, op, ldt, D, D, gmean);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   const int64_t total = (int64_t)k * S * D;
   const int64_t want = (total + 255) / 256;
   const int blocks = (int)(want < 8192 ? want : 8192);
   hipLaunchKernelGGL(psvi_gauss_gwrite_kernel, dim3(blocks), dim3(256), 0, st, op, ldt, (const double*)gmean, (const double*)H_dev, ldh,
                      (int)S, (int)D, (double*)glls_dev, total);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -382,8 +369,8 @@ extern "C" int bcx_psvi_gradient_gaussian(void* stream, const void* operand_dev,
   static const char* who = "bcx_psvi_gradient_gaussian";
   int rc = ps_gauss_check(who, operand_dev, S, ldt, D, H_dev, k, ldh, work_dev);
   if (rc) return rc;
-  if (!colsum_dev || !corevecs_dev || !w_dev || !out_dev) return ps_arg_error(who, "null pointer");
-  if (ldcv < S) return ps_arg_error(who, "corevecs leading dimension shorter than S");
+  if (!colsum_dev || !corevecs_dev || !w_dev || !out_dev) return bcx_fail(BCX_ERR_ARG, who, "null pointer");
+  if (ldcv < S) return bcx_fail(BCX_ERR_ARG, who, "corevecs leading dimension shorter than S");
   hipStream_t st = (hipStream_t)stream;
   const double* op = (const double*)operand_dev;
   const double* cv = (const double*)corevecs_dev;
@@ -394,12 +381,12 @@ extern "C" int bcx_psvi_gradient_gaussian(void* stream, const void* operand_dev,
   double* gmean = (double*)work_dev + (int64_t)k * S;
   hipLaunchKernelGGL(psvi_prep_kernel, dim3((S + 15) / 16), dim3(256), 0, st, k, S, (const double*)colsum_dev, scaling, cv, ldcv, w,
                      resid, op, ldt, D, D, gmean);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   hipLaunchKernelGGL(psvi_wgrad_kernel, dim3(k), dim3(256), 0, st, S, cv, ldcv, (const double*)resid, wgrad);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   hipLaunchKernelGGL(psvi_gauss_ugrad_kernel, dim3((D + 63) / 64), dim3(256), 0, st, op, ldt, (const double*)gmean, (const double*)resid,
                      (const double*)H_dev, ldh, w, (int)k, (int)S, (int)D, ugrad);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }
 
@@ -486,19 +473,19 @@ extern "C" int bcx_psvi_adam_step(void* stream, int32_t k, int32_t d, const void
                                   int64_t ldp, void* mom1_dev, void* mom2_dev, const void* sched_dev, int32_t step, double b1,
                                   double b2, double eps, void* XT_dev, int64_t ldk, void* y_dev, void* trace_dev) {
   static const char* who = "bcx_psvi_adam_step";
-  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return ps_arg_error(who, "k (pseudo-points) must be in 1 .. 4096");
-  if (d < 1 || d > BCX_PSVI_ADAM_MAX_COLS) return ps_arg_error(who, "d (columns of a point) must be in 1 .. 4096");
-  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return ps_arg_error(who, "S (samples) must be in 1 .. 8192");
-  if (step < 0) return ps_arg_error(who, "step must not be negative");
-  if (!grad_dev || !w_dev || !P_dev || !mom1_dev || !mom2_dev || !sched_dev) return ps_arg_error(who, "null pointer");
-  if (ldp < d || (ldp & 1)) return ps_arg_error(who, "ldp must be even and at least d (rows of the points start on 16-byte boundaries)");
-  if (((uintptr_t)P_dev | (uintptr_t)mom1_dev | (uintptr_t)mom2_dev) & 15) return ps_arg_error(who, "points and moments must be 16-byte aligned");
-  if (((uintptr_t)grad_dev | (uintptr_t)w_dev | (uintptr_t)sched_dev | (uintptr_t)trace_dev) & 7) return ps_arg_error(who, "misaligned pointer");
+  if (k < 1 || k > BCX_PSVI_MAX_POINTS) return bcx_fail(BCX_ERR_ARG, who, "k (pseudo-points) must be in 1 .. 4096");
+  if (d < 1 || d > BCX_PSVI_ADAM_MAX_COLS) return bcx_fail(BCX_ERR_ARG, who, "d (columns of a point) must be in 1 .. 4096");
+  if (S < 1 || S > BCX_PSVI_MAX_SAMPLES) return bcx_fail(BCX_ERR_ARG, who, "S (samples) must be in 1 .. 8192");
+  if (step < 0) return bcx_fail(BCX_ERR_ARG, who, "step must not be negative");
+  if (!grad_dev || !w_dev || !P_dev || !mom1_dev || !mom2_dev || !sched_dev) return bcx_fail(BCX_ERR_ARG, who, "null pointer");
+  if (ldp < d || (ldp & 1)) return bcx_fail(BCX_ERR_ARG, who, "ldp must be even and at least d (rows of the points start on 16-byte boundaries)");
+  if (((uintptr_t)P_dev | (uintptr_t)mom1_dev | (uintptr_t)mom2_dev) & 15) return bcx_fail(BCX_ERR_ARG, who, "points and moments must be 16-byte aligned");
+  if (((uintptr_t)grad_dev | (uintptr_t)w_dev | (uintptr_t)sched_dev | (uintptr_t)trace_dev) & 7) return bcx_fail(BCX_ERR_ARG, who, "misaligned pointer");
   if (XT_dev) {
-    if (!y_dev) return ps_arg_error(who, "the mirror needs both XT and y");
-    if (d < 2) return ps_arg_error(who, "the mirror needs a feature and the response (d >= 2)");
-    if (ldk < ((int64_t)k + 31) / 32 * 32) return ps_arg_error(who, "ldk must be at least k rounded up to 32");
-    if (((uintptr_t)XT_dev | (uintptr_t)y_dev) & 7) return ps_arg_error(who, "misaligned pointer");
+    if (!y_dev) return bcx_fail(BCX_ERR_ARG, who, "the mirror needs both XT and y");
+    if (d < 2) return bcx_fail(BCX_ERR_ARG, who, "the mirror needs a feature and the response (d >= 2)");
+    if (ldk < ((int64_t)k + 31) / 32 * 32) return bcx_fail(BCX_ERR_ARG, who, "ldk must be at least k rounded up to 32");
+    if (((uintptr_t)XT_dev | (uintptr_t)y_dev) & 7) return bcx_fail(BCX_ERR_ARG, who, "misaligned pointer");
   }
   PsaArgs a;
   a.g = (const double*)grad_dev; a.sched = (const double*)sched_dev;
@@ -506,6 +493,6 @@ extern "C" int bcx_psvi_adam_step(void* stream, int32_t k, int32_t d, const void
   a.XT = (double*)XT_dev; a.y = (double*)y_dev; a.trace = (double*)trace_dev;
   a.ldp = ldp; a.ldk = ldk; a.k = k; a.d = d; a.S = S; a.step = step; a.b1 = b1; a.b2 = b2; a.eps = eps;
   hipLaunchKernelGGL(psvi_adam_kernel, dim3((d + 15) / 16, (k + 31) / 32), dim3(256), 0, (hipStream_t)stream, a);
-  PS_HIP(hipGetLastError());
+  BCX_TRY(who, hipGetLastError());
   return BCX_OK;
 }

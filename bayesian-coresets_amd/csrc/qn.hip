@@ -331,15 +331,6 @@ __global__ __launch_bounds__(QN_BACK_THREADS) void qn_back_kernel(QnArgs a) {
 }
 
 // ---- host side -------------------------------------------------------------------------------------------------------------------------
-#define QN_HIP(call)                                                              \
-  do {                                                                            \
-    hipError_t _e = (call);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      bcx_project_set_error(std::string(#call) + ": " + hipGetErrorString(_e));   \
-      return BCX_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
-
 static int64_t qn_even(int64_t n) { return (n + 1) & ~(int64_t)1; }
 struct QnLayout { int64_t y, part, Vc, G, T, gram, total; int Sp, kp, nslab; };      // offsets in doubles; total in bytes
 static QnLayout qn_layout(int k, int S) {
@@ -368,11 +359,9 @@ extern "C" int bcx_quasi_newton_step(void* stream, int32_t k, int32_t S, const v
                                      int64_t ldc, int32_t core_is_raw, void* w_dev, const void* sched_dev, int32_t step, double tau,
                                      void* dir_dev, void* trace_dev, void* status_dev, void* work_dev, int64_t work_bytes) {
   if (k < 1 || k > QN_KMAX || S < 1 || S > QN_SMAX || ldc < S || step < 0 || !(tau >= 0.0) || !colsum_dev || !core_dev || !w_dev ||
-      !sched_dev || !status_dev || !work_dev || ((uintptr_t)work_dev & 15) || work_bytes < bcx_quasi_newton_scratch_bytes(k, S)) {
-    bcx_project_set_error("bcx_quasi_newton_step: bad arguments (1 <= k <= 4096 weights, 1 <= S <= 8192, ldc >= S, tau >= 0, 16-byte "
-                          "aligned scratch of bcx_quasi_newton_scratch_bytes(k, S) bytes)");
-    return BCX_ERR_ARG;
-  }
+      !sched_dev || !status_dev || !work_dev || ((uintptr_t)work_dev & 15) || work_bytes < bcx_quasi_newton_scratch_bytes(k, S))
+    return bcx_fail(BCX_ERR_ARG, "bcx_quasi_newton_step", "bad arguments (1 <= k <= 4096 weights, 1 <= S <= 8192, ldc >= S, tau >= 0, 16-byte "
+                                                          "aligned scratch of bcx_quasi_newton_scratch_bytes(k, S) bytes)");
   const QnLayout L = qn_layout(k, S);
   double* work = (double*)work_dev;
   QnArgs a;
@@ -383,15 +372,13 @@ extern "C" int bcx_quasi_newton_step(void* stream, int32_t k, int32_t S, const v
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(qn_center_kernel, dim3(L.nslab), dim3(256), 0, st, a);
   hipLaunchKernelGGL(qn_rhs_kernel, dim3(L.nslab), dim3(256), (size_t)S * sizeof(double), st, a);
-  QN_HIP(hipGetLastError());
-  if (bcx_gram_rows_tiled(st, a.Vc, k, L.Sp, (int64_t)L.Sp, a.G, (int64_t)L.kp, work + L.gram) != BCX_OK) {
-    bcx_project_set_error("bcx_quasi_newton_step: Gram kernel launch failed");
-    return BCX_ERR_HIP;
-  }
+  BCX_TRY("bcx_quasi_newton_step", hipGetLastError());
+  const int rc = bcx_gram_rows_tiled(st, a.Vc, k, L.Sp, (int64_t)L.Sp, a.G, (int64_t)L.kp, work + L.gram);
+  if (rc != BCX_OK) return rc;                        // (the text names bcx_gram, whose kernel it is)
   if (k <= QN_SINGLE_MAX) {
     const size_t lds = QN_SMALL_LDS(k);
     static PerDevice<size_t> lds_max;
-    QN_HIP(raise_dynamic_lds((const void*)qn_small_kernel, lds, 32 * 1024, lds_max));
+    BCX_TRY("bcx_quasi_newton_step", raise_dynamic_lds((const void*)qn_small_kernel, lds, 32 * 1024, lds_max));
     hipLaunchKernelGGL(qn_small_kernel, dim3(1), dim3(QN_SMALL_THREADS), lds, st, a);
   } else {
     for (int jj = 0; jj < L.kp; jj += QN_NB) {
@@ -405,6 +392,6 @@ extern "C" int bcx_quasi_newton_step(void* stream, int32_t k, int32_t S, const v
     }
     hipLaunchKernelGGL(qn_back_kernel, dim3(1), dim3(QN_BACK_THREADS), 0, st, a);
   }
-  QN_HIP(hipGetLastError());
+  BCX_TRY("bcx_quasi_newton_step", hipGetLastError());
   return BCX_OK;
 }

@@ -610,26 +610,15 @@ __global__ __launch_bounds__(256) void svi_colmean_kernel(const double* __restri
   if (g == 0 && c < ld) out[(size_t)blockIdx.x * out_stride + c] = (((sp[0][c & 63] + sp[1][c & 63]) + sp[2][c & 63]) + sp[3][c & 63]) / (double)n;
 }
 
-#define SVI_HIP(call)                                                             \
-  do {                                                                            \
-    hipError_t _e = (call);                                                       \
-    if (_e != hipSuccess) {                                                       \
-      bcx_project_set_error(std::string(#call) + ": " + hipGetErrorString(_e));   \
-      return BCX_ERR_HIP;                                                         \
-    }                                                                             \
-  } while (0)
-
 extern "C" int bcx_linreg_posterior_draw(void* stream, int32_t k, int32_t D, int32_t ld, const void* w_dev, const void* K0_dev,
                                          const void* xmu0_dev, const void* y_dev, const void* XU0_dev, const void* XS0_dev,
                                          const void* U0T_dev, const void* mu0_dev, double sigsq, const void* R_dev,
                                          const void* Rbar_dev, int32_t S, void* theta_dev, void* tbar_dev) {
   if (k < 0 || k > LRS_KMAX || D < 1 || ld < D || (ld & 1) || S < 1 || S > LRS_SMAX || !(sigsq > 0.0) || !U0T_dev || !mu0_dev ||
       !R_dev || !Rbar_dev || !theta_dev || !tbar_dev || (k > 0 && (!w_dev || !K0_dev || !xmu0_dev || !y_dev || !XU0_dev || !XS0_dev)) ||
-      ((uintptr_t)R_dev & 15) || ((uintptr_t)Rbar_dev & 15)) {
-    bcx_project_set_error("bcx_linreg_posterior_draw: bad arguments (k <= 64 points, even leading dimension, "
-                          "16-byte aligned normal draws)");
-    return BCX_ERR_ARG;
-  }
+      ((uintptr_t)R_dev & 15) || ((uintptr_t)Rbar_dev & 15))
+    return bcx_fail(BCX_ERR_ARG, "bcx_linreg_posterior_draw", "bad arguments (k <= 64 points, even leading dimension, "
+                                                              "16-byte aligned normal draws)");
   LrsArgs a;
   a.w = (const double*)w_dev; a.K0 = (const double*)K0_dev; a.xmu0 = (const double*)xmu0_dev; a.y = (const double*)y_dev;
   a.XU0 = (const double*)XU0_dev; a.XS0 = (const double*)XS0_dev; a.U0T = (const double*)U0T_dev; a.mu0 = (const double*)mu0_dev;
@@ -638,7 +627,7 @@ extern "C" int bcx_linreg_posterior_draw(void* stream, int32_t k, int32_t D, int
   static const char* dbg = bcx_dev_env("BCX_SVI_DBG");
   a.dbg = dbg ? atoi(dbg) : 0;
   hipLaunchKernelGGL(lrs_draw_kernel, dim3((ld + 15) / 16, (S + 1 + 63) / 64), dim3(256), 0, (hipStream_t)stream, a);
-  SVI_HIP(hipGetLastError());
+  BCX_TRY("bcx_linreg_posterior_draw", hipGetLastError());
   return BCX_OK;
 }
 
@@ -652,10 +641,8 @@ extern "C" int bcx_linreg_posterior_apply(void* stream, int32_t k, int32_t D, in
                                           void* theta_dev, void* tbar_dev, const void* gscale_dev) {
   if (!bcx_linreg_posterior_apply_ok(k, ld) || D < 1 || ld < D || (ld & 1) || S < 1 || !(sigsq > 0.0) || !w_dev || !K0_dev || !xmu0_dev ||
       !y_dev || !X_dev || !XS0_dev || !mu0_dev || !G_dev || !Gbar_dev || !theta_dev || !tbar_dev ||
-      (((uintptr_t)G_dev | (uintptr_t)Gbar_dev | (uintptr_t)XS0_dev | (uintptr_t)theta_dev | (uintptr_t)gscale_dev) & 15)) {
-    bcx_project_set_error("bcx_linreg_posterior_apply: bad arguments (see bcx_linreg_posterior_apply_ok; 16-byte aligned rows)");
-    return BCX_ERR_ARG;
-  }
+      (((uintptr_t)G_dev | (uintptr_t)Gbar_dev | (uintptr_t)XS0_dev | (uintptr_t)theta_dev | (uintptr_t)gscale_dev) & 15))
+    return bcx_fail(BCX_ERR_ARG, "bcx_linreg_posterior_apply", "bad arguments (see bcx_linreg_posterior_apply_ok; 16-byte aligned rows)");
   LraArgs a;
   a.w = (const double*)w_dev; a.K0 = (const double*)K0_dev; a.xmu0 = (const double*)xmu0_dev; a.y = (const double*)y_dev;
   a.X = (const double*)X_dev; a.XS0 = (const double*)XS0_dev; a.mu0 = (const double*)mu0_dev; a.G = (const double*)G_dev;
@@ -663,9 +650,9 @@ extern "C" int bcx_linreg_posterior_apply(void* stream, int32_t k, int32_t D, in
   a.sigsq = sigsq; a.k = k; a.D = D; a.S = S; a.ld = ld;
   const size_t lds = (size_t)2 * k * ld * sizeof(double);
   static PerDevice<size_t> lds_max;      // per DEVICE (a process may drive several): the largest request so far on the current one
-  SVI_HIP(raise_dynamic_lds((const void*)lrs_apply_kernel, lds, 32 * 1024, lds_max));
+  BCX_TRY("bcx_linreg_posterior_apply", raise_dynamic_lds((const void*)lrs_apply_kernel, lds, 32 * 1024, lds_max));
   hipLaunchKernelGGL(lrs_apply_kernel, dim3((S + 1 + 3) / 4), dim3(256), lds, (hipStream_t)stream, a);
-  SVI_HIP(hipGetLastError());
+  BCX_TRY("bcx_linreg_posterior_apply", hipGetLastError());
   return BCX_OK;
 }
 
@@ -673,14 +660,12 @@ extern "C" int bcx_sparsevi_adam_step(void* stream, int32_t k, int32_t S, const 
                                       int64_t ldc, void* w_dev, void* mom1_dev, void* mom2_dev, const void* sched_dev, int32_t step,
                                       double b1, double b2, double eps, void* trace_dev, int32_t core_is_raw) {
   if (k < 1 || k > LRS_KMAX || S < 1 || S > 8192 || ldc < S || step < 0 || !colsum_dev || !core_dev || !w_dev || !mom1_dev ||
-      !mom2_dev || !sched_dev) {
-    bcx_project_set_error("bcx_sparsevi_adam_step: bad arguments (1 <= k <= 64 weights, S <= 8192)");
-    return BCX_ERR_ARG;
-  }
+      !mom2_dev || !sched_dev)
+    return bcx_fail(BCX_ERR_ARG, "bcx_sparsevi_adam_step", "bad arguments (1 <= k <= 64 weights, S <= 8192)");
   hipLaunchKernelGGL(svi_adam_kernel, dim3(1), dim3(256), (size_t)S * sizeof(double), (hipStream_t)stream, (const double*)colsum_dev,
                      scaling, (const double*)core_dev, ldc, (int)k, (int)S, (double*)w_dev, (double*)mom1_dev, (double*)mom2_dev,
                      (const double*)sched_dev, (int)step, b1, b2, eps, (double*)trace_dev, (int)core_is_raw);
-  SVI_HIP(hipGetLastError());
+  BCX_TRY("bcx_sparsevi_adam_step", hipGetLastError());
   return BCX_OK;
 }
 
@@ -699,11 +684,9 @@ extern "C" int bcx_sparsevi_adam_step_ws(void* stream, int32_t k, int32_t S, con
     return bcx_sparsevi_adam_step(stream, k, S, colsum_dev, scaling, core_dev, ldc, w_dev, mom1_dev, mom2_dev, sched_dev, step, b1, b2, eps,
                                   trace_dev, core_is_raw);
   if (k < 1 || k > SVB_KMAX || S < 1 || S > 8192 || ldc < S || step < 0 || !colsum_dev || !core_dev || !w_dev || !mom1_dev || !mom2_dev ||
-      !sched_dev || !work_dev || work_bytes < bcx_sparsevi_adam_scratch_bytes(k, S)) {
-    bcx_project_set_error("bcx_sparsevi_adam_step_ws: bad arguments (1 <= k <= 4096 weights, S <= 8192, scratch of "
-                          "bcx_sparsevi_adam_scratch_bytes(k, S) bytes)");
-    return BCX_ERR_ARG;
-  }
+      !sched_dev || !work_dev || work_bytes < bcx_sparsevi_adam_scratch_bytes(k, S))
+    return bcx_fail(BCX_ERR_ARG, "bcx_sparsevi_adam_step_ws", "bad arguments (1 <= k <= 4096 weights, S <= 8192, scratch of "
+                                                              "bcx_sparsevi_adam_scratch_bytes(k, S) bytes)");
   SvbArgs a;
   a.colsum = (const double*)colsum_dev; a.core = (const double*)core_dev; a.sched = (const double*)sched_dev;
   a.w = (double*)w_dev; a.mom1 = (double*)mom1_dev; a.mom2 = (double*)mom2_dev; a.trace = (double*)trace_dev;
@@ -712,7 +695,7 @@ extern "C" int bcx_sparsevi_adam_step_ws(void* stream, int32_t k, int32_t S, con
   const int nslab = (k + SVB_ROWS - 1) / SVB_ROWS;
   hipLaunchKernelGGL(svi_adam_a_kernel, dim3(nslab), dim3(256), 0, (hipStream_t)stream, a);
   hipLaunchKernelGGL(svi_adam_b_kernel, dim3(nslab), dim3(256), (size_t)S * sizeof(double), (hipStream_t)stream, a);
-  SVI_HIP(hipGetLastError());
+  BCX_TRY("bcx_sparsevi_adam_step_ws", hipGetLastError());
   return BCX_OK;
 }
 
@@ -720,24 +703,22 @@ extern "C" int bcx_sparsevi_adam_step_ws(void* stream, int32_t k, int32_t S, con
 // pair counters offset .. offset + ceil(count / 2) - 1 under the key `seed` -- a caller that advances `offset` by
 // ceil(count / 2) per call draws one reproducible stream.
 extern "C" int bcx_standard_normal(void* stream, uint64_t seed, uint64_t offset, int64_t count, void* out_dev) {
-  if (count < 0 || (count > 0 && !out_dev)) { bcx_project_set_error("bcx_standard_normal: bad arguments"); return BCX_ERR_ARG; }
+  if (count < 0 || (count > 0 && !out_dev)) return bcx_fail(BCX_ERR_ARG, "bcx_standard_normal", "bad arguments");
   if (count == 0) return BCX_OK;
   const int64_t pairs = (count + 1) / 2;
   hipLaunchKernelGGL(svi_normal_kernel, dim3((unsigned)((pairs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, (double*)out_dev, count,
                      (unsigned long long)seed, (unsigned long long)offset);
-  SVI_HIP(hipGetLastError());
+  BCX_TRY("bcx_standard_normal", hipGetLastError());
   return BCX_OK;
 }
 // out_dev[b * out_stride + c] = mean over the n rows of block b of rows_dev (nblocks blocks of n x ld doubles, block_stride doubles
 // apart): the column means of every ADAM step's normal numbers in one launch.
 extern "C" int bcx_column_means(void* stream, const void* rows_dev, int32_t nblocks, int32_t n, int32_t ld, int64_t block_stride,
                                 void* out_dev, int64_t out_stride) {
-  if (nblocks < 1 || n < 1 || ld < 1 || block_stride < 0 || out_stride < ld || !rows_dev || !out_dev) {
-    bcx_project_set_error("bcx_column_means: bad arguments");
-    return BCX_ERR_ARG;
-  }
+  if (nblocks < 1 || n < 1 || ld < 1 || block_stride < 0 || out_stride < ld || !rows_dev || !out_dev)
+    return bcx_fail(BCX_ERR_ARG, "bcx_column_means", "bad arguments");
   hipLaunchKernelGGL(svi_colmean_kernel, dim3(nblocks, (ld + 63) / 64), dim3(256), 0, (hipStream_t)stream, (const double*)rows_dev, (int)n,
                      (int)ld, block_stride, (double*)out_dev, out_stride);
-  SVI_HIP(hipGetLastError());
+  BCX_TRY("bcx_column_means", hipGetLastError());
   return BCX_OK;
 }

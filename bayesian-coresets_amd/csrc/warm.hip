@@ -385,7 +385,7 @@ int bcx_warm_start(bcx_solver* s, int k, void* buf, double* gram_work, const int
   wb.rej = (int32_t*)base; base += (size_t)kp * 4;
   wb.keptq = (int32_t*)base; base += (size_t)kp * 4;
   wb.p = (int32_t*)base;                          // [0] size of the passive set, [1] columns accepted so far (Cholesky)
-  if (hipMemsetAsync(wb.p, 0, 2 * sizeof(int32_t), s->stream) != hipSuccess) return BCX_ERR_HIP;
+  BCX_HIP(hipMemsetAsync(wb.p, 0, 2 * sizeof(int32_t), s->stream));
   hipStream_t st = s->stream;
   hipLaunchKernelGGL(warm_order_kernel, dim3((kp + 255) / 256), dim3(256), (size_t)k * 8, st, (const double*)s->act_w, (const double*)s->act_norm, k, kp, wb);
   hipLaunchKernelGGL(warm_gather_kernel, dim3((kp + 255) / 256, kp), dim3(256), 0, st, (const double*)s->gram, (int64_t)s->gram_cap, k, kp, wb);
@@ -403,7 +403,7 @@ int bcx_warm_start(bcx_solver* s, int k, void* buf, double* gram_work, const int
   warm_invert(s, st, kp, wb, 0, np);                         // Y = L^-T
   BCX_HIP(hipGetLastError());
   const int rc = bcx_gram_rows(st, wb.Y, kp, kp, (int64_t)kp, wb.A, (int64_t)kp, gram_work);      // H = Y Y^T (fp64 MFMA)
-  if (rc != BCX_OK) { s->err = "optimize: Gram kernel (inverse) launch failed"; return rc; }
+  if (rc != BCX_OK) { s->err = std::string("optimize: Gram kernel (inverse) launch failed: ") + bcx_fail_text(); return rc; }
   hipLaunchKernelGGL(warm_scan_kernel, dim3(1), dim3(1024), 0, st, k, kp, wb, s->plist);
   hipLaunchKernelGGL(warm_compact_kernel, dim3((kp + 255) / 256, kp), dim3(256), 0, st, kp, wb, s->hinv, s->hinv_lo, (int64_t)s->gram_cap);
   BCX_HIP(hipGetLastError());

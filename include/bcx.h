@@ -501,6 +501,10 @@ int bcx_gram_check(void* stream, const void* work_dev);
  * row's sum of squares to out_dev (N doubles) -- the subsample branch drops the rows where it is zero. */
 int bcx_center_rows(void* stream, void* rows_dev, int64_t N, int32_t S, int64_t ld);
 int bcx_row_sumsq(void* stream, const void* rows_dev, int64_t N, int32_t S, int64_t ld, void* out_dev);
+/* The text of the calling host thread's last failure in an entry point that takes no bcx_solver* (projection, moments, Gram,
+ * PSVI, SVI, quasi-Newton, Gaussian, linear-regression posterior, Laplace, HMC, NUTS, predictive, pair statistics):
+ * "<entry point>: <what>", and for BCX_ERR_HIP "<entry point>: <the HIP call>: <HIP's reason>".  One string per thread: "" before
+ * that thread's first failure, valid and unchanged until its next one; a call that succeeds leaves it alone. */
 const char* bcx_project_last_error(void);
 /* Measurement: hipEvents around the projection kernel alone, recorded on the stream the kernel is launched on.
  * bcx_project_profile(1) starts timing every later projection launch of the calling host thread, (0) stops;
